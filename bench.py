@@ -9,9 +9,13 @@ N=1 workload = BASELINE.json configs[1]: ViT-L/14 random-init, 1 object x 162 te
 N>1 (one rank per GPU, torch.distributed / RCCL): weak scaling, B crops per rank, template bank
 sharded by template index with the two all-gathers of gigapose_amd/sharding.py (configs[3] shape).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (dominant kernel
-family timed by HIP events on the launch stream inside the timed region) and `cpu_baseline` (the
-CPU oracle port timed on the host cores on a bounded sample; N=1 only).
+Prints ONE JSON line on rank 0.  A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the headline (`value`, `ms_per_step`, `dtype`, `config`) -- nothing else.  `--full` adds
+everything else this file measures: `roofline` (dominant kernel family timed by HIP events on the launch stream
+inside the timed region, a per-family replay, the matrix-ceiling micro-benchmark), the other numerics modes, the
+BASELINE config-3 / config-5 shapes and the batch curve, the drop-in flow, the other multi-GPU mode (N > 1) and
+`cpu_baseline` (the CPU oracle port timed on the host cores on a bounded sample; N=1 only).
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -37,6 +41,33 @@ sys.path.insert(0, ROOT)
 F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X dense f32-input MFMA peak (MI355X_MICROARCH.md)
 FLOP_PER_CROP = {"dinov2_vitl14": 162.0e9, "dinov2_vits14": 12.25e9, "dinov2_vitb14": 0.0}
 ANCHOR_FILE = os.path.join(ROOT, "profiles", "r06_cpu_reference_vs_port.txt")
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def host_outputs(pred):
+    """The arrays a caller of GigaPose.predict receives (every tensor of the returned collection), on the host as float32 (floating
+    tensors) or float64 (integer / bool tensors: exact for every index and count the path returns)."""
+    out = {}
+    for name, t in (pred.tensors.items() if pred is not None else ()):
+        a = t.detach().cpu()
+        if a.dtype != torch.float64:
+            a = a.float() if a.is_floating_point() else a.to(torch.float64)
+        out[name] = a.numpy()
+    return out
+
+
+def dump_outputs(outputs, out_dir):
+    """DIR/<name>.npy per output array.  Should the arrays exceed DUMP_BYTES in all (large --batch / --k), every array is replaced by a
+    fixed, seeded sample of its flattened elements (in index order), each array keeping its share of the budget."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in sorted(outputs.items()):
+        if total > DUMP_BYTES:
+            n = max(1, a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def reference_over_port(threads):
@@ -215,10 +246,11 @@ class _StubLib:
 
 class _StubModel:
     """GIGAPOSE_BENCH_STUB=1: everything of THIS FILE -- argument handling, process-group set-up, the timed region with its barriers,
-    the max-over-ranks all-reduce, the per-rank gather, the both-modes block, the rank-0-only JSON line -- runs on CPU over gloo
-    with this object in place of the model (no kernels: `predict` sleeps 2 ms and, when sharded, issues the two collectives of
-    gigapose_amd/sharding.py on small tensors).  tests/test_bench_distributed.py launches it under torch.distributed.run with two
-    ranks: the 8-GPU driver run must not be the first time this control flow executes with more than one rank."""
+    the max-over-ranks all-reduce, the per-rank gather, the both-modes block, --dump-outputs, the rank-0-only JSON line -- runs on CPU
+    over gloo with this object in place of the model (no kernels: `predict` sleeps 2 ms, when sharded issues the two collectives of
+    gigapose_amd/sharding.py on small tensors, and returns two small tensors of fixed values).  tests/test_bench_distributed.py
+    launches it under torch.distributed.run with two ranks: the 8-GPU driver run must not be the first time this control flow
+    executes with more than one rank."""
 
     def __init__(self):
         import types
@@ -253,6 +285,7 @@ class _StubModel:
         import torch.distributed as dist
 
         from gigapose_amd import sharding
+        from gigapose_amd.tensor_collection import TensorCollection
 
         time.sleep(0.002)
         if self.template_shard is not None and dist.is_initialized():
@@ -261,7 +294,8 @@ class _StubModel:
             if work is not None:
                 work.wait()
             sharding.all_to_all_rows(allrows[:, :8].contiguous(), self.template_shard[2])          # exchange #2
-        return None
+        B = tar_img.shape[0]
+        return TensorCollection(scores=torch.linspace(0.0, 1.0, B * 5).reshape(B, 5), id_src=torch.arange(B * 5).reshape(B, 5))
 
 
 def main():
@@ -275,15 +309,22 @@ def main():
     ap.add_argument("--variant", default="dinov2_vitl14")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--mode", default="auto", choices=["auto", "sharded", "replicas"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and per-family kernel table, matrix-ceiling micro-benchmark, other numerics modes, "
+                         "BASELINE config-3 / config-5 shapes and batch curve, drop-in flow, the other multi-GPU mode, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32 / float64; rank 0's crops when N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--overlap", action="store_true", help="IST backbone on a second HIP stream at every batch size (default: up to 32 crops only; at 64 crops measured 0-1 %%)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config-3 / config-5 shaped extra measurements")
-    ap.add_argument("--no-other", action="store_true", help="skip timing the other numerics mode")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the BASELINE config-3 / config-5 shaped extra measurements and the drop-in flow")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip timing the other numerics modes")
     ap.add_argument("--numerics", default="split", choices=["split", "chain"],
                     help="numerics of `value`: split = 3 x f16 MFMA on split f32 operands (f32-equivalent, DESIGN.md 2); "
-                         "chain = f32-input MFMA fmaf chain (bit-exact vs the CPU oracle).  The other mode is timed too "
+                         "chain = f32-input MFMA fmaf chain (bit-exact vs the CPU oracle).  With --full the other mode is timed too "
                          "and reported under `other_numerics` (N=1 only).")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     stub = os.environ.get("GIGAPOSE_BENCH_STUB") == "1"   # control-flow test of this file on CPU / gloo (see _StubModel); never a measurement
     if not torch.cuda.is_available() and not stub:
         sys.exit("bench.py: no GPU visible -- the hot path is HIP only (no CPU fallback); run it on an MI355X box "
@@ -365,8 +406,9 @@ def main():
             names = [lib.gp_prof_kind_name(i).decode() for i in range(kinds)]
             lib.gp_prof_begin(names.index(profile[1]), SAMPLE_STRIDE)
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = step()   # what the caller of the timed path receives from its last step (--dump-outputs)
         sync()
         t_own = time.perf_counter() - t0   # this rank's own K steps (before the closing barrier): a straggler GPU shows here
         if world > 1:
@@ -385,27 +427,32 @@ def main():
                     kern[name] = {"ms_per_step": round(ms[i] / steps, 3), "launches_per_step": cnt[i] // steps,
                                   "avg_launch_us": round(1e3 * ms[i] / cnt[i], 2), "launches_timed": int(cnt[i]),
                                   unit: round(work[i] / ms[i] / (1e6 if name == "layernorm" else 1e9), 2) if ms[i] > 0 else 0.0}
-        return dt, kern, t_own
+        return dt, kern, t_own, last
 
-    def run_mode(numerics):
-        """Onboard the bank in `numerics`, warm up, time K steps (THE timed region), then replay them with events around every
-        launch for the per-family table.  Returns (dt = max over ranks, dt_serial, kernels, sampled kernels, per-rank ms per step)."""
+    def run_mode(numerics, keep_outputs=False):
+        """Onboard the bank in `numerics`, warm up, time K steps (THE timed region), then (--full) replay them with events around every
+        launch for the per-family table.  Returns (dt = max over ranks, dt_serial, kernels, sampled kernels, per-rank ms per step,
+        the last timed step's outputs on the host if `keep_outputs`)."""
         model.set_numerics(numerics)
         model.set_template_data("syn")  # onboarding: excluded from the timed region (reference gigaPose.py:396-398)
         model.pose_recovery["syn"].check_asserts = False  # no host sync inside the timed loop
         model.overlap_ist = True if args.overlap else "auto"   # "auto" = the product default: the IST backbone on a second stream up to 32 crops only
         for _ in range(args.warmup):
             step()
-        # THE timed region: K steps; HIP events on the launch stream around one in SAMPLE_STRIDE launches of the dominant kernel
-        # family (roofline.achieved comes from these).  Bracketing all ~210 launches of a step costs 1.4 ms of queue time per
+        # THE timed region: K steps.  --full: HIP events on the launch stream around one in SAMPLE_STRIDE launches of the dominant
+        # kernel family (roofline.achieved comes from these).  Bracketing all ~210 launches of a step costs 1.4 ms of queue time per
         # step (measured A/B, 46.3 vs 44.9 ms), so the per-family table comes from a second, untimed replay with full events.
         dominant = "gemm_split" if numerics == "split" else "gemm_kmajor"
-        dt, kern_timed, t_own = timed(args.steps, profile=("sampled", dominant))
+        dt, kern_timed, t_own, last = timed(args.steps, profile=("sampled", dominant) if args.full else None)
         _lib.check_status()  # guard rails (lost hand-off / split range / labels): read once, outside the timed region
-        overlap = model.overlap_ist
-        model.overlap_ist = False
-        dt_serial, kern, _ = timed(args.steps, profile="all")
-        model.overlap_ist = overlap
+        outputs = host_outputs(last) if keep_outputs else None   # now: a later predict() may reuse the buffers behind them
+        del last
+        dt_serial, kern = None, {}
+        if args.full:
+            overlap = model.overlap_ist
+            model.overlap_ist = False
+            dt_serial, kern, _, _ = timed(args.steps, profile="all")
+            model.overlap_ist = overlap
         per_rank = [round(1e3 * t_own / args.steps, 3)]
         if world > 1:
             tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -415,9 +462,45 @@ def main():
             every = torch.empty(world, device=dev, dtype=torch.float64)
             dist.all_gather_into_tensor(every, mine)
             per_rank = [round(1e3 * float(t) / args.steps, 3) for t in every.tolist()]
-        return dt, dt_serial, kern, kern_timed, per_rank
+        return dt, dt_serial, kern, kern_timed, per_rank, outputs
 
-    dt, dt_serial, kern, kern_timed, per_rank_ms = run_mode(args.numerics)
+    def headline(dt, per_rank_ms):
+        """The result line's headline fields: what a plain run prints, and what --full prints ahead of its extras."""
+        out = {
+            "metric": "query-crops/sec (ViT feat + template NN + 4DoF regress), 162 templates, 1/2/4/8 GPU",
+            "value": round(world * args.batch * args.steps / dt, 2), "unit": "query-crops/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": ("f32 (ViT linear layers + attention, matcher, IST convolutions: f32 operands split into f16 hi/lo, 3 x f16 MFMA per k-block, f32 accumulate -- "
+                      "error vs f64 below the f32 fmaf chain's, tests/test_gpu_split.py; everything else f32)"
+                      if args.numerics == "split" else "f32"),
+            "data": "synthetic",
+            "config": {"workload": f"BASELINE configs[1]: {args.variant} random-init, {args.objects} object(s) x {args.templates} templates, "
+                                   f"batch={args.batch} crops per GPU, k={args.k}, full path ViT->match->IST->RANSAC->pose",
+                       "numerics": args.numerics, "global_batch": world * args.batch,
+                       "parallelism": f"{mode}{world}" if (world > 1 or (mode == "sharded" and dist.is_initialized())) else "single",
+                       "streams": ("ViT+match on stream 0, IST backbone on stream 1"
+                                   if (model.overlap_ist is True or (model.overlap_ist == "auto" and args.batch <= 32)) else "single stream"),
+                       "rccl_ranks": world if dist.is_initialized() else 0,   # = N under the launcher: one rank per GPU
+                       "per_rank_ms_per_step": per_rank_ms,                  # each rank's own K steps before the closing barrier (a straggler GPU shows here)
+                       "collective_backend": (dist.get_backend() if dist.is_initialized() else None),
+                       "host_syncs_in_timed_loop": "none: pose recovery's crop-transform assert readback (reference lib3d/torch.py:54-55) is "
+                                                   "disabled for the loop (check_asserts=False); the device status word is read once after it"},
+        }
+        if stub:
+            out["data"] = "STUB (GIGAPOSE_BENCH_STUB=1): control-flow test of bench.py on CPU / gloo, no kernels -- not a measurement"
+        return out
+
+    dt, dt_serial, kern, kern_timed, per_rank_ms, outputs = run_mode(args.numerics, keep_outputs=args.dump_outputs is not None and rank == 0)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            emit(json.dumps(headline(dt, per_rank_ms)))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     # N > 1: the same job once more in the OTHER multi-GPU mode, so that one driver run reports both -- "sharded" (north_star's
     # template-bank partition: two exchanges per step) and "replicas" (full bank per GPU, no data-path collective).  Weak scaling
     # either way; in sharded mode every rank still matches all W * B crops against its 1 / W of the bank, so it saves memory,
@@ -432,7 +515,7 @@ def main():
                 model.template_shard = None
             else:
                 model.enable_template_sharding()
-            adt, _, akern, _, aper = run_mode(args.numerics)
+            adt, _, akern, _, aper, _ = run_mode(args.numerics)
             other_modes = {alt: {"value": round(world * args.batch * args.steps / adt, 2), "unit": "query-crops/sec",
                                  "ms_per_step": round(1e3 * adt / args.steps, 3), "parallelism": f"{alt}{world}",
                                  "per_rank_ms_per_step": aper,
@@ -474,7 +557,7 @@ def main():
 
         other_mode = "chain" if args.numerics == "split" else "split"
         try:
-            odt, odt_serial, okern, _, _ = run_mode(other_mode)
+            odt, odt_serial, okern, _, _, _ = run_mode(other_mode)
             other[other_mode] = numerics_entry(other_mode, odt, odt_serial, okern,
                                                "verification mode: f32-input MFMA fmaf chains, bit-exact vs the CPU oracle" if other_mode == "chain" else None)
         except Exception as e:
@@ -487,7 +570,7 @@ def main():
             vit.set_split_gemm("128")
             ist.conv_kernel = "128"
             ist.invalidate()
-            odt, odt_serial, okern, _, _ = run_mode("split")
+            odt, odt_serial, okern, _, _, _ = run_mode("split")
             other["split128"] = numerics_entry("split128", odt, odt_serial, okern,
                                                "the mode the automatic range fallback selects (|activation| >= 8190): 128 x 128 two-accumulator kernels, range 65504")
         except Exception as e:
@@ -507,7 +590,7 @@ def main():
             keep_sd = {k: v.detach().clone() for k, v in vit.state_dict().items()}
             syn_.plant_dinov2_outliers(vit)
             try:
-                odt, odt_serial, okern, _, _ = run_mode("split")
+                odt, odt_serial, okern, _, _, _ = run_mode("split")
                 e = numerics_entry("split_outliers", odt, odt_serial, okern,
                                    "planted DINOv2-like outliers; per-tensor plane scales calibrated at onboarding (vit.py: calibrate_plane_scales), "
                                    "all GEMMs on the 256 x 256 plane kernels")
@@ -744,7 +827,6 @@ def main():
         dist.destroy_process_group()
         return
 
-    crops = world * args.batch * args.steps
     # HBM traffic of the dominant kernel family from the committed PMC passes of this same command (tools/pmc_bench.sh;
     # counters cannot be collected from inside the timed run): bytes per launch, corrected as the MI355X guide says
     traffic = None
@@ -826,27 +908,8 @@ def main():
                     "(bracketing all ~210 launches of a step costs 1.4 ms of queue time per step, so it is kept out of `value`)",
         "replay_ms_per_step_with_all_events": round(1e3 * dt_serial / args.steps, 3), "kernels": kern,
         "timed_region_sample": {k: {"launches_timed": v["launches_timed"], "avg_launch_us": v["avg_launch_us"]} for k, v in kern_timed.items()}})
-    out = {
-        "metric": "query-crops/sec (ViT feat + template NN + 4DoF regress), 162 templates, 1/2/4/8 GPU",
-        "value": round(crops / dt, 2), "unit": "query-crops/sec", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": ("f32 (ViT linear layers + attention, matcher, IST convolutions: f32 operands split into f16 hi/lo, 3 x f16 MFMA per k-block, f32 accumulate -- "
-                  "error vs f64 below the f32 fmaf chain's, tests/test_gpu_split.py; everything else f32)"
-                  if args.numerics == "split" else "f32"),
-        "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[1]: {args.variant} random-init, {args.objects} object(s) x {args.templates} templates, "
-                               f"batch={args.batch} crops per GPU, k={args.k}, full path ViT->match->IST->RANSAC->pose",
-                   "numerics": args.numerics, "global_batch": world * args.batch, "parallelism": f"{mode}{world}" if (world > 1 or (mode == "sharded" and dist.is_initialized())) else "single",
-                   "streams": ("ViT+match on stream 0, IST backbone on stream 1"
-                               if (model.overlap_ist is True or (model.overlap_ist == "auto" and args.batch <= 32)) else "single stream"),
-                   "rccl_ranks": world if dist.is_initialized() else 0,   # = N under the launcher: one rank per GPU
-                   "per_rank_ms_per_step": per_rank_ms,                  # each rank's own K steps before the closing barrier (a straggler GPU shows here)
-                   "collective_backend": (dist.get_backend() if dist.is_initialized() else None),
-                   "host_syncs_in_timed_loop": "none: pose recovery's crop-transform assert readback (reference lib3d/torch.py:54-55) is "
-                                               "disabled for the loop (check_asserts=False); the device status word is read once after it"},
-        "roofline": roofline,
-    }
+    out = headline(dt, per_rank_ms)
+    out["roofline"] = roofline
     if other_modes is not None:
         out["other_modes"] = other_modes
     if other is not None:
@@ -857,8 +920,6 @@ def main():
         out["batch_curve"] = batch_curve
     if dropin_flow:
         out["dropin_flow"] = dropin_flow
-    if stub:
-        out["data"] = "STUB (GIGAPOSE_BENCH_STUB=1): control-flow test of bench.py on CPU / gloo, no kernels -- not a measurement"
     if world == 1 and not args.no_cpu_baseline and not stub:
         try:
             out["cpu_baseline"] = cpu_baseline(args.variant, args.templates, args.k)

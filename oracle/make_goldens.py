@@ -447,7 +447,29 @@ def gen_bop_csv():
     print("bop_csv:", [k for k in gold if k != "seed"])
 
 
-STAGES = {"bop_csv": gen_bop_csv, "val": gen_val, "matcher": gen_matcher, "matcher_variants": gen_matcher_variants, "ist": gen_ist, "pose": gen_pose, "pose_scored": gen_pose_scored, "e2e": gen_e2e, "crop": gen_crop,
+def gen_signatures():
+    """The reference's constructor / method signatures of the classes a Hydra `_target_` swap replaces (tests/test_dropin_signatures.py:
+    PAIRS) -> reference_signatures.json, and its model config composed and `_target_`-swapped (tests/dropin_flow.py) ->
+    model_cfg_resolved.json: the drop-in tests compare the mirrors against these two files."""
+    import importlib
+    import json
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dropin_flow
+    from test_dropin_signatures import PAIRS, signature
+
+    ref_shim.install()
+    sigs = {}
+    for ref_mod, cls, _, methods in PAIRS:
+        ref = getattr(importlib.import_module(ref_mod), cls)
+        sigs[f"{ref_mod}.{cls}"] = {name: signature(getattr(ref, name)) for name in ["__init__"] + methods}
+    json.dump(sigs, open(os.path.join(GOLD, "reference_signatures.json"), "w"), indent=1, sort_keys=True)
+    cfg = dropin_flow.compose_reference_model_cfg(ref_shim.REFERENCE_ROOT, save_dir="<save_dir>")
+    json.dump(cfg, open(os.path.join(GOLD, "model_cfg_resolved.json"), "w"), indent=1, sort_keys=True)
+    print("signatures:", len(sigs), "classes; model config:", cfg["_target_"])
+
+
+STAGES = {"signatures": gen_signatures, "bop_csv": gen_bop_csv, "val": gen_val, "matcher": gen_matcher, "matcher_variants": gen_matcher_variants, "ist": gen_ist, "pose": gen_pose, "pose_scored": gen_pose_scored, "e2e": gen_e2e, "crop": gen_crop,
           "matcher_big": lambda: gen_matcher_big(["match_cfg2", "match_cfg3"]), "matcher_cfg5": lambda: gen_matcher_big(["match_cfg5"]), "e2e_cfg2": lambda: gen_e2e("e2e_cfg2"), "e2e_cfg3": lambda: gen_e2e("e2e_cfg3"),
           "e2e_cfg2_f64": lambda: gen_e2e_f64("e2e_cfg2"), "e2e_cfg3_f64": lambda: gen_e2e_f64("e2e_cfg3"), "e2e_f64": lambda: gen_e2e_f64("e2e")}
 

@@ -1,15 +1,17 @@
 """CPU: bench.py's OWN main() under `torch.distributed.run` with two ranks (gloo) and a stub model (GIGAPOSE_BENCH_STUB=1: no
 kernels, bench.py: _StubModel).  The driver's 8-GPU scaling run must not be the first time the N > 1 control flow of this file
 executes: process-group set-up from the launcher's environment, the timed region's barriers, the max-over-ranks all-reduce, the
-per-rank gather, the both-modes block (sharded AND replicas in one run, with the sharded pass issuing the two exchanges of
-gigapose_amd/sharding.py), the failure flag exchange, and the rank-0-only single JSON line."""
+per-rank gather, the both-modes block of --full (sharded AND replicas in one run, with the sharded pass issuing the two exchanges of
+gigapose_amd/sharding.py), the failure flag exchange, --dump-outputs, and the rank-0-only single JSON line."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,7 +40,7 @@ def launch(nproc, extra, timeout=240):
 
 @pytest.mark.parametrize("mode,alt", [("auto", "replicas"), ("replicas", "sharded")])
 def test_bench_main_world2_prints_one_line_with_both_modes(mode, alt):
-    out = launch(2, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--mode", mode])
+    out = launch(2, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--mode", mode, "--full"])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert out["metric"].startswith("query-crops/sec") and out["unit"] == "query-crops/sec" and out["higher_is_better"] is True
     cfg = out["config"]
@@ -90,10 +92,38 @@ def test_bench_main_world8_prints_one_line_with_both_modes():
     """The shape of the driver's scaling run at N = 8 (one rank per GPU of a node): eight gloo ranks through bench.py's own main() with the
     stub model -- the both-modes block with the two exchanges of gigapose_amd/sharding.py among eight ranks, the max-over-ranks time, the
     per-rank gather of eight entries, one JSON line."""
-    out = launch(8, ["--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "4"], timeout=400)
+    out = launch(8, ["--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "4", "--full"], timeout=400)
     cfg = out["config"]
     assert out["n_gpus"] == 8 and cfg["rccl_ranks"] == 8 and cfg["global_batch"] == 32 and cfg["parallelism"] == "sharded8"
     assert len(cfg["per_rank_ms_per_step"]) == 8 and out["scaling"] == "weak"
     other = out["other_modes"]["replicas"]
     assert "error" not in other and other["parallelism"] == "replicas8" and len(other["per_rank_ms_per_step"]) == 8
     assert abs(out["value"] - 8 * 4 * 2 / (out["ms_per_step"] * 2 / 1e3)) / out["value"] < 1e-3
+
+
+def test_bench_plain_world2_prints_the_headline_only():
+    """Without --full a run times its K steps and prints the headline: no second multi-GPU mode, no roofline."""
+    out = launch(2, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4"])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["config"]["parallelism"] == "sharded2"
+    assert len(out["config"]["per_rank_ms_per_step"]) == 2
+    assert abs(out["value"] - 2 * 4 * 3 / (out["ms_per_step"] * 3 / 1e3)) / out["value"] < 1e-3
+    assert "other_modes" not in out and "roofline" not in out
+
+
+def test_bench_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs DIR: every array the timed path returned, as DIR/<name>.npy in float32 (floating) or float64 (integer)."""
+    launch(1, ["--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path)])
+    assert sorted(os.listdir(tmp_path)) == ["id_src.npy", "scores.npy"]
+    scores, ids = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "id_src.npy")
+    assert scores.dtype == np.float32 and ids.dtype == np.float64 and scores.shape == ids.shape == (4, 5)
+    assert (scores.reshape(-1) == torch.linspace(0.0, 1.0, 20).numpy()).all() and (ids.reshape(-1) == np.arange(20)).all()
+
+
+def test_bench_dump_outputs_samples_beyond_64_mb(tmp_path):
+    """Outputs larger than 64 MB in all are written as a fixed, seeded sample of each array, in index order, within the budget."""
+    B = 1_200_000   # 5 float32 + 5 float64 per crop: 72 MB
+    launch(1, ["--steps", "1", "--warmup", "0", "--batch", str(B), "--dump-outputs", str(tmp_path)])
+    scores, ids = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "id_src.npy")
+    assert scores.nbytes + ids.nbytes <= 64 << 20 and scores.ndim == ids.ndim == 1 and 0 < ids.size < 5 * B
+    assert (np.diff(ids) > 0).all() and ids.max() < 5 * B and (ids == np.round(ids)).all()
+    assert np.array_equal(scores, torch.linspace(0.0, 1.0, 5 * B).numpy()[ids.astype(np.int64)])

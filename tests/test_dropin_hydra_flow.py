@@ -1,25 +1,22 @@
-"""CPU, build container (needs the reference's config files): the reference's OWN model config -- configs/model/large.yaml with its
-defaults -- instantiates into the gigapose_amd classes after the `_target_` swap of INTEGRATION.md section 1, every YAML key being a
-constructor argument the mirror accepts; the resolved config is committed (tests/golden/model_cfg_resolved.json) so that the GPU
-box, which has no reference tree, builds the model from the same file (tests/test_gpu_dropin_flow.py)."""
+"""CPU: the reference's OWN model config -- configs/model/large.yaml with its defaults -- instantiates into the gigapose_amd classes
+after the `_target_` swap of INTEGRATION.md section 1, every YAML key being a constructor argument the mirror accepts.  The resolved
+config is committed (tests/golden/model_cfg_resolved.json, written from the reference's config files by `oracle/make_goldens.py
+signatures`), so the test needs no reference tree; where one is present, the file is checked against a fresh composition.  The GPU
+test of the same flow builds its model from this file too (tests/test_gpu_dropin_flow.py)."""
 import json
 import os
-
-import pytest
 
 import dropin_flow as df
 from oracle import ref_shim
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="needs /root/reference")
 FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "model_cfg_resolved.json")
 
 
 def test_reference_yaml_instantiates_into_the_mirrors(tmp_path):
-    cfg = df.compose_reference_model_cfg(ref_shim.REFERENCE_ROOT, save_dir="<save_dir>")
-    want = json.loads(json.dumps(cfg))                        # plain JSON types
-    if os.environ.get("GIGAPOSE_WRITE_FIXTURES") == "1" or not os.path.exists(FIXTURE):
-        json.dump(want, open(FIXTURE, "w"), indent=1, sort_keys=True)
-    assert json.load(open(FIXTURE)) == want, "tests/golden/model_cfg_resolved.json is stale: regenerate with GIGAPOSE_WRITE_FIXTURES=1"
+    cfg = json.load(open(FIXTURE))
+    if ref_shim.available():   # the reference's config files are here: the fixture must still be what they compose to
+        want = json.loads(json.dumps(df.compose_reference_model_cfg(ref_shim.REFERENCE_ROOT, save_dir="<save_dir>")))   # plain JSON types
+        assert cfg == want, "tests/golden/model_cfg_resolved.json is stale: regenerate with `python oracle/make_goldens.py signatures`"
     cfg["log_dir"] = str(tmp_path)
     cfg["test_setting"] = "localization"                      # test.py:46 sets it on the config before instantiating
     model = df.instantiate(cfg)

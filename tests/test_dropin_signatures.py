@@ -1,14 +1,17 @@
-"""CPU, build container only (needs /root/reference): the mirror classes a Hydra `_target_` swap instantiates
-(reference test.py:43-47; configs/model/large.yaml:1, ae_net/dinov2_l.yaml:1, ist_net/resnet.yaml:1) take the reference's
-constructor arguments -- same names, same order, same defaults -- and expose the methods / attributes the reference's
-callers use.  Skipped where the reference tree is absent (the GPU box)."""
+"""CPU: the mirror classes a Hydra `_target_` swap instantiates (reference test.py:43-47; configs/model/large.yaml:1,
+ae_net/dinov2_l.yaml:1, ist_net/resnet.yaml:1) take the reference's constructor arguments -- same names, same order, same
+defaults -- and expose the methods / attributes the reference's callers use.  The reference's signatures are
+read from tests/golden/reference_signatures.json, written from the unmodified reference by `oracle/make_goldens.py signatures`;
+where the reference tree is present, they are also taken from it and the file is checked against them."""
 import inspect
+import json
+import os
 
 import pytest
 
 from oracle import ref_shim
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="needs /root/reference")
+FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "reference_signatures.json")
 
 PAIRS = [  # (reference module, class, mirror module, methods the callers use)
     ("src.models.gigaPose", "GigaPose", "gigapose_amd.gigaPose", ["set_template_data", "eval_retrieval", "filter_and_save", "test_step", "on_test_epoch_end"]),
@@ -21,27 +24,40 @@ PAIRS = [  # (reference module, class, mirror module, methods the callers use)
 ]
 
 
-def params(fn):
-    return [(p.name, p.kind, p.default) for p in list(inspect.signature(fn).parameters.values())[1:]]  # without self
+def signature(fn):
+    """[name, kind, has a default, repr of the default] per parameter, without self (the fixture's form)."""
+    return [[p.name, p.kind.name, p.default is not inspect.Parameter.empty, None if p.default is inspect.Parameter.empty else repr(p.default)]
+            for p in list(inspect.signature(fn).parameters.values())[1:]]
+
+
+def reference_signatures(ref_mod, cls, methods):
+    want = json.load(open(FIXTURE))[f"{ref_mod}.{cls}"]
+    if ref_shim.available():   # the reference tree is here: the fixture must still be what it says
+        import importlib
+
+        ref_shim.install()
+        ref = getattr(importlib.import_module(ref_mod), cls)
+        fresh = {name: signature(getattr(ref, name)) for name in ["__init__"] + methods}
+        assert fresh == want, "tests/golden/reference_signatures.json is stale: regenerate with `python oracle/make_goldens.py signatures`"
+    return want
 
 
 @pytest.mark.parametrize("ref_mod,cls,mine_mod,methods", PAIRS)
 def test_constructor_and_method_signatures_match_the_reference(ref_mod, cls, mine_mod, methods):
     import importlib
 
-    ref_shim.install()
-    ref = getattr(importlib.import_module(ref_mod), cls)
+    ref = reference_signatures(ref_mod, cls, methods)
     mine = getattr(importlib.import_module(mine_mod), cls)
-    r, m = params(ref.__init__), params(mine.__init__)
-    assert [(n, k) for n, k, _ in m] == [(n, k) for n, k, _ in r], f"{cls}.__init__ parameters differ: {m} vs {r}"
-    for (n, _, dm), (_, _, dr) in zip(m, r):
-        assert dm == dr or (dm is inspect.Parameter.empty) == (dr is inspect.Parameter.empty) and repr(dm) == repr(dr), f"{cls}.__init__ default of {n}"
+    r, m = ref["__init__"], signature(mine.__init__)
+    assert [(n, k) for n, k, _, _ in m] == [(n, k) for n, k, _, _ in r], f"{cls}.__init__ parameters differ: {m} vs {r}"
+    for (n, _, hm, dm), (_, _, hr, dr) in zip(m, r):
+        assert hm == hr and dm == dr, f"{cls}.__init__ default of {n}: {dm} vs {dr}"
     for name in methods:
         assert hasattr(mine, name), f"{cls}.{name} missing"
-        rp, mp = params(getattr(ref, name)), params(getattr(mine, name))
+        rp, mp = ref[name], signature(getattr(mine, name))
         # the mirror may ADD trailing keyword parameters with defaults; the reference's own must be there, in order
-        assert [n for n, _, _ in mp][:len(rp)] == [n for n, _, _ in rp], f"{cls}.{name}: {mp} vs {rp}"
-        assert all(d is not inspect.Parameter.empty for _, _, d in mp[len(rp):]), f"{cls}.{name}: extra parameter without a default"
+        assert [n for n, _, _, _ in mp][:len(rp)] == [n for n, _, _, _ in rp], f"{cls}.{name}: {mp} vs {rp}"
+        assert all(has for _, _, has, _ in mp[len(rp):]), f"{cls}.{name}: extra parameter without a default"
 
 
 def test_gigapose_accepts_the_hydra_config_kwargs():

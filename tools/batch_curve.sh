@@ -2,7 +2,7 @@
 # batch-size curve of the headline bench: one JSON line per batch size under gpurun_out/$1/
 out=gpurun_out/${1:-curve}; mkdir -p $out
 for b in ${BATCHES:-8 16 32 48 63 64 128}; do
-  timeout 300 python bench.py --batch $b --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-configs --no-other > $out/b$b.json 2> $out/b$b.err
+  timeout 300 python bench.py --full --batch $b --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-configs --no-other > $out/b$b.json 2> $out/b$b.err
   python - $out/b$b.json $b <<'PY'
 import json,sys
 try:

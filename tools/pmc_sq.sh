@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=${1:-gpurun_out/pmc_sq}
 mkdir -p "$OUT"
 timeout 500 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU \
-  --kernel-trace --output-format csv -d /tmp/pmc_sq -o p -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-other > "$OUT/bench.log" 2>&1
+  --kernel-trace --output-format csv -d /tmp/pmc_sq -o p -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-other > "$OUT/bench.log" 2>&1
 echo "rc=$?"
 python - "$(find /tmp/pmc_sq -name '*counter_collection.csv' | head -1)" > "$OUT/summary.txt" <<'PY'
 import collections, csv, sys
