@@ -554,7 +554,7 @@ __global__ __launch_bounds__(512, 2) void match_tiles_split_kernel(
         trace[7] = ((unsigned long long)(xcc & 0xf) << 32) | hw;
     }
     // tile order inside an XCD's chunk: bands of kSplitBand crops x all N templates, crops fastest -- the 32 tiles an XCD runs at a time
-    // are kSplitBand crops x 32 / kSplitBand templates (GP_MATCH_BAND: compile-time A/B, tools/gpu_r06_match.sh)
+    // are kSplitBand crops x 32 / kSplitBand templates (GP_MATCH_BAND: compile-time A/B, tools/build_variant.sh)
     const int band = q / (kSplitBand * N), r8 = q - band * (kSplitBand * N);
     const int gsz = min(kSplitBand, B - band * kSplitBand);
     const int b = band * kSplitBand + r8 % gsz, n = r8 / gsz;

@@ -65,13 +65,11 @@ __global__ __launch_bounds__(256) void split256_weights_kernel(const float* __re
     lo[i] = (_Float16)(v - (float)h);
 }
 
-__device__ unsigned long long g_t256[8];  // probe: per-phase cycle totals of wave 0 of one mid-grid block + step count
+__device__ unsigned long long g_t256[8];  // probe (gp_gemm_planes256_timing): per-phase cycle totals of wave 0 of one mid-grid block + step count
 
-template <int EPI, bool ACT_IS_B, bool TIMING = false>
+template <int EPI, bool ACT_IS_B>
 __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 {
-    unsigned long long tc[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, t1 = 0;
-#define X_T(i) do { if (TIMING) { t1 = __builtin_readcyclecounter(); tc[i] += t1 - t0; t0 = t1; } } while (0)
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * TBUF];  // 128 KiB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
@@ -212,9 +210,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 #define X_MFMA(A_, B_, mi, ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[mi], B_[ni], acc[mi][ni], 0, 0, 0)
         for (int s = 0; s < ns; ++s) {
             const int buf = s & 1;
-            if (TIMING) { t0 = __builtin_readcyclecounter(); tc[5] += 1; }
             if (s + 1 < ns) stage(buf ^ 1);  // slab s+1: loaded one step ago
-            X_T(0);
             const _Float16* L = lds + buf * TBUF;
             g16x8 ah[2], al[2], bh[4], bl[4];
 #pragma unroll
@@ -235,7 +231,6 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
             X_MFMA(ah, bl, 0, 2); X_MFMA(ah, bl, 1, 2); X_MFMA(ah, bl, 0, 3); X_MFMA(ah, bl, 1, 3);
             X_MFMA(al, bh, 0, 0); X_MFMA(al, bh, 1, 0); X_MFMA(al, bh, 0, 1); X_MFMA(al, bh, 1, 1);
             X_MFMA(al, bh, 0, 2); X_MFMA(al, bh, 1, 2); X_MFMA(al, bh, 0, 3); X_MFMA(al, bh, 1, 3);
-            X_T(1);
             // k16 block 1
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
@@ -254,11 +249,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) { X_MFMA(al, bh, 0, ni); X_MFMA(al, bh, 1, ni); }
             if (s + 3 < ns) advance();  // the last steps re-load an in-bounds slab (unused): the step stays branch-free
-            X_T(2);
-            if (TIMING) asm volatile("" :: "v"(acc[1][3][15]));
-            X_T(3);
             __syncthreads();
-            X_T(4);
         }
 #undef X_MFMA
 #undef X_LD
@@ -309,12 +300,9 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
         }
     }
     if (bad) gp_raise(a.status, GP_ST_SPLIT_RANGE);
-    if (TIMING && blockIdx.x == 100 && tid == 0)
-        for (int i = 0; i < 6; ++i) g_t256[i] = tc[i];
 }
 
 unsigned g_epoch256 = 0;
-#undef X_T
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1276,7 +1264,7 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     GpProfScope prof(GP_PROF_GEMM_SPLIT, 2.0 * I * (J_valid > 0 && J_valid < J ? J_valid : J) * K, st);
     // The product's three epilogues (the ViT plane path: 3 = in-place residual, 6 = GELU -> planes, 7 = bias -> planes); the f32-output
     // epilogues 0, 1, 2, 4, 5 are instantiated in probe builds only (-DGP_PROBES: tests of the tile / strip / split-K machinery on
-    // plain GEMMs, the f32-attention A/B path of the ViT)
+    // plain GEMMs)
 #ifdef GP_PROBES
 #define GP_PLANES_EXTRA(...)                                                                                              \
     case XEPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_NONE, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;           \
@@ -1407,23 +1395,6 @@ int gp_gemm_planes256_scaled(const void* a_hi, const void* a_lo, const void* b_h
 }
 
 #ifdef GP_PROBES
-/* probe: proj-shaped launch (act_is_b, no epilogue) with per-phase cycle counters; out6 (host): stage, k16-0 issue,
- * k16-1 issue, MFMA drain, barrier, steps */
-int gp_gemm_split256_timing(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
-                            float* scratch, unsigned long long* out6, void* stream)
-{
-    GP_REQUIRE(gp_gemm_split256_usable(I, J, K) && out6, "gp_gemm_split256_timing: bad arguments");
-    if (hipMemsetAsync(scratch, 0, kHeaderBytes, (hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
-    Args256 a{act, ld_act, (const _Float16*)whi, (const _Float16*)wlo, D, ldd, K, nullptr, nullptr, nullptr, 0, I / TB, J / TB, 4,
-              reinterpret_cast<int*>(scratch), reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0};
-    if (++g_epoch256 == 0) ++g_epoch256;
-    a.epoch = (int)g_epoch256;
-    hipLaunchKernelGGL((gemm_split256_kernel<XEPI_NONE, true, true>), dim3(kSlots), dim3(TNT), 0, (hipStream_t)stream, a);
-    GP_CHECK_LAUNCH("gp_gemm_split256_timing");
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
-    return hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_t256), 6 * sizeof(unsigned long long)) == hipSuccess ? GP_OK : GP_ELAUNCH;
-}
-
 /* probe: no-epilogue launch with per-phase cycle counters of wave 0 of block 100; out6 (host, 8 entries): matrix phase,
  * barrier after it, memory phase, barrier after it, 0, phases, whole-kernel shader cycles, whole-kernel 100 MHz ticks */
 int gp_gemm_planes256_timing(const void* a_hi, const void* a_lo, const void* b_hi, const void* b_lo, float* D, int ldd, int I, int J,

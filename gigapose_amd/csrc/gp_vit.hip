@@ -356,88 +356,66 @@ int launch_layernorm_planes(const float* X, _Float16* hi, _Float16* lo, const fl
 // dot product equals scaling q first).
 constexpr int NKT = 9;  // ceil(257 / 32) key tiles
 
-// NQ query tiles of 32 per wave share every K / V operand load (one 4-byte global load feeds NQ MFMAs).
-// PLANES: the output goes to token-major activation planes (Ohi / Olo pre-offset to this image's first token and this
-// head's first channel; row stride C) instead of channel-major f32 -- the same values o * inv, split as 8 x.
-template <int NQ, bool PLANES = false>
 __device__ __forceinline__ void attention_body(const float* __restrict__ Qp, const float* __restrict__ Kp,
                                                const float* __restrict__ Vp, float* __restrict__ Op, int q0, int C,
-                                               int Mpad, float scale, _Float16* __restrict__ Ohi = nullptr,
-                                               _Float16* __restrict__ Olo = nullptr, unsigned int* Tile = nullptr)
+                                               int Mpad, float scale)
 {
     const int lane = threadIdx.x, half = lane >> 5, l31 = lane & 31;
-    int tq[NQ], tq_c[NQ];
-#pragma unroll
-    for (int u = 0; u < NQ; ++u) {
-        tq[u] = q0 + 32 * u + l31;
-        tq_c[u] = tq[u] < T_TOK ? tq[u] : T_TOK - 1;
-    }
+    const int tq = q0 + l31;
+    const int tq_c = tq < T_TOK ? tq : T_TOK - 1;
     // Online softmax over 3 chunks of 3 key tiles (96 keys).
-    f32x16 o0[NQ], o1[NQ];
-    float m_run[NQ], l_part[NQ];  // l_part: this lane-half's share of the softmax denominator
+    f32x16 o0, o1;
 #pragma unroll
-    for (int u = 0; u < NQ; ++u) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[u][r] = 0.f; o1[u][r] = 0.f; }
-        m_run[u] = -INFINITY;
-        l_part[u] = 0.f;
-    }
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m_run = -INFINITY, l_part = 0.f;  // l_part: this lane-half's share of the softmax denominator
 
 #pragma unroll 1
     for (int ch = 0; ch < 3; ++ch) {
-        f32x16 s[3][NQ];
+        f32x16 s[3];
         int tk_c[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
 #pragma unroll
-            for (int u = 0; u < NQ; ++u)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[t][u][r] = 0.f;
+            for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
             const int tk = (ch * 3 + t) * 32 + l31;
             tk_c[t] = tk < T_TOK ? tk : T_TOK - 1;
         }
 #pragma unroll 8
         for (int kk = 0; kk < 32; ++kk) {
             const size_t drow = (size_t)(2 * kk + half) * Mpad;
-            float qv[NQ];
-#pragma unroll
-            for (int u = 0; u < NQ; ++u) qv[u] = Qp[drow + tq_c[u]];
+            const float qv = Qp[drow + tq_c];
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 const float kv = Kp[drow + tk_c[t]];
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) s[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv, qv[u], s[t][u], 0, 0, 0);
+                s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv, qv, s[t], 0, 0, 0);
             }
         }
+        float cmax = -INFINITY;
 #pragma unroll
-        for (int u = 0; u < NQ; ++u) {
-            float cmax = -INFINITY;
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
-            for (int t = 0; t < 3; ++t)
+            for (int r = 0; r < 16; ++r) {
+                const int tk = (ch * 3 + t) * 32 + frag_row(r, lane);
+                const float v = (tk < T_TOK) ? s[t][r] * scale : -INFINITY;
+                s[t][r] = v;
+                cmax = fmaxf(cmax, v);
+            }
+        cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
+        const float m_new = fmaxf(m_run, cmax);
+        const float alpha = expf(m_run - m_new);  // first chunk: exp(-inf) = 0
+        float psum = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int tk = (ch * 3 + t) * 32 + frag_row(r, lane);
-                    const float v = (tk < T_TOK) ? s[t][u][r] * scale : -INFINITY;
-                    s[t][u][r] = v;
-                    cmax = fmaxf(cmax, v);
-                }
-            cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
-            const float m_new = fmaxf(m_run[u], cmax);
-            const float alpha = expf(m_run[u] - m_new);  // first chunk: exp(-inf) = 0
-            float psum = 0.f;
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
-            for (int t = 0; t < 3; ++t)
+            for (int r = 0; r < 16; ++r) {
+                const float p = expf(s[t][r] - m_new);
+                s[t][r] = p;
+                psum += p;
+            }
+        l_part = l_part * alpha + psum;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float p = expf(s[t][u][r] - m_new);
-                    s[t][u][r] = p;
-                    psum += p;
-                }
-            l_part[u] = l_part[u] * alpha + psum;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o0[u][r] *= alpha; o1[u][r] *= alpha; }
-            m_run[u] = m_new;
-        }
+        for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+        m_run = m_new;
         // O[d][tq] += sum_tk V[tk][d] * P[tk][tq]; the A-operand lane (i = d, k-slot = half) reads
         // V[tk = tile*32 + frag_row(r, lane)][d] -- the key this lane's P register r belongs to.
 #pragma unroll
@@ -448,84 +426,28 @@ __device__ __forceinline__ void attention_body(const float* __restrict__ Qp, con
                 tk = tk < T_TOK ? tk : T_TOK - 1;  // P is 0 there; keep the load in bounds / finite
                 const float* vrow = Vp + (size_t)tk * C + l31;
                 const float v0 = vrow[0], v1 = vrow[32];
-#pragma unroll
-                for (int u = 0; u < NQ; ++u) {
-                    o0[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, s[t][u][r], o0[u], 0, 0, 0);
-                    o1[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, s[t][u][r], o1[u], 0, 0, 0);
-                }
+                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, s[t][r], o0, 0, 0, 0);
+                o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, s[t][r], o1, 0, 0, 0);
             }
     }
+    const float inv = 1.0f / (l_part + __shfl_xor(l_part, 32));
+    if (tq < T_TOK) {
 #pragma unroll
-    for (int u = 0; u < NQ; ++u) {
-        const float inv = 1.0f / (l_part[u] + __shfl_xor(l_part[u], 32));
-        if (PLANES) {
-            // transpose through the wave's LDS tile [32 queries][64 channels (+1)] of packed (hi, lo) words, then 16-byte
-            // stores: 8 lanes cover the 128 contiguous bytes of a token row's head slice
-#pragma unroll
-            for (int half_d = 0; half_d < 2; ++half_d)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = ((half_d ? o1[u][r] : o0[u][r]) * inv) * kPlaneScale;
-                    const _Float16 hh = (_Float16)v;
-                    const _Float16 ll = (_Float16)(v - (float)hh);
-                    Tile[l31 * 65 + 32 * half_d + frag_row(r, lane)] =
-                        (unsigned int)__builtin_bit_cast(unsigned short, hh) | ((unsigned int)__builtin_bit_cast(unsigned short, ll) << 16);
-                }
-            __syncthreads();
-#pragma unroll
-            for (int pass = 0; pass < 4; ++pass) {
-                const int tok = 8 * pass + (lane >> 3), g = lane & 7;
-                v16x8 h, l;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned int w = Tile[tok * 65 + 8 * g + e];
-                    h[e] = __builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
-                    l[e] = __builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
-                }
-                if (q0 + 32 * u + tok < T_TOK) {
-                    const size_t o = (size_t)(q0 + 32 * u + tok) * C + 8 * g;
-                    *reinterpret_cast<v16x8*>(Ohi + o) = h;
-                    *reinterpret_cast<v16x8*>(Olo + o) = l;
-                }
-            }
-        } else if (tq[u] < T_TOK) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = frag_row(r, lane);
-                Op[(size_t)d * Mpad + tq[u]] = o0[u][r] * inv;
-                Op[(size_t)(32 + d) * Mpad + tq[u]] = o1[u][r] * inv;
-            }
+        for (int r = 0; r < 16; ++r) {
+            const int d = frag_row(r, lane);
+            Op[(size_t)d * Mpad + tq] = o0[r] * inv;
+            Op[(size_t)(32 + d) * Mpad + tq] = o1[r] * inv;
         }
     }
 }
 
-// One wave per (image, head, query block).  NQ = 1: nine blocks of 32 queries (the first version; kept as the A/B
-// reference, results are bit-identical).  NQ = 2: four blocks of 64 queries + one of 32 (the 257th token), so eight
-// of the nine query tiles share their K / V operand loads pairwise.
-template <int NQ>
-__global__ __launch_bounds__(64, NQ == 1 ? 4 : 2) void attention_kernel(const float* __restrict__ QK /*[2C][Mpad]*/,
-                                                                         const float* __restrict__ Vt /*[Mpad][C]*/,
-                                                                         float* __restrict__ O /*[C][Mpad]*/, int B, int H,
-                                                                         int C, int Mpad, float scale)
-{
-    constexpr int NB = NQ == 1 ? NKT : 5;
-    const int q = xcd_chunked_tile(blockIdx.x, B * H * NB);
-    if (q < 0) return;
-    const int qb = q % NB, bh = q / NB, h = bh % H, b = bh / H;
-    const float* Qp = QK + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
-    const float* Kp = QK + (size_t)(C + h * 64) * Mpad + (size_t)b * T_TOK;
-    const float* Vp = Vt + (size_t)b * T_TOK * C + h * 64;
-    float* Op = O + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
-    if (NQ == 1) attention_body<1>(Qp, Kp, Vp, Op, qb * 32, C, Mpad, scale);
-    else if (qb < 4) attention_body<2>(Qp, Kp, Vp, Op, qb * 64, C, Mpad, scale);
-    else attention_body<1>(Qp, Kp, Vp, Op, 256, C, Mpad, scale);
-}
-
-// NQ = 1 with the output written as activation planes [Mpad][C] (split numerics, plane x plane GEMMs).  Direct 8-byte
-// stores from the accumulator layout instead of the LDS transpose measured the same end to end (966-969 crops/s).
-__global__ __launch_bounds__(64, 4) void attention_planes_kernel(const float* __restrict__ QK, const float* __restrict__ Vt,
-                                                                  _Float16* __restrict__ Ohi, _Float16* __restrict__ Olo, int B, int H,
-                                                                  int C, int Mpad, float scale)
+// One wave per (image, head, 32-query block): nine blocks per (image, head).  Measured on ViT-L, B=64 (whole forward in split
+// numerics): this kernel 58.2 ms; two query tiles per wave sharing their operand loads (226 VGPR -> 2 waves/SIMD) 60.4 ms; K / V
+// shared through LDS (one 147 KB workgroup per CU) 60.8 ms (profiles/r01_probe_attention_nq.txt).  Occupancy wins.
+__global__ __launch_bounds__(64, 4) void attention_kernel(const float* __restrict__ QK /*[2C][Mpad]*/,
+                                                          const float* __restrict__ Vt /*[Mpad][C]*/,
+                                                          float* __restrict__ O /*[C][Mpad]*/, int B, int H, int C,
+                                                          int Mpad, float scale)
 {
     const int q = xcd_chunked_tile(blockIdx.x, B * H * NKT);
     if (q < 0) return;
@@ -533,9 +455,8 @@ __global__ __launch_bounds__(64, 4) void attention_planes_kernel(const float* __
     const float* Qp = QK + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
     const float* Kp = QK + (size_t)(C + h * 64) * Mpad + (size_t)b * T_TOK;
     const float* Vp = Vt + (size_t)b * T_TOK * C + h * 64;
-    const size_t o = (size_t)b * T_TOK * C + h * 64;
-    __shared__ unsigned int tile[32 * 65];
-    attention_body<1, true>(Qp, Kp, Vp, nullptr, qb * 32, C, Mpad, scale, Ohi + o, Olo + o, tile);
+    float* Op = O + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
+    attention_body(Qp, Kp, Vp, Op, qb * 32, C, Mpad, scale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -900,119 +821,11 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(const _Float16* __
     }
 }
 
-// K and V of one (image, head) staged in LDS ONCE and shared by the nine query-tile waves of the workgroup (the
-// register-resident kernel above re-reads them from L2 with one 4-byte load per MFMA, nine times per (image, head)).
-//   sK [64 d][288 keys] (keys >= 257 zero), sV [288 keys][64 d]: 147 KB -> one workgroup per CU, 9 waves.
-// Operand reads are conflict-free ds_read_b32 (lanes = consecutive keys / consecutive d).  Q fragments are loaded once
-// per wave (32 registers).  Arithmetic per (key, query) is the same MFMA chain and the same 3-chunk online softmax
-// as attention_body, so the result is bit-identical.
-constexpr int AK = 288;  // padded key count
-__global__ __launch_bounds__(576, 1) void attention_lds_kernel(const float* __restrict__ QK, const float* __restrict__ Vt,
-                                                                float* __restrict__ O, int B, int H, int C, int Mpad,
-                                                                float scale)
-{
-    __shared__ float sK[64 * AK];
-    __shared__ float sV[AK * 64];
-    const int bh = xcd_chunked_tile(blockIdx.x, B * H);
-    if (bh < 0) return;
-    const int h = bh % H, b = bh / H;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const float* Qp = QK + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
-    const float* Kp = QK + (size_t)(C + h * 64) * Mpad + (size_t)b * T_TOK;
-    const float* Vp = Vt + (size_t)b * T_TOK * C + h * 64;
-    float* Op = O + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
-    for (int e = tid; e < 64 * AK; e += 576) {
-        const int d = e / AK, key = e - d * AK;
-        sK[e] = key < T_TOK ? Kp[(size_t)d * Mpad + key] : 0.f;
-    }
-    for (int e = tid; e < AK * 64; e += 576) {
-        const int key = e >> 6, d = e & 63;
-        sV[e] = key < T_TOK ? Vp[(size_t)key * C + d] : 0.f;
-    }
-    const int tq = wave * 32 + l31;
-    const int tq_c = tq < T_TOK ? tq : T_TOK - 1;
-    float qreg[32];
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) qreg[kk] = Qp[(size_t)(2 * kk + half) * Mpad + tq_c];
-    __syncthreads();
-
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-    float m_run = -INFINITY, l_part = 0.f;
-#pragma unroll 1
-    for (int ch = 0; ch < 3; ++ch) {
-        f32x16 s[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) {
-            const float* krow = sK + (2 * kk + half) * AK + ch * 96 + l31;
-#pragma unroll
-            for (int t = 0; t < 3; ++t) s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[32 * t], qreg[kk], s[t], 0, 0, 0);
-        }
-        float cmax = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int tk = (ch * 3 + t) * 32 + frag_row(r, lane);
-                const float v = (tk < T_TOK) ? s[t][r] * scale : -INFINITY;
-                s[t][r] = v;
-                cmax = fmaxf(cmax, v);
-            }
-        cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
-        const float m_new = fmaxf(m_run, cmax);
-        const float alpha = expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = expf(s[t][r] - m_new);
-                s[t][r] = p;
-                psum += p;
-            }
-        l_part = l_part * alpha + psum;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-        m_run = m_new;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int tk = (ch * 3 + t) * 32 + frag_row(r, lane);  // < 288; rows >= 257 are zero and P is 0 there
-                const float* vrow = sV + tk * 64 + l31;
-                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[0], s[t][r], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[32], s[t][r], o1, 0, 0, 0);
-            }
-    }
-    const float inv = 1.0f / (l_part + __shfl_xor(l_part, 32));
-    if (tq < T_TOK) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int d = frag_row(r, lane);
-            Op[(size_t)d * Mpad + tq] = o0[r] * inv;
-            Op[(size_t)(32 + d) * Mpad + tq] = o1[r] * inv;
-        }
-    }
-}
-
-// Measured on ViT-L, B=64 (tools/probe_attn.py, whole forward in split numerics): register-resident with one query tile
-// per wave 58.2 ms; two tiles per wave (operand loads shared, 226 VGPR -> 2 waves/SIMD) 60.4 ms; K/V through LDS (one
-// 147 KB workgroup per CU, staging not overlapped) 60.8 ms.  Occupancy wins: the default stays 1.
-// split numerics: activation planes + plane x plane GEMMs when every GEMM of a layer fits them.  2 (default): attention in
-// split numerics too (Q | K | V as planes, attention_split_kernel); 1: f32 attention on f32 Q, K, V (bit-identical to 0);
-// 0: f32 activations and the lock-step kernels (kept for A/B runs and the bit-identity test)
-static int g_vit_planes = 2;
+// split numerics: activation planes + plane x plane GEMMs, attention in split numerics, when every GEMM of a layer fits them
+// (the default); off: f32 activations and the lock-step kernels (what the ViT-L split test compares the plane path against)
+static bool g_vit_planes = true;
 #ifdef GP_PROBES
-extern "C" void gp_vit_set_planes(int mode) { g_vit_planes = (mode >= 0 && mode <= 2) ? mode : 2; }
-#endif
-static int g_attn_nq = 1;  // 0: LDS-shared K/V kernel; 1 / 2: register-resident kernel with 1 / 2 query tiles per wave
-#ifdef GP_PROBES
-extern "C" void gp_attention_set_nq(int nq) { g_attn_nq = (nq >= 0 && nq <= 2) ? nq : 1; }
+extern "C" void gp_vit_set_planes(int on) { g_vit_planes = on != 0; }
 #endif
 
 // ---- x_prenorm[:, 1:] -> (B, C, 256), F.normalize over C (ae_net.py:64-69); fixed fmaf order
@@ -1132,13 +945,11 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
 {
     hipStream_t st = (hipStream_t)stream;
     enum { PS_LN1 = 0, PS_QKV, PS_LN2, PS_GELU, PS_PER_LAYER = 4 };
-    bool default_scales = true;
     if (plane_scales)
         for (int i = 0; i < depth * PS_PER_LAYER; ++i) {
             int ex = 0;
             GP_REQUIRE(plane_scales[i] > 0.f && frexpf(plane_scales[i], &ex) == 0.5f && plane_scales[i] <= 64.f && plane_scales[i] >= 1.0f / 1024.0f,
                        "gp_vit_forward_split2: plane scale %d = %g is not a power of two in [2^-10, 64]", i, (double)plane_scales[i]);
-            default_scales = default_scales && plane_scales[i] == kPlaneScale;
         }
     GP_REQUIRE(B >= 0 && dim > 0 && depth > 0 && heads > 0, "gp_vit_forward: bad config");
     if (B == 0) return GP_OK;
@@ -1184,15 +995,15 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
 
     const int nl = (stop_after_layers >= 0 && stop_after_layers < depth) ? stop_after_layers : depth;
     // Split numerics, third generation: when all five GEMMs of a layer fill the chip with 256 x 256 tiles, the
-    // activations between the kernels travel as token-major f16 planes (written by LayerNorm, attention and fc1's GELU
-    // epilogue; the f32 residual stream X, Q/K and V stay as they are) and every GEMM is gemm_planes256_kernel.  The
-    // planes alias the f32 buffers they replace (2 planes x 2 bytes = 4 bytes per element).  Bit-identical to the
-    // f32-activation kernels (same values, same split, same k order).
+    // activations between the kernels travel as token-major f16 planes (written by LayerNorm, the plane epilogues of the
+    // q | k | v and fc1 GEMMs, and attention; the f32 residual stream X stays as it is), every GEMM is
+    // gemm_planes256_kernel and attention runs in split numerics (attention_split_kernel).  The planes alias the f32
+    // buffers they replace (2 planes x 2 bytes = 4 bytes per element).  The GEMMs compute the f32-activation kernels'
+    // values (same split, same k order); gp_vit_set_planes(0) (probe build) turns the plane path off for comparison.
     const int Mtok = B * T_TOK;  // rows that carry tokens: the plane GEMMs tile floor(Mtok / 256) * 256 of them + a strip
     const bool planes = have_x64 && g_vit_planes && gp_gemm_planes256_usable(2 * C, Mpad, Mtok, C) &&
                         gp_gemm_planes256_usable(C, Mpad, Mtok, C) && gp_gemm_planes256_usable(mlp_dim, Mpad, Mtok, C) &&
-                        gp_gemm_planes256_usable(C, Mpad, Mtok, mlp_dim) && (g_vit_planes == 2 || gp_gemm_split256_usable(Mpad, C, C));
-    GP_REQUIRE(g_vit_planes == 2 || !planes || (default_scales && !plane_amax), "gp_vit_forward_split2: plane scales need the full plane path (gp_vit_set_planes(2))");
+                        gp_gemm_planes256_usable(C, Mpad, Mtok, mlp_dim);
     if (planes) {
         _Float16* Hhi = reinterpret_cast<_Float16*>(Hn);
         _Float16* Hlo = Hhi + (size_t)C * Mpad;
@@ -1205,58 +1016,40 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
             // this layer's plane scales (powers of two) and, in a calibration pass, where each tensor's max |x| goes
             const float* ps = plane_scales ? plane_scales + l * PS_PER_LAYER : ps_default;
             float* am = plane_amax ? plane_amax + l * PS_PER_LAYER : nullptr;
-            const float os = 1.0f / (kPlaneScale * 64.0f);  // g_vit_planes == 1 (probe path): activations x 8, weights x 64
             const float os_ln1 = 1.0f / (ps[PS_LN1] * 64.0f), os_qkv = 1.0f / (ps[PS_QKV] * 64.0f), os_ln2 = 1.0f / (ps[PS_LN2] * 64.0f),
                         os_gelu = 1.0f / (ps[PS_GELU] * 64.0f);   // a consumer undoes its B operand's scale and the weights' x 64, exactly
             const GpPlaneOut po_qkv{ps[PS_QKV], am ? am + PS_QKV : nullptr}, po_gelu{ps[PS_GELU], am ? am + PS_GELU : nullptr};
             launch_layernorm_planes(X, Hhi, Hlo, w[L_LN1_G], w[L_LN1_B], C, Mpad, ln_eps, st, ps[PS_LN1], am ? am + PS_LN1 : nullptr);
             GP_CHECK_LAUNCH("gp_vit_forward/layernorm_planes");
-            if (g_vit_planes == 2) {
-                // Q | K | V as planes [Mpad][3C] (aliasing the f32 QK + Vt buffers): W_qk / W_v (A) x tokens (B), plane epilogue
-                _Float16* Ahi = reinterpret_cast<_Float16*>(QK);
-                _Float16* Alo = Ahi + (size_t)3 * C * Mpad;
-                // one launch when the host packed q|k and v contiguously (planes and biases are views of one tensor, vit.py): 12 x 64 =
-                // 768 tiles = 3 per slot instead of 512 + 256 in two launches (one strip, one launch boundary less per layer)
-                const bool fused_qkv = (const char*)sq[S_V_HI] == (const char*)sq[S_QK_HI] + (size_t)2 * C * C * 2 &&
-                                       (const char*)sq[S_V_LO] == (const char*)sq[S_QK_LO] + (size_t)2 * C * C * 2 && w[L_V_B] == w[L_QK_B] + 2 * C &&
-                                       gp_gemm_planes256_usable(3 * C, Mpad, Mtok, C);
-                if (fused_qkv) {
-                    if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 3 * C, Mpad, Mtok, C,
-                                                       7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
-                        return rc;
-                } else {
-                    if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 2 * C, Mpad, Mtok, C,
-                                                       7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
-                        return rc;
-                    if ((rc = gp_gemm_planes256_launch(sq[S_V_HI], sq[S_V_LO], Hhi, Hlo, nullptr, 0, Ahi + 2 * C, Alo + 2 * C, 3 * C, C, Mpad, Mtok, C,
-                                                       7 /*BIAS_I -> planes*/, w[L_V_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
-                        return rc;
-                }
-                {
-                    GpProfScope prof(GP_PROF_ATTN, 4.0 * B * heads * 257.0 * 257.0 * 64.0, st);
-                    hipLaunchKernelGGL(attention_split_kernel, dim3(xcd_chunked_grid(B * heads)), dim3(ATH), 0, st, Ahi, Alo, Hhi, Hlo, B,
-                                       heads, C, Mpad, 1.0f / (ps[PS_QKV] * ps[PS_QKV]));
-                }
-                GP_CHECK_LAUNCH("gp_vit_forward/attention_split");
+            // Q | K | V as planes [Mpad][3C] (aliasing the f32 QK + Vt buffers): W_qk / W_v (A) x tokens (B), plane epilogue
+            _Float16* Ahi = reinterpret_cast<_Float16*>(QK);
+            _Float16* Alo = Ahi + (size_t)3 * C * Mpad;
+            // one launch when the host packed q|k and v contiguously (planes and biases are views of one tensor, vit.py): 12 x 64 =
+            // 768 tiles = 3 per slot instead of 512 + 256 in two launches (one strip, one launch boundary less per layer)
+            const bool fused_qkv = (const char*)sq[S_V_HI] == (const char*)sq[S_QK_HI] + (size_t)2 * C * C * 2 &&
+                                   (const char*)sq[S_V_LO] == (const char*)sq[S_QK_LO] + (size_t)2 * C * C * 2 && w[L_V_B] == w[L_QK_B] + 2 * C &&
+                                   gp_gemm_planes256_usable(3 * C, Mpad, Mtok, C);
+            if (fused_qkv) {
+                if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 3 * C, Mpad, Mtok, C,
+                                                   7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                    return rc;
             } else {
-            // Q,K channel-major [2C][Mpad] = W_qk (A) x tokens (B)
-            if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, QK, Mpad, nullptr, nullptr, 0, 2 * C, Mpad, Mtok, C,
-                                               1 /*BIAS_I*/, w[L_QK_B], nullptr, nullptr, 0, os, SK, st)))
-                return rc;
-            // V token-major [Mpad][C] = tokens (A) x W_v (B), bias along j
-            if ((rc = gp_gemm_planes256_launch(Hhi, Hlo, sq[S_V_HI], sq[S_V_LO], Vt, C, nullptr, nullptr, 0, Mpad, C, C, C,
-                                               4 /*BIAS_J*/, w[L_V_B], nullptr, nullptr, 0, os, SK, st)))
-                return rc;
+                if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 2 * C, Mpad, Mtok, C,
+                                                   7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                    return rc;
+                if ((rc = gp_gemm_planes256_launch(sq[S_V_HI], sq[S_V_LO], Hhi, Hlo, nullptr, 0, Ahi + 2 * C, Alo + 2 * C, 3 * C, C, Mpad, Mtok, C,
+                                                   7 /*BIAS_I -> planes*/, w[L_V_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                    return rc;
+            }
             {
                 GpProfScope prof(GP_PROF_ATTN, 4.0 * B * heads * 257.0 * 257.0 * 64.0, st);
-                hipLaunchKernelGGL(attention_planes_kernel, dim3(xcd_chunked_grid(B * heads * NKT)), dim3(64), 0, st, QK, Vt, Hhi, Hlo,
-                                   B, heads, C, Mpad, 0.125f);
+                hipLaunchKernelGGL(attention_split_kernel, dim3(xcd_chunked_grid(B * heads)), dim3(ATH), 0, st, Ahi, Alo, Hhi, Hlo, B,
+                                   heads, C, Mpad, 1.0f / (ps[PS_QKV] * ps[PS_QKV]));
             }
-            GP_CHECK_LAUNCH("gp_vit_forward/attention_planes");
-            }
-            // x = x + ls1 * proj(attn)   (the attention output carries the q | k | v scale; g_vit_planes == 1: the default x 8)
+            GP_CHECK_LAUNCH("gp_vit_forward/attention_split");
+            // x = x + ls1 * proj(attn)   (the attention output carries the q | k | v scale)
             if ((rc = gp_gemm_planes256_launch(sq[S_PROJ_HI], sq[S_PROJ_LO], Hhi, Hlo, X, Mpad, nullptr, nullptr, 0, C, Mpad, Mtok, C,
-                                               3 /*BIAS_I_SCALE_RES*/, w[L_PROJ_B], w[L_LS1], X, Mpad, g_vit_planes == 2 ? os_qkv : os, SK, st)))
+                                               3 /*BIAS_I_SCALE_RES*/, w[L_PROJ_B], w[L_LS1], X, Mpad, os_qkv, SK, st)))
                 return rc;
             launch_layernorm_planes(X, Hhi, Hlo, w[L_LN2_G], w[L_LN2_B], C, Mpad, ln_eps, st, ps[PS_LN2], am ? am + PS_LN2 : nullptr);
             GP_CHECK_LAUNCH("gp_vit_forward/layernorm_planes");
@@ -1294,15 +1087,8 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
         if (rc) return rc;
         {
             GpProfScope prof(GP_PROF_ATTN, 4.0 * B * heads * 257.0 * 257.0 * 64.0, st);
-            if (g_attn_nq == 0)
-                hipLaunchKernelGGL(attention_lds_kernel, dim3(xcd_chunked_grid(B * heads)), dim3(576), 0, st, QK, Vt, Hn, B, heads, C,
-                                   Mpad, 0.125f);
-            else if (g_attn_nq == 1)
-                hipLaunchKernelGGL(attention_kernel<1>, dim3(xcd_chunked_grid(B * heads * NKT)), dim3(64), 0, st, QK, Vt, Hn, B,
-                                   heads, C, Mpad, 0.125f);
-            else
-                hipLaunchKernelGGL(attention_kernel<2>, dim3(xcd_chunked_grid(B * heads * 5)), dim3(64), 0, st, QK, Vt, Hn, B,
-                                   heads, C, Mpad, 0.125f);
+            hipLaunchKernelGGL(attention_kernel, dim3(xcd_chunked_grid(B * heads * NKT)), dim3(64), 0, st, QK, Vt, Hn, B, heads, C,
+                               Mpad, 0.125f);
         }
         GP_CHECK_LAUNCH("gp_vit_forward/attention");
         // x = x + ls1 * proj(attn)

@@ -27,17 +27,11 @@ void gp_gemm_set_streamk(int mode); /* 0 = one workgroup per tile even with a sc
                                        whenever the tile count allows (results identical) */
 void gp_gemm_set_group(int g);      /* tiles are ordered in bands of g i-tiles (default 8; results identical) */
 int gp_gemm_streamk_error(const float* scratch, void* stream);  /* synchronises; the scratch's error word (0 = every hand-off arrived) */
-int gp_gemm_probe(int variant, const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J, int K, void* stream);
-int gp_gemm_probe_occupancy(void);
-int gp_gemm_product_occupancy(int streamk);
-int gp_gemm_probe_clock(unsigned long long* host4);
 
 /* ---- split GEMMs ---- */
 int gp_gemm_split_set_trace(unsigned long long* dev_buf);
 int gp_gemm_split_timing(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
                          unsigned long long* out20 /* 23 entries */, void* stream);
-int gp_gemm_split256_timing(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
-                            float* scratch, unsigned long long* out6, void* stream);
 int gp_gemm_split256_error(const float* scratch, void* stream); /* scratch error word of gp_gemm_split256 / gp_gemm_planes256_scaled */
 /* gemm_planes256_kernel: bit 0 (default 1): data-parallel rounds before the stream-K remainder; bit 1: TEST hook, head fragments are
  * never published (every waiter times out -> GP_STATUS_HANDOFF_SPLIT) */
@@ -55,11 +49,10 @@ int gp_gemm_planes256_timing(const void* a_hi, const void* a_lo, const void* b_h
                              int K, float* scratch, unsigned long long* out8, void* stream);
 
 /* ---- ViT ---- */
-void gp_attention_set_nq(int nq); /* chain attention: 1 (default) / 2 = register-resident kernel with 1 / 2 query tiles per wave; 0 = K/V
-                                     shared through LDS (results identical) */
 void gp_vit_set_ln_reg(int mode); /* plane path's LayerNorm: 1 (default) 32-token blocks, 16-token blocks when the launch has at most 128 of
                                      them; 2 always 32-token blocks; 0 the first-generation three-pass kernel (results identical) */
-void gp_vit_set_planes(int mode); /* 2 (default) = planes + attention in split numerics, 1 = planes + f32 attention, 0 = f32 activations */
+void gp_vit_set_planes(int on);   /* split numerics: 1 (default; any value but 0) = activation planes + attention in split numerics where the
+                                     shapes allow, 0 = f32 activations and the lock-step kernels */
 
 /* ---- IST convolutions ---- */
 void gp_conv_set_direct(int on);                                  /* 0 = always the generic gather kernel (results identical) */

@@ -178,23 +178,6 @@ def test_aenet_interface_chunks():
     assert tuple(net(x[:0].to(DEV)).shape) == (0, 128, 16, 16)
 
 
-@pytest.mark.probes
-def test_attention_variants_are_bit_identical():
-    """The three attention kernels (1 or 2 query tiles per wave, K/V through LDS) run the same MFMA chains."""
-    from gigapose_amd import _lib
-
-    hf, vit, x = run_vit(128, 2, 2, 3, seed=61)
-    lib = _lib.lib()
-    outs = []
-    try:
-        for nq in (1, 2, 0):
-            lib.gp_attention_set_nq(nq)
-            outs.append(vit.patch_features(x.to(DEV), normalize=False).cpu())
-    finally:
-        lib.gp_attention_set_nq(1)
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-
-
 def test_vit_large_width_every_batch_size_split_vs_chain():
     """ViT-L width (4 blocks) at batch sizes on both sides of every path switch of the split numerics: 1-7 crops (fewer than 8 plane
     tiles: 128 x 128 kernels), 8-63 (plane GEMMs with the parallel split-K, S = 16 ... 1 slots per tile, strips of B rows), 64 and

@@ -49,11 +49,3 @@ for (I, J, K, act_is_b, name, epi) in [(1024, M, 1024, 1, "proj", 3), (4096, M, 
     ms = timeit(run)
     print(f"{name:5s} I={I} J={J} K={K}: {ms:.3f} ms = {2.0*I*J*K/ms/1e9:.0f} TF-equivalent | err/sum|ab| rms {e.pow(2).mean().sqrt().item():.2e} max {e.max().item():.2e} | hand-off error word {err}")
 
-I, J, K = 1024, M, 4096
-W = torch.randn(I, K, device=dev) * 0.03; X = torch.randn(K, J, device=dev); hi, lo = planes256(W); D = torch.empty(I, J, device=dev)
-out = (ctypes.c_ulonglong * 6)()
-for _ in range(2):
-    lib.gp_gemm_split256_timing(_lib.ptr(X), J, _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), J, I, J, K, _lib.ptr(ws), out, _lib.stream_ptr())
-n = max(1, out[5])
-print("fc2 shape, wave 0 of block 100, cycles per k-step: stage %d, k16-0 (reads+24 MFMA+12 loads) %d, k16-1 (reads+24 MFMA) %d, drain %d, barrier %d  (steps %d; one wave's MFMAs occupy the pipe 1536)"
-      % (out[0] / n, out[1] / n, out[2] / n, out[3] / n, out[4] / n, n))
