@@ -903,6 +903,9 @@ __global__ __launch_bounds__(256) void planes_from_cm_kernel(const float* __rest
     for (int r = ty; r < 32; r += 8) {
         if (p0 + r < npix && c0 + tx < C) {
             float v = t[tx][r] * kActScale;
+            // as in split_planes_kernel: without it the compiler folds multiply + conversion into v_fma_mixlo_f16 (x, 8, +0) -- same
+            // value (8 is a power of two) but -0 comes out as +0 in the hi plane; hi and lo must see the one f32 product
+            asm volatile("" : "+v"(v));
             const _Float16 h = (_Float16)v;
             hi[(size_t)(p0 + r) * C + c0 + tx] = h;
             lo[(size_t)(p0 + r) * C + c0 + tx] = (_Float16)(v - (float)h);

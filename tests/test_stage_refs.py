@@ -1,0 +1,231 @@
+"""CPU: the float64 references and input builders of the split path's stage tests (gigapose_testing/stage_refs.py) against torch's
+own float64 operators, and every "reference alone" condition those tests rely on -- so that a failure of a GPU stage test is a
+finding about a kernel, not about its yardstick.  No GPU, no HIP library."""
+import numpy as np
+import pytest
+import torch
+
+from gigapose_testing import stage_refs as sr
+
+F = torch.nn.functional
+
+
+# ---------------------------------------------------------------------------------------------------------------- planes
+@pytest.mark.parametrize("scale", [8.0, 64.0, 0.25, 1.0, 3.3])
+def test_host_split_reconstructs_to_22_bits_and_is_well_formed(scale):
+    x = torch.from_numpy(sr.split_values_case(100003, 5))
+    hi, lo = sr.split_planes_host(x, scale)
+    assert hi.dtype == torch.float16 and lo.dtype == torch.float16
+    v = (x * torch.tensor(scale, dtype=torch.float32)).double()            # the f32 product the planes split
+    fits = v.abs() < 65504.0                                               # 8000 x 64 leaves f16: hi = inf there, on the device too
+    assert int(fits.sum()) > 90000 and bool(torch.isinf(hi[~fits].float()).all())
+    v, hi, lo = v[fits], hi[fits], lo[fits]
+    back = hi.double() + lo.double()
+    # 22 bits of v, down to the f16 subnormal floor of the lo plane (2^-25 absolute)
+    assert bool(((back - v).abs() <= sr.PLANE_BITS * v.abs() + 2.0 ** -25).all())
+    assert sr.planes_well_formed(hi, lo)
+    big = v.abs() >= 0.25                  # lo = f16(v - hi) is a normal f16 or an exact subnormal from here up: the pure relative statement
+    assert int(big.sum()) > 1000 and float(((back - v).abs() / v.abs())[big].max()) <= sr.PLANE_BITS
+
+
+def test_host_split_on_hand_computed_values():
+    hi, lo = sr.split_planes_host(torch.tensor([1.0 + 2.0 ** -11, 1.0 + 3.0 * 2.0 ** -11, 0.0, -0.0, 1.0 + 2.0 ** -20]), 1.0)
+    # ties go to even: 1 + 2^-11 -> 1 (lo = +2^-11), 1 + 3 * 2^-11 -> 1 + 2^-9 (lo = -2^-11)
+    assert hi.tolist() == [1.0, 1.0 + 2.0 ** -9, 0.0, -0.0, 1.0]
+    assert lo.tolist() == [2.0 ** -11, -2.0 ** -11, 0.0, 0.0, 2.0 ** -20]
+    assert torch.signbit(hi[3]) and not torch.signbit(hi[2])
+    # x 3.3 is not exact: the planes split the ROUNDED f32 product, not the exact one
+    x = torch.tensor([0.7], dtype=torch.float32)
+    hi, lo = sr.split_planes_host(x, 3.3)
+    v = np.float32(0.7) * np.float32(3.3)
+    assert float(hi) == float(np.float16(v)) and float(lo) == float(np.float16(v - np.float32(np.float16(v))))
+
+
+def test_split_values_case_holds_what_it_is_named_after():
+    x = sr.split_values_case(257, 1)
+    assert x.dtype == np.float32 and x.shape == (257,)
+    a = np.abs(x[x != 0])
+    assert a.min() <= 1e-29 and a.max() >= 7999.0 and a.max() <= 8000.0
+    assert (x == 0).sum() >= 2 and np.signbit(x[x == 0]).any() and not np.signbit(x[x == 0]).all()
+    hi, lo = sr.split_planes_host(torch.from_numpy(x), 1.0)
+    nz = x != 0
+    assert int(((lo == 0) & torch.from_numpy(nz) & (hi != 0)).sum()) >= 4                      # exact f16 values
+    assert int(((lo != 0) & (lo.double().abs() < 2.0 ** -14)).sum()) >= 3                     # f16-subnormal lows
+    assert int((lo.double().abs() == 0.5 * sr.f16_ulp(hi)).sum()) >= 3                        # halfway cases
+    assert sr.split_values_case(1, 3).shape == (1,)
+
+
+def test_f16_ulp():
+    h = torch.tensor([1.0, 1.5, 2.0, 1000.0, 2.0 ** -14, 2.0 ** -15, 0.0, -3.0, 65504.0], dtype=torch.float16)
+    assert sr.f16_ulp(h).tolist() == [2.0 ** -10, 2.0 ** -10, 2.0 ** -9, 0.5, 2.0 ** -24, 2.0 ** -24, 2.0 ** -24, 2.0 ** -9, 32.0]
+    assert not sr.planes_well_formed(torch.tensor([1.0], dtype=torch.float16), torch.tensor([2.0 ** -10], dtype=torch.float16))
+    assert not sr.planes_well_formed(torch.tensor([float("inf")], dtype=torch.float16), torch.tensor([0.0], dtype=torch.float16))
+
+
+# ---------------------------------------------------------------------------------------------------------------- LayerNorm
+@pytest.mark.parametrize("C,Mpad", [(384, 1024), (1024, 2304), (1280, 1024)])
+def test_layernorm_f64_equals_torch_and_the_classes_are_what_they_say(C, Mpad):
+    x, cls, gamma, beta = sr.layernorm_case(C, Mpad, 11)
+    y, xhat = sr.layernorm_f64(x, gamma, beta, 1e-6)
+    ref = F.layer_norm(x.double(), (C,), gamma.double(), beta.double(), 1e-6)
+    assert float((y - ref).abs().max()) < 1e-12
+    # the classes
+    names = sr.LN_CLASSES
+    assert set(cls.tolist()) == set(range(5))
+    plain, massive, offset, const, pad = (x[cls == i].double() for i in range(5))
+    assert abs(float(plain.mean())) < 0.1 and 0.3 < float(plain.std(dim=1).min()) and float(plain.std(dim=1).max()) < 3.6
+    assert float(massive[:, 7].min()) > 235 and float(massive[:, C - 3].max()) < -165
+    assert float(offset.mean(dim=1).min()) > 49 and float((offset.mean(dim=1) / offset.std(dim=1)).min()) > 10   # mean >> spread
+    assert bool((const == 3.0).all()) and bool((pad == 0.0).all())
+    # positions: first / last columns of 16-, 32- and 64-token blocks and the end of the buffer carry special tokens
+    cols = sr.layernorm_class_columns(Mpad)
+    for name in ("massive", "offset", "constant"):
+        assert all(int(cls[c]) == names.index(name) for c in cols[name]) and Mpad - 4 <= max(cols[name])
+    assert {c % 16 for cc in cols.values() for c in cc} >= {0, 15} and {c % 64 for cc in cols.values() for c in cc} >= {0, 63, 31, 32}
+    assert int(cls[Mpad - 1]) == 4
+    # constant and pad tokens: x - mean is exactly 0, y = beta exactly; the guard is far away (max |8 y| a few hundred)
+    assert bool((y[(cls == 3) | (cls == 4)] == beta.double()).all())
+    assert float((8 * y).abs().max()) < 1000.0
+    # the reference alone (ATen's f32 LayerNorm on the CPU) per class: f32-class figures, the offset class an order above the others
+    e = sr.per_class_max(sr.layernorm_error(F.layer_norm(x, (C,), gamma, beta, 1e-6), y, xhat, gamma, beta), cls)
+    print(f"C={C} Mpad={Mpad}: f32 CPU LayerNorm vs float64 per class: " + ", ".join(f"{k} {v:.2e}" for k, v in e.items()))
+    assert e["plain"] < 5e-7 and e["massive"] < 5e-7 and 1e-6 < e["offset"] < 3e-5 and e["constant"] == 0 and e["pad"] == 0
+    # ... and the numpy f32 model of the kernels' own summation orders (16 / 32 interleaved partial sums of the register kernels, 16
+    # contiguous slices of the three-pass kernel) is an f32 LayerNorm of the same class: exact where the sums are exact, a few ulp elsewhere
+    for slices, contiguous in ((16, False), (32, False), (16, True)):
+        if C % (8 * slices):
+            continue
+        m = sr.per_class_max(sr.layernorm_error(torch.from_numpy(sr.layernorm_partial_sums_f32(x.numpy(), gamma.numpy(), beta.numpy(), 1e-6, slices,
+                                                                                                  contiguous)), y, xhat, gamma, beta), cls)
+        print(f"   model with {slices} {'contiguous' if contiguous else 'interleaved'} partial sums: " + ", ".join(f"{k} {v:.2e}" for k, v in m.items()))
+        assert m["plain"] < 5e-7 and m["massive"] < 5e-7 and 1e-6 < m["offset"] < 3e-5 and m["constant"] == 0 and m["pad"] == 0
+
+
+def test_layernorm_reference_notices_a_wrong_variance():
+    """The measure separates the biased from the unbiased variance (1 / C vs 1 / (C - 1): a relative 1.3e-3 at C = 384)."""
+    C = 384
+    x, cls, gamma, beta = sr.layernorm_case(C, 1024, 12)
+    y, xhat = sr.layernorm_f64(x, gamma, beta, 1e-6)
+    xd = x.double()
+    wrong = (xd - xd.mean(1, keepdim=True)) / torch.sqrt(xd.var(1, unbiased=True, keepdim=True) + 1e-6) * gamma.double() + beta.double()
+    e = sr.per_class_max(sr.layernorm_error(wrong, y, xhat, gamma, beta), cls)
+    assert e["plain"] > 1e-4 and e["massive"] > 1e-4 and e["offset"] > 1e-4
+
+
+# ---------------------------------------------------------------------------------------------------------------- the split stem
+@pytest.mark.parametrize("S,Cout,B", [(32, 16, 2), (64, 128, 1), (18, 8, 3)])
+def test_framed_stem_reference_equals_conv2d(S, Cout, B):
+    g = torch.Generator().manual_seed(S)
+    x = torch.randn(B, 3, S, S, generator=g, dtype=torch.float64)
+    w = torch.randn(Cout, 3, 7, 7, generator=g, dtype=torch.float64)
+    got = sr.stem_conv_framed_f64(sr.frame_image(x), sr.pack_stem_weights(w))
+    ref = F.conv2d(x, w, stride=2, padding=3)
+    assert got.shape == ref.shape == (B, Cout, S // 2, S // 2)
+    assert float((got - ref).abs().max()) < 1e-12 * float(ref.abs().max())
+    wk = sr.pack_stem_weights(w).reshape(Cout, 7, 8, 4)
+    assert bool((wk[:, :, 7] == 0).all()) and bool((wk[..., 3] == 0).all())
+    assert wk[3, 2, 5, 1] == w[3, 1, 2, 5]                       # k = dy * 32 + dx * 4 + ci
+    fr = sr.frame_image(x)
+    assert fr.shape == (B, S + 6, S + 8, 4) and bool((fr[:, :3] == 0).all()) and bool((fr[:, S + 3:] == 0).all())
+    assert bool((fr[:, :, :3] == 0).all()) and bool((fr[:, :, S + 3:] == 0).all()) and bool((fr[..., 3] == 0).all())
+    a, b = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g)
+    full = sr.bn_relu_f64(got, a, b, True)
+    assert float((full - torch.relu(ref * a.double()[None, :, None, None] + b.double()[None, :, None, None])).abs().max()) < 1e-10
+    assert sr.bn_relu_f64(got, None, None, False) is got
+
+
+def test_framed_stem_reference_notices_a_shifted_frame():
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(1, 3, 32, 32, generator=g, dtype=torch.float64)
+    w = torch.randn(8, 3, 7, 7, generator=g, dtype=torch.float64)
+    fr = torch.roll(sr.frame_image(x), 1, dims=2)               # image one column to the right
+    assert float((sr.stem_conv_framed_f64(fr, sr.pack_stem_weights(w)) - F.conv2d(x, w, stride=2, padding=3)).abs().max()) > 0.1
+
+
+def test_resize_reference_identity_and_f32_error():
+    g = torch.Generator().manual_seed(2)
+    for (IH, IW, S) in [(224, 224, 256), (200, 312, 256), (256, 256, 256), (224, 224, 32), (37, 53, 64)]:
+        x = torch.randn(3, 3, IH, IW, generator=g)
+        r64 = sr.resize_f64(x, S)
+        r32 = F.interpolate(x, (S, S), mode="bilinear", align_corners=True)
+        e = float((r32.double() - r64).abs().max())
+        # f32 places a sample with the rounded ratio (IH - 1) / (S - 1): up to 1e-5 of a pixel off at the far border, times the slope of noise
+        assert r64.shape == (3, 3, S, S) and e < 2e-4
+        if IH == S and IW == S:
+            assert torch.equal(r64, x.double()) and e == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------- IST regressor
+def _ist(seed):
+    from test_oracle_pose_ist import build_ist, mlp_weights
+
+    net = build_ist(seed)
+    return net, mlp_weights(net)
+
+
+def test_ist_regressor_f64_equals_the_module_in_double():
+    net, w = _ist(101)
+    feats = torch.randn(300, 512, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
+    sc, cs = sr.ist_regressor_f64(feats, w)
+    reg = net.regressor.double()
+    with torch.no_grad():
+        rsc, rcs = reg.scale_predictor(feats)[:, 0], reg.inplane_predictor(feats)
+    assert float((sc - rsc).abs().max()) < 1e-12 and float((cs - rcs).abs().max()) < 1e-12
+    assert isinstance(reg.inplane_predictor[-1], torch.nn.Tanh) and float(cs.abs().max()) <= 1.0
+    net.regressor.float()
+
+
+def test_ist_live_sets_have_the_row_counts_they_are_named_after():
+    B, k = 4, 3
+    R = B * k * sr.P
+    assert R == 3072 == 24 * 128 and sr.IST_LIVE_COUNTS == (0, 1, 127, 128, 129, 1280, 1281, R - 1, R)
+    tar, src, order = sr.ist_points_case(7, B, k)
+    assert sorted(order.tolist()) == list(range(R)) and order[0] >= R - sr.P
+    assert tar.min() >= 0 and tar.max() <= 15 and src.min() >= 0 and src.max() <= 15
+    prev = np.zeros(R, bool)
+    for n in sr.IST_LIVE_COUNTS:
+        tp, sp, live = sr.ist_live_set(tar, src, order, n)
+        valid = ((tp != -1).all(-1) & (sp != -1).all(-1)).reshape(R)
+        assert int(valid.sum()) == n == int(live.sum()) and (valid == live).all()
+        assert (tp.reshape(R, 2)[live] == tar.reshape(R, 2)[live]).all() and (sp.reshape(R, 2)[live] == src.reshape(R, 2)[live]).all()
+        assert (tp.reshape(R, 2)[~live] == -1).all() and (sp.reshape(R, 2)[~live] == -1).all()
+        assert (live | ~prev).all()                                      # nested
+        prev = live
+        if n == 1:
+            assert live[R - sr.P:].sum() == 1                            # the single live row sits in the last (b, j) block
+    # half-specified rows: exactly one coordinate of a side is -1, and the oracle's validity rule calls them invalid
+    tp, sp, live = sr.ist_live_set(tar, src, order, 1280)
+    tp2, sp2, rows = sr.ist_half_specified(tp, sp, live, 9)
+    t2, s2 = tp2.reshape(R, 2)[rows], sp2.reshape(R, 2)[rows]
+    assert not live[rows].any() and len(set(rows.tolist())) == 64
+    assert (((t2 == -1).sum(1) == 1) | ((s2 == -1).sum(1) == 1)).all() and ((t2 == -1).sum(1) <= 1).all() and ((s2 == -1).sum(1) <= 1).all()
+    assert ((t2[:, 0] == -1) & (t2[:, 1] != -1)).any() and ((t2[:, 1] == -1) & (t2[:, 0] != -1)).any()
+    assert ((s2[:, 0] == -1) & (s2[:, 1] != -1)).any() and ((s2[:, 1] == -1) & (s2[:, 0] != -1)).any()
+    valid2 = ((tp2 != -1).all(-1) & (sp2 != -1).all(-1)).reshape(R)
+    assert (valid2 == live).all()
+
+
+def test_ist_gather_f64_and_the_oracle_agree_on_the_live_rows():
+    """The float64 gather + regressor against the CPU oracle (f32 fmaf chains) on one live set: same rows, f32-class difference; a
+    gather that exchanges x and y is noticed."""
+    from oracle import cpu as oracle
+
+    net, w = _ist(111)
+    rs = np.random.RandomState(112)
+    O, N, B, k = 2, 5, 4, 3
+    bank = rs.standard_normal((O, N, 256, 256)).astype(np.float32)
+    tarf = rs.standard_normal((B, 256, 256)).astype(np.float32)
+    labels0 = rs.randint(0, O, B).astype(np.int32)
+    ids = rs.randint(0, N, (B, k)).astype(np.int64)
+    tar, src, order = sr.ist_points_case(113, B, k)
+    tp, sp, live = sr.ist_live_set(tar, src, order, 129)
+    osc, ocs = oracle.ist_inference(tarf, bank[labels0[:, None], ids], tp, sp, w)
+    rows = np.nonzero(live)[0]
+    assert ((osc.reshape(-1) == -1000) == ~live).all()
+    sc, cs = sr.ist_regressor_f64(sr.ist_gather_f64(tarf, bank, labels0, ids, tp, sp, rows), w)
+    mag = float(sc.abs().max())
+    assert float((torch.from_numpy(osc.reshape(-1)[rows]).double() - sc).abs().max()) < 1e-5 * max(1.0, mag)
+    assert float((torch.from_numpy(ocs.reshape(-1, 2)[rows]).double() - cs).abs().max()) < 1e-5
+    swapped = sr.ist_gather_f64(tarf, bank, labels0, ids, tp, sp[..., ::-1], rows)
+    sc2, _ = sr.ist_regressor_f64(swapped, w)
+    assert float((sc2 - sc).abs().max()) > 1e-2 * max(1.0, mag)
