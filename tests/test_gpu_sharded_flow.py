@@ -8,23 +8,18 @@
     all_gather_into_tensor / all_to_all_single on device buffers, including the status-word all-gather and the done-word exchange.
 """
 import os
-import socket
 
 import numpy as np
 import pandas as pd
 import pytest
 import torch
 
+from gigapose_testing import spawn
+from gigapose_testing.spawn import free_port as _free_port
+
 pytestmark = pytest.mark.gpu
 SIZES = {0: [5, 9, 0], 1: [7, 3, 12]}
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+COLLECTIVE_S, SPAWN_S = 60, 900   # a rank that dies inside a collective frees its peers (and the GPU) after 60 s; the join has a deadline
 
 
 def _image(tset, seed, n, view_id, dev):
@@ -94,11 +89,9 @@ def _compare(want, got, sizes, numerics, who):
 def _worker(rank, world, port, tmp):
     import torch.distributed as dist
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    spawn.init_gloo(rank, world, port, COLLECTIVE_S)
     try:
         for numerics in ("chain", "split"):
             want, _ = _run(tmp, "plain_" + numerics, numerics, SIZES[rank], rank, dev, sharded=False, rows=0)
@@ -111,9 +104,7 @@ def _worker(rank, world, port, tmp):
 
 
 def test_sharded_test_step_with_different_detection_counts_per_rank_two_ranks_on_one_gpu(tmp_path):
-    import torch.multiprocessing as mp
-
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    spawn.spawn_and_join(_worker, (2, _free_port(), str(tmp_path)), nprocs=2, deadline_s=SPAWN_S)
 
 
 @pytest.mark.parametrize("numerics", ["chain", "split"])
@@ -141,11 +132,9 @@ def _replica_worker(rank, world, port, tmp):
 
     from gigapose_testing import factory
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    spawn.init_gloo(rank, world, port, COLLECTIVE_S)
     try:
         tset = factory.TemplateSet(2, 11, seed=70)
         model = factory.build_model("dinov2_vits14", k=5, device=dev, seed=5, log_dir=os.path.join(tmp, "owned"))
@@ -169,9 +158,7 @@ def _replica_worker(rank, world, port, tmp):
 
 
 def test_round_robin_image_ownership_with_two_replicas_on_one_gpu(tmp_path):
-    import torch.multiprocessing as mp
-
-    mp.spawn(_replica_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    spawn.spawn_and_join(_replica_worker, (2, _free_port(), str(tmp_path)), nprocs=2, deadline_s=SPAWN_S)
     # the same images through ONE process: identical files (chain numerics: a crop's result does not depend on its batch)
     from gigapose_testing import factory
 

@@ -5,31 +5,21 @@ object's templates (81 + 81 of 162, and the uneven 6 + 5 of 11), runs GigaPose.p
 both ranks' query rows, gp_match_tiles[_split] / gp_topk / gp_gather_records run on the rank-major gathered rows against a shard
 with a non-zero template offset, exchange #2 returns each rank the candidates of its crops, merge, IST / RANSAC / recovery --
 and every tensor of the result must equal, bit for bit, the unsharded predict of the same crops in the same process."""
-import os
-import socket
-
 import pytest
 import torch
 
+from gigapose_testing import spawn
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+COLLECTIVE_S, SPAWN_S = 60, 900   # a rank that dies inside a collective frees its peers (and the GPU) after 60 s; the join has a deadline
 
 
 def _worker(rank, world, port):
     import torch.distributed as dist
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    spawn.init_gloo(rank, world, port, COLLECTIVE_S)
     try:
         from gigapose_amd import _lib
         from gigapose_testing import factory
@@ -68,6 +58,4 @@ def _worker(rank, world, port):
 
 
 def test_template_sharded_predict_with_two_ranks_on_one_gpu_equals_unsharded():
-    import torch.multiprocessing as mp
-
-    mp.spawn(_worker, args=(2, _free_port()), nprocs=2, join=True)
+    spawn.spawn_and_join(_worker, (2, spawn.free_port()), nprocs=2, deadline_s=SPAWN_S)
