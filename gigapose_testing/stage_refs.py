@@ -275,3 +275,141 @@ def ist_half_specified(tar_pts, src_pts, live, seed, n=64):
         else:
             tp[r, 1], sp[r, 0] = -1, -1
     return tp.reshape(tar_pts.shape), sp.reshape(src_pts.shape), rows
+
+
+# ---------------------------------------------------------------------------------------------------------------- split attention
+T_TOK = 257                      # tokens per crop: cls + 256 patches
+ATTN_CHUNKS = ((0, 96), (96, 192), (192, 257))     # attention_split_kernel's three passes over the keys (the last one holds 65 + 31 masked)
+ATTN_CLASSES = ("plain", "peaked", "sink", "sink256", "offset", "uniform", "zero_q", "descending", "ascending")
+ATTN_OTHER_SCALE = ("plain", "peaked", "offset")   # the classes that also run on planes that carry another scale than 8
+
+
+def attention_case(cls, B, H, seed):
+    """-> q | k | v as one f32 tensor [B * 257][3 * 64 H] (the layout gp_attention_split reads, before the split into planes).
+    Base: N(0, 1) everywhere.  d = a random unit vector of the 64 head channels (one per case).
+      plain       q, k x 1.5                                       logit std 2-3 (the only kind of input the stage tests had)
+      peaked      q, k x 4                                          softmax close to one-hot
+      sink        q += 6 d, k[0] += 30 d, k[256] += 30 d            two keys (the first and the LAST) take nearly all the weight
+      sink256     q += 6 d, k[256] += 30 d                          the one valid key of the masked last tile takes it
+      offset      channel 7 of q = 40 + 0.1 n, of k = 60 + 0.1 n    logits near 300 with an ordinary spread: the f32 rounding of the logit
+      uniform     every key of an image = its key 0                 softmax = 1 / 257 exactly: the output is the column mean of V
+      zero_q      q = 0                                             the same through zero logits
+      descending  q += 8 d, k[:96] += 12 d, k[96:] -= 12 d          the maximum sits in chunk 0, > 15 log2 units above the later chunks
+      ascending   q += 8 d, k[:192] -= 12 d, k[192:] += 12 d        ... in the last chunk: the running reference jumps, alpha ~ 0"""
+    assert cls in ATTN_CLASSES
+    g = torch.Generator().manual_seed(seed)
+    q, k, v = (torch.randn(B, T_TOK, H, 64, generator=g, dtype=torch.float64) for _ in range(3))
+    d = torch.randn(64, generator=g, dtype=torch.float64)
+    d = d / d.norm()
+    n1, n2 = (torch.randn(B, T_TOK, H, generator=g, dtype=torch.float64) for _ in range(2))
+    if cls == "plain":
+        q, k = 1.5 * q, 1.5 * k
+    elif cls == "peaked":
+        q, k = 4.0 * q, 4.0 * k
+    elif cls in ("sink", "sink256"):
+        q = q + 6.0 * d
+        k[:, 256] += 30.0 * d
+        if cls == "sink":
+            k[:, 0] += 30.0 * d
+    elif cls == "offset":
+        q[..., 7] = 40.0 + 0.1 * n1
+        k[..., 7] = 60.0 + 0.1 * n2
+    elif cls == "uniform":
+        k = k[:, :1].expand(B, T_TOK, H, 64).clone()
+    elif cls == "zero_q":
+        q = torch.zeros_like(q)
+    elif cls == "descending":
+        q = q + 8.0 * d
+        k[:, :96] += 12.0 * d
+        k[:, 96:] -= 12.0 * d
+    elif cls == "ascending":
+        q = q + 8.0 * d
+        k[:, :192] -= 12.0 * d
+        k[:, 192:] += 12.0 * d
+    return torch.stack([q, k, v], dim=2).reshape(B * T_TOK, 3 * 64 * H).float()
+
+
+def attention_qkv(vals, B, H):
+    """[B * 257][3 * 64 H] values (any float type) -> q, k, v [B][H][257][64]."""
+    x = vals.reshape(B, T_TOK, 3, H, 64)
+    return x[:, :, 0].permute(0, 2, 1, 3), x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)
+
+
+def attention_logits(vals, B, H):
+    """float64 logits q . k / 8 [B][H][query][key] (HF modeling_dinov2.py:207-229, head width 64)."""
+    q, k, _ = attention_qkv(vals.double(), B, H)
+    return q @ k.transpose(-1, -2) * 0.125
+
+
+def attention_ref(vals, B, H, dtype=torch.float64):
+    """softmax(q k^T / 8) v evaluated in `dtype` on the given values -> [B][257][H][64] (the layout of the output planes).
+    float64: the reference.  float32: torch's own f32 evaluation of the same formula (one rounding of the scaled logit, as the kernel has),
+    whose error against float64 sets the kernel's bound."""
+    q, k, v = attention_qkv(vals.to(dtype), B, H)
+    return (torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1) @ v).permute(0, 2, 1, 3)
+
+
+def attention_preconditions(cls, logits, vals=None, B=None, H=None):
+    """{name: (figure, holds)} of the class on its float64 logits [B][H][257][257]: what makes the case the edge it is named after.
+    A generator that stops producing the edge fails here, not silently in front of the kernel."""
+    p = torch.softmax(logits, dim=-1)
+    ent = -(p * torch.log(p.clamp_min(1e-300))).sum(-1)
+    out = {}
+    if cls == "plain":
+        s = float(logits.std())
+        out["logit std in [2, 3]"] = (s, 2.0 <= s <= 3.0)
+    elif cls == "peaked":
+        out["mean entropy < 0.5"] = (float(ent.mean()), float(ent.mean()) < 0.5)
+        out["logit std > 10"] = (float(logits.std()), float(logits.std()) > 10.0)
+    elif cls == "sink":
+        top = float(p.max(-1).values.mean())
+        out["mean top weight > 0.7"] = (top, top > 0.7)
+        frac = float(((p[..., 0] + p[..., 256]) > 0.99).double().mean())
+        out["keys 0 + 256 hold > 0.99 of the weight in > 99 % of rows"] = (frac, frac > 0.99)
+        first = float((logits.argmax(-1) == 0).double().mean())
+        out["key 0 leads in 30-70 % of rows, key 256 in the others"] = (first, 0.3 <= first <= 0.7)
+    elif cls == "sink256":
+        frac = float((logits.argmax(-1) == 256).double().mean())
+        out["argmax key = 256 in > 99 % of rows"] = (frac, frac > 0.99)
+        f256 = float((logits[:, :, 256].argmax(-1) == 256).double().mean())
+        out["... and for every query 256"] = (f256, f256 == 1.0)
+    elif cls == "offset":
+        out["max |logit| > 250"] = (float(logits.abs().max()), float(logits.abs().max()) > 250.0)
+        out["mean entropy > 4.5"] = (float(ent.mean()), float(ent.mean()) > 4.5)
+    elif cls in ("uniform", "zero_q"):
+        spread = float((logits.max(-1).values - logits.min(-1).values).max())
+        out["logits of a row all equal (to float64 round-off of the 64-term dot products)"] = (spread, spread <= 1e-12)
+    else:
+        LOG2E = 1.4426950408889634
+        cm = torch.stack([logits[..., a:b].max(-1).values for a, b in ATTN_CHUNKS], dim=-1) * LOG2E      # chunk maxima, log2 units
+        lead = 0 if cls == "descending" else 2
+        others = [c for c in range(3) if c != lead]
+        gap = cm[..., lead] - torch.maximum(cm[..., others[0]], cm[..., others[1]])
+        frac = float((gap > 15.0).double().mean())
+        out[f"chunk {lead} maximum > 15 log2 units above both others in >= 99 % of rows (minimum gap {float(gap.min()):.1f})"] = (frac, frac >= 0.99)
+    return out
+
+
+# deliberately wrong attention "references" (tests/test_stage_refs.py shows that the float64 reference tells each from the right one by far
+# more than the bound the kernel is held to -- every one is a bug attention_split_kernel could have)
+def attention_mutant(kind, vals, B, H):
+    q, k, v = attention_qkv(vals.double(), B, H)
+    if kind == "drop_key_256":            # wave 0 forgets key 256 / the last tile is masked one key too early
+        return (torch.softmax(q @ k[:, :, :256].transpose(-1, -2) * 0.125, dim=-1) @ v[:, :, :256]).permute(0, 2, 1, 3)
+    if kind == "scale_63":                # 1 / sqrt(63) instead of 1 / 8
+        return (torch.softmax(q @ k.transpose(-1, -2) * 63.0 ** -0.5, dim=-1) @ v).permute(0, 2, 1, 3)
+    if kind == "per_chunk_max":           # every chunk relative to its OWN maximum, no alpha rescale of what came before
+        s = q @ k.transpose(-1, -2) * 0.125
+        num, den = 0.0, 0.0
+        for a, b in ATTN_CHUNKS:
+            pc = torch.exp(s[..., a:b] - s[..., a:b].max(-1, keepdim=True).values)
+            num, den = num + pc @ v[:, :, a:b], den + pc.sum(-1, keepdim=True)
+        return (num / den).permute(0, 2, 1, 3)
+    raise ValueError(kind)
+
+
+def attention_bound(e32, scale):
+    """The kernel's bound on max |err| / max |ref|: twice torch's own f32 evaluation of the formula on the same values (a different
+    summation order and nothing else), not below the stage bound the kernel already had (2e-6 on x 8 planes, 4e-6 on others), plus the
+    output planes' 22 bits."""
+    return max(2.0 * e32, 2e-6 if scale == 8.0 else 4e-6) + 2.0 ** -21

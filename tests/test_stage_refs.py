@@ -229,3 +229,70 @@ def test_ist_gather_f64_and_the_oracle_agree_on_the_live_rows():
     swapped = sr.ist_gather_f64(tarf, bank, labels0, ids, tp, sp[..., ::-1], rows)
     sc2, _ = sr.ist_regressor_f64(swapped, w)
     assert float((sc2 - sc).abs().max()) > 1e-2 * max(1.0, mag)
+
+
+# ---------------------------------------------------------------------------------------------------------------- split attention
+def _attention_values(cls, B, H, seed, scale=8.0):
+    hi, lo = sr.split_planes_host(sr.attention_case(cls, B, H, seed), scale)
+    return sr.planes_value(hi, lo, scale)
+
+
+def test_attention_ref_is_torchs_own_float64_attention():
+    B, H = 2, 3
+    vals = _attention_values("plain", B, H, 3)
+    q, k, v = sr.attention_qkv(vals, B, H)
+    want = F.scaled_dot_product_attention(q, k, v).permute(0, 2, 1, 3)         # scale = 64^-0.5
+    got = sr.attention_ref(vals, B, H)
+    assert got.dtype == torch.float64 and got.shape == (B, sr.T_TOK, H, 64)
+    assert float((got - want).abs().max()) < 1e-13
+    # the layout: q | k | v blocks of 64 H channels per token row, head-major inside a block
+    x = vals.reshape(B, sr.T_TOK, 3 * 64 * H)
+    assert torch.equal(q[1, 2, 5], x[1, 5, 2 * 64:3 * 64]) and torch.equal(v[0, 1, 256], x[0, 256, 2 * 64 * H + 64:2 * 64 * H + 128])
+
+
+@pytest.mark.parametrize("cls", sr.ATTN_CLASSES)
+def test_attention_classes_hold_their_preconditions_and_the_reference_rejects_wrong_kernels(cls):
+    """Per input class of tests/test_gpu_attention_split.py, at the ViT-L geometry, on the CPU: (1) the class's preconditions hold on
+    the float64 logits, (2) the bound the kernel is held to is small against what a wrong kernel does: a kernel that drops key 256, one that
+    scales by 1 / sqrt(63), one that takes every chunk of keys relative to its own maximum without rescaling -- each differs from the float64
+    reference by more than 20 x the bound (where the class can see the bug at all: equal logits hide a wrong scale and a wrong maximum, the
+    descending class gives key 256 no weight; those pairs are named below and shown to be blind, so nobody counts on them)."""
+    B, H = 3, 16
+    vals = _attention_values(cls, B, H, 5)
+    pre = sr.attention_preconditions(cls, sr.attention_logits(vals, B, H))
+    assert pre and all(ok for _, ok in pre.values()), pre
+    ref = sr.attention_ref(vals, B, H)
+    e32 = float((sr.attention_ref(vals, B, H, torch.float32).double() - ref).abs().max() / ref.abs().max())
+    bound = sr.attention_bound(e32, 8.0)
+    assert 1e-7 < e32 < 2e-4 and bound < 2e-4          # offset: ~7e-5 (the logit's own f32 rounding at |logit| ~ 300); every other < 1e-5
+    if cls in ("uniform", "zero_q"):
+        _, _, v = sr.attention_qkv(vals, B, H)
+        mean = v.mean(dim=2, keepdim=True).expand(-1, -1, sr.T_TOK, -1).permute(0, 2, 1, 3)
+        assert float((ref - mean).abs().max()) < 1e-14                                       # the reference IS the column mean of V
+    blind = {"uniform": ("scale_63", "per_chunk_max"), "zero_q": ("scale_63", "per_chunk_max"),
+             "descending": ("drop_key_256",)}.get(cls, ())      # descending: key 256 carries < 2^-15 of every row's weight
+    for kind in ("drop_key_256", "scale_63", "per_chunk_max"):
+        d = sr.attention_mutant(kind, vals, B, H) - ref
+        err = float(d.abs().max() / ref.abs().max())
+        err256 = float(d[:, 256].abs().max() / ref.abs().max())
+        if kind in blind:
+            assert err < 0.1 * bound, (kind, err)
+            continue
+        assert err > 20.0 * bound, (kind, err, bound)
+        if kind == "drop_key_256":
+            assert err256 > 20.0 * bound, (kind, err256, bound)      # query 256 has its own path to key 256: seen on that row alone too
+
+
+def test_attention_preconditions_reject_another_class():
+    """A generator that quietly stops producing its edge fails its precondition: each class's conditions, put to a case of another class."""
+    B, H = 3, 16
+    for cls, other in (("peaked", "plain"), ("plain", "peaked"), ("sink", "sink256"), ("sink256", "sink"), ("offset", "plain"),
+                       ("uniform", "plain"), ("zero_q", "plain"), ("descending", "ascending"), ("ascending", "descending"),
+                       ("descending", "peaked")):
+        pre = sr.attention_preconditions(cls, sr.attention_logits(_attention_values(other, B, H, 5), B, H))
+        assert not all(ok for _, ok in pre.values()), (cls, other, pre)
+
+
+def test_attention_bound_is_the_stage_bound_for_plain_inputs():
+    assert sr.attention_bound(9.0e-7, 8.0) == 2e-6 + 2.0 ** -21 and sr.attention_bound(9.0e-7, 0.5) == 4e-6 + 2.0 ** -21
+    assert sr.attention_bound(7.2e-5, 8.0) == 1.44e-4 + 2.0 ** -21
