@@ -1,0 +1,292 @@
+"""GPU: RGBA renders -> templates (libgigapose_onboard.so, gigapose_amd/onboard.py).
+
+The two kernels against the reference golden (tests/golden/onboard_templates.npz: PIL getbbox + the unmodified CropResizePad);
+the alpha boxes against numpy on frames whose templates and rows are misaligned, with stale output buffers; the crop against
+oracle/crop_numpy.py on every box class of the source-index arithmetic and, with explicit boxes, against the existing
+gp_crop_resize_pad kernel; the error paths; and RenderedTemplates -> set_template_data -> predict against the same model
+onboarded from host-prepared items.  Everything is compared bit for bit: same arithmetic on the same input bits."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gigapose_testing import factory, renders
+from gigapose_testing import synthetic as syn
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def assert_bits(got, want, what):
+    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+    want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
+    assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
+
+
+def nan_outputs(N, T):
+    return {"rgb": torch.full((N, 3, T, T), float("nan"), device=DEV), "mask": torch.full((N, T, T), float("nan"), device=DEV),
+            "M": torch.full((N, 3, 3), float("nan"), device=DEV)}
+
+
+# ---------------------------------------------------------------------------------------------- 1. the reference golden
+def test_onboarder_equals_the_reference_golden(golden_dir):
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    g = np.load(os.path.join(golden_dir, "onboard_templates.npz"))
+    rgba = renders.golden_renders(int(g["seed"]))
+    assert str(g["input_checksum"]) == syn.checksum(rgba)
+    out = TemplateOnboarder()(_t(rgba))
+    assert_bits(out["box"], g["boxes"], "boxes")
+    for name in ("rgb", "mask", "M"):
+        assert_bits(out[name], g[name], name)
+
+
+# ---------------------------------------------------------------------------------------------- 2. alpha boxes
+def placements(H, W):
+    """name -> list of (y, x, alpha): where a render has alpha."""
+    row, col = H // 2, W // 3
+    return {"corner (0,0)": [(0, 0, 255)], "corner (0,W-1)": [(0, W - 1, 9)], "corner (H-1,0)": [(H - 1, 0, 128)],
+            "only (H-1,W-1)": [(H - 1, W - 1, 2)], "one pixel of alpha 1": [(H // 2, W // 2 + 1, 1)],
+            "full frame": [(y, x, 1 + (x + y) % 255) for y in range(H) for x in range(W)],
+            "one row": [(row, x, 200) for x in range(W)], "one column": [(y, col, 4) for y in range(H)],
+            "opposite corners": [(0, W - 1, 1), (H - 1, 0, 64)]}
+
+
+def render_at(colour, pixels):
+    H, W, _ = colour.shape
+    rgba = np.zeros((H, W, 4), np.uint8)
+    rgba[..., :3] = colour
+    if len(pixels) == H * W:
+        rgba[..., 3] = np.asarray([a for _, _, a in pixels], np.uint8).reshape(H, W)
+    else:
+        for y, x, a in pixels:
+            rgba[y, x, 3] = a
+    return rgba
+
+
+@pytest.mark.parametrize("H,W,N", [(5, 61, 3), (33, 130, 2), (48, 64, 4), (480, 640, 2)])
+def test_alpha_boxes_equal_numpy(H, W, N):
+    """(5,61,3) and (33,130,2): H*W*4 is no multiple of 16, so every template but the first starts misaligned and the rows do
+    too (one pixel per lane); (48,64,4) and (480,640,2) take the 16-byte loads, the last with several row bands per template.
+    Call k holds placements k, k+1, ... so every template slot sees every placement; the SAME boxes / flag buffers serve every
+    call (first filled with garbage), and the renders are a view with a storage offset into a larger batch."""
+    from gigapose_amd import onboard
+
+    colour = renders.colour_field(np.random.RandomState(H * 1000 + W), H, W)
+    assert (colour > 0).all()                                # colour where alpha is 0: an any-channel box would be the full frame
+    views = {k: render_at(colour, p) for k, p in placements(H, W).items()}
+    names = list(views)
+    boxes = torch.full((N, 4), -0x0123456789abcdef, dtype=torch.int64, device=DEV)
+    boxes[:, 2:] = 0x7fffffffffffffff
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for k in range(len(names)):
+        batch = np.stack([views[names[(k + n) % len(names)]] for n in range(-1, N)])     # one render more, in front
+        want = renders.alpha_boxes_numpy(batch[1:])
+        assert (want[:, 2] > want[:, 0]).all()
+        view = _t(batch)[1:]
+        assert view.storage_offset() == H * W * 4 and view.is_contiguous()
+        onboard._alpha_boxes(view, boxes, err)
+        assert int(err.item()) == 0
+        assert_bits(boxes, want, f"call {k} ({names[k]} first)")
+        assert_bits(onboard.alpha_boxes(view), want, f"alpha_boxes, call {k}")
+
+
+# ---------------------------------------------------------------------------------------------- 3. / 4. the crop
+@pytest.fixture(scope="module")
+def classes():
+    names, rgba, boxes = renders.box_class_renders()
+    return dict(names=names, rgba=rgba, boxes=boxes, dev=_t(rgba), ref={224: renders.prepare_numpy(rgba, boxes, 224)})
+
+
+def check_against_numpy(out, ref, names):
+    rgb, mask, M, boxes = ref
+    assert_bits(out["box"], boxes, "boxes")
+    for n, name in enumerate(names):
+        assert_bits(out["rgb"][n], rgb[n], f"rgb of '{name}'")
+        assert_bits(out["mask"][n], mask[n], f"mask of '{name}'")
+        assert_bits(out["M"][n], M[n], f"M of '{name}'")
+    assert not any(bool(torch.isnan(out[k]).any()) for k in ("rgb", "mask", "M")), "a pixel was not written"
+
+
+def test_crop_equals_crop_numpy_on_every_box_class(classes):
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    out = TemplateOnboarder(target_size=224)(classes["dev"], out=nan_outputs(len(classes["names"]), 224))
+    check_against_numpy(out, classes["ref"][224], classes["names"])
+    pad = (0.0 - np.float32(syn.CLIP_MEAN[0])) / np.float32(syn.CLIP_STD[0])
+    tall = classes["names"].index("30 x 460: tall")
+    assert out["rgb"][tall, 0, 100, 0].item() == pad and out["mask"][tall, 100, 0].item() == 0.0      # padding: (0 - mean) / std
+    assert len(torch.unique(out["mask"])) > 200                                                          # 256 levels, not binarised
+
+
+def test_crop_equals_crop_numpy_at_target_98(classes):
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    pick = [0, 1, 4, 6, 8, 9, 11, 12]
+    names = [classes["names"][i] for i in pick]
+    ref = renders.prepare_numpy(classes["rgba"][pick], classes["boxes"][pick], 98)
+    out = TemplateOnboarder(target_size=98)(classes["dev"][pick], out=nan_outputs(len(pick), 98))
+    check_against_numpy(out, ref, names)
+
+
+def test_explicit_boxes_equal_the_existing_crop_kernel(classes):
+    """boxes= given: the result is gigapose_amd.crop.CropResizePad (gp_crop_resize_pad, itself bit-exact against the reference) on
+    the planar rgba / 255, then the normalisation in torch.  Boxes other than the alpha boxes, two of them past the frame's border
+    (the slicing clamp) and one that starts at the last pixel."""
+    from gigapose_amd.crop import CropResizePad
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    boxes = np.asarray([(10, 20, 300, 310), (600, 400, 700, 520), (0, 0, 640, 480), (320, 100, 432, 212), (639, 479, 650, 490),
+                        (100, 50, 324, 274), (3, 7, 64, 471), (500, 300, 900, 420)], np.int64)
+    rgba = classes["dev"][:len(boxes)]
+    out = TemplateOnboarder()(rgba, boxes=boxes)
+    assert_bits(out["box"], boxes, "boxes")
+    planar = (rgba.cpu().permute(0, 3, 1, 2).float() / 255).contiguous()       # the division on the CPU: IEEE, as the kernel's
+    ref = CropResizePad(target_size=224)(_t(boxes), planar.to(DEV))
+    images = ref["images"].cpu()
+    mean, std = torch.tensor(syn.CLIP_MEAN).view(3, 1, 1), torch.tensor(syn.CLIP_STD).view(3, 1, 1)
+    assert_bits(out["rgb"], ((images[:, :3] - mean) / std).contiguous(), "rgb")
+    assert_bits(out["mask"], images[:, 3].contiguous(), "mask")
+    assert_bits(out["M"], ref["M"], "M")
+
+
+def test_word_index_past_2_to_31():
+    """7000 renders at 480 x 640 are 2.15e9 pixels (8.6 GB): the last render lies past a 32-bit word index, every render after
+    the 1748th past a 32-bit byte offset.  The batch is zeros made on the device; only the first and the last render are real."""
+    from gigapose_amd import onboard
+
+    N, H, W, T = 7000, 480, 640, 32
+    assert N * H * W > 2 ** 31
+    real = renders.renders_with_boxes(9, H, W, [(600, 440, 640, 480), (3, 401, 90, 478)])
+    dev = torch.zeros(N, H, W, 4, dtype=torch.uint8, device=DEV)
+    dev[0].copy_(_t(real[0]))
+    dev[N - 1].copy_(_t(real[1]))
+    boxes = torch.full((N, 4), -1, dtype=torch.int64, device=DEV)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    onboard._alpha_boxes(dev, boxes, err)
+    assert 2 <= int(err.item()) <= N - 1                       # one of the transparent renders in between is reported
+    want = np.zeros((N, 4), np.int64)
+    want[[0, N - 1]] = renders.alpha_boxes_numpy(real)
+    assert_bits(boxes, want, "boxes")
+    explicit = np.tile(np.asarray([(5, 400, 95, 479)], np.int64), (N, 1))
+    explicit[0] = want[0]
+    out = onboard.TemplateOnboarder(target_size=T)(dev, boxes=explicit, out=nan_outputs(N, T))
+    rgb, mask, M, _ = renders.prepare_numpy(real, explicit[[0, N - 1]], T)
+    for k, n in enumerate((0, N - 1)):
+        assert_bits(out["rgb"][n], rgb[k], f"rgb {n}")
+        assert_bits(out["mask"][n], mask[k], f"mask {n}")
+        assert_bits(out["M"][n], M[k], f"M {n}")
+    assert float(out["mask"][1:N - 1].abs().max()) == 0.0 and not bool(torch.isnan(out["rgb"]).any())
+    del dev, out
+    torch.cuda.empty_cache()
+
+
+# ---------------------------------------------------------------------------------------------- 5. errors
+def test_fully_transparent_template_is_named_and_left_untouched():
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    rgba = renders.golden_renders()[[0, 4, 6]].copy()
+    rgba[1, ..., 3] = 0                                      # colour everywhere, alpha nowhere
+    out = nan_outputs(3, 224)
+    with pytest.raises(ValueError, match=r"template 1 is fully transparent"):
+        TemplateOnboarder()(_t(rgba), out=out)
+    rgb, mask, M, _ = renders.prepare_numpy(rgba[[0, 2]])
+    for k, n in enumerate((0, 2)):
+        assert_bits(out["rgb"][n], rgb[k], f"rgb {n}")
+        assert_bits(out["mask"][n], mask[k], f"mask {n}")
+        assert_bits(out["M"][n], M[k], f"M {n}")
+    assert all(bool(torch.isnan(out[key][1]).all()) for key in ("rgb", "mask", "M")), "the bad template's outputs were written"
+
+
+def test_alpha_column_that_scales_to_nothing_raises():
+    from gigapose_amd.onboard import TemplateOnboarder, alpha_boxes
+
+    rgba = renders.renders_with_boxes(5, 480, 640, [(100, 100, 200, 200)] * 2)
+    rgba[1, ..., 3] = 0
+    rgba[1, 120:360, 333, 3] = 255                           # 1 x 240: 224 / 240 of a pixel wide, F.interpolate raises in the reference
+    dev = _t(rgba)
+    assert alpha_boxes(dev).tolist() == [[100, 100, 200, 200], [333, 120, 334, 360]]
+    with pytest.raises(ValueError, match=r"template 1 .*box scales to an empty crop"):
+        TemplateOnboarder()(dev)
+
+
+def test_cpu_input_raises():
+    from gigapose_amd import _lib
+    from gigapose_amd.onboard import RenderedTemplates, TemplateOnboarder, alpha_boxes
+
+    rgba = torch.from_numpy(renders.golden_renders()[:2])
+    with pytest.raises(_lib.GigaPoseHipError):
+        TemplateOnboarder()(rgba)
+    with pytest.raises(_lib.GigaPoseHipError):
+        alpha_boxes(rgba.numpy())
+    with pytest.raises(_lib.GigaPoseHipError):
+        RenderedTemplates([(rgba, renders.object_poses(1, 2))], device="cpu")[0]
+
+
+# ---------------------------------------------------------------------------------------------- 6. determinism
+def test_two_runs_give_the_same_bits(classes):
+    from gigapose_amd.onboard import TemplateOnboarder
+
+    a = TemplateOnboarder()(classes["dev"])
+    b = TemplateOnboarder()(classes["dev"])
+    for key in ("box", "rgb", "mask", "M"):
+        assert_bits(a[key], b[key], key)
+
+
+# ---------------------------------------------------------------------------------------------- 7. through the model
+@pytest.fixture(scope="module")
+def vits_model():
+    model = factory.build_model("dinov2_vits14", k=4, device=DEV, seed=70, numerics="chain")
+    syn.condition_ist(model.ist_net)
+    return model
+
+
+class HostItems:
+    def __init__(self, items):
+        self.items = items
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, i):
+        return self.items[i]
+
+
+@pytest.mark.parametrize("numerics", ["chain", "split"])
+def test_rendered_templates_through_the_model_equal_host_prepared_items(vits_model, numerics):
+    """ViT-S, 2 objects x 6 renders at 96 x 128, 3 crops.  Route A: RenderedTemplates (u8 renders, boxes and crops on the GPU).
+    Route B: the items prepared on the host by oracle/crop_numpy.py.  Every tensor of the bank and of the prediction is equal."""
+    from gigapose_amd.onboard import RenderedTemplates
+
+    objects = [(renders.object_renders(800 + 10 * o, 6, 96, 128), renders.object_poses(900 + o, 6)) for o in range(2)]
+    host = HostItems([renders.host_item(r, p) for r, p in objects])
+    q = host[0]
+    tar_mask = (q.mask[[0, 2, 5]] > 0).float()
+    tar_K, tar_M = syn.crop_geometry(77, 3)
+    crops = dict(tar_img=(q.rgb[[0, 2, 5]] * tar_mask[:, None]).to(DEV), tar_mask=tar_mask.to(DEV), tar_K=_t(tar_K), tar_M=_t(tar_M))
+    labels = torch.tensor([1, 2, 1])
+    model = vits_model
+    model.set_numerics(numerics)
+    results = []
+    for dataset in (RenderedTemplates(objects, device=DEV), host):
+        assert len(dataset) == 2
+        model.template_datasets = {"renders": dataset}
+        model.set_template_data("renders")
+        bank = {k: v.clone() for k, v in model.template_datas["renders"].tensors.items()}
+        pred = model.predict(crops["tar_img"], crops["tar_mask"], crops["tar_K"], crops["tar_M"], labels, "renders",
+                             sort_pred_by_inliers=False)
+        torch.cuda.synchronize()
+        results.append((bank, {k: v.clone() for k, v in pred.tensors.items()}))
+    item = RenderedTemplates(objects, device=DEV)[1]
+    assert item.rgb.is_cuda and item.rgb.shape == (6, 3, 224, 224) and item.K.shape == (3, 3) and item.poses.shape == (6, 4, 4)
+    assert_bits(item.K, syn.TEMPLATE_K, "the default K")
+    for part, (a, b) in zip(("bank", "prediction"), zip(*results)):
+        assert sorted(a) == sorted(b) and len(a) >= 6
+        for key in a:
+            assert_bits(a[key], b[key], f"{numerics} {part}: {key}")
