@@ -122,20 +122,26 @@ class LocalSimilarity(torch.nn.Module):
         _lib.call("gp_l2norm_cp", _lib.ptr(x), _lib.ptr(out), _lib.i(rows), _lib.i(C), _lib.stream_ptr())
         return out
 
-    def match_tiles(self, query, qmask, bank, labels0, search_direction=None):
+    def match_tiles(self, query, qmask, bank, labels0, search_direction=None, out=None):
         """All (detection, template) tiles.  query (B,C,256) normalised, qmask (B,256),
         bank: MatchBank, labels0 (B,) int32 0-based.  Returns idx_t2s u8, score_t2s, mask_all
-        (B,N,256) and sim_avg (B,N)."""
+        (B,N,256) and sim_avg (B,N).  out: those four buffers, allocated by the caller (tests pre-fill them)."""
         split = isinstance(query, (tuple, list))
         if split != (getattr(bank, "numerics", "chain") == "split"):
             raise ValueError(f"query numerics and bank numerics ({bank.numerics}) differ")
         B, C = (query[0].shape[0], query[0].shape[2]) if split else query.shape[:2]
         N = bank.N
         dev = qmask.device
-        idx = torch.empty(B, N, P, dtype=torch.uint8, device=dev)
-        sc = torch.empty(B, N, P, dtype=torch.float32, device=dev)
-        ma = torch.empty(B, N, P, dtype=torch.float32, device=dev)
-        avg = torch.empty(B, N, dtype=torch.float32, device=dev)
+        if out is not None:
+            idx, sc, ma, avg = out
+            want = [((B, N, P), torch.uint8), ((B, N, P), torch.float32), ((B, N, P), torch.float32), ((B, N), torch.float32)]
+            if any(tuple(t.shape) != shp or t.dtype != dt or t.device != dev for t, (shp, dt) in zip(out, want)):
+                raise ValueError("match_tiles: out must be (idx u8, score f32, mask f32) of shape (B, N, 256) and sim_avg f32 (B, N) on the masks' device")
+        else:
+            idx = torch.empty(B, N, P, dtype=torch.uint8, device=dev)
+            sc = torch.empty(B, N, P, dtype=torch.float32, device=dev)
+            ma = torch.empty(B, N, P, dtype=torch.float32, device=dev)
+            avg = torch.empty(B, N, dtype=torch.float32, device=dev)
         direction = 1 if (search_direction or self.search_direction) == "src2tar" else 0   # reference matching.py:239-244
         if split:
             _lib.call("gp_match_tiles_split_dir", _lib.ptr(query[0]), _lib.ptr(query[1]), _lib.ptr(bank.hi), _lib.ptr(bank.lo),

@@ -413,3 +413,449 @@ def attention_bound(e32, scale):
     summation order and nothing else), not below the stage bound the kernel already had (2e-6 on x 8 planes, 4e-6 on others), plus the
     output planes' 22 bits."""
     return max(2.0 * e32, 2e-6 if scale == 8.0 else 4e-6) + 2.0 ** -21
+
+
+# ---------------------------------------------------------------------------------------------------------------- the split matcher
+# match_tiles_split_kernel (gp_match.hip) against float64 at every live-block layout: input builders, the float64 restatement of the
+# reference matcher on the values the kernel reads (matching.py:233-278 with find_consistency_patches :80-113), and a checker in the
+# manner of tests/parity_explain.py -- a difference from the float64 run is legitimate only where it sits on a float64 decision margin.
+MATCH_SCALE = 32.0                                   # the matcher's planes hold 32 x the unit vectors (kFeatScale)
+MATCH_COUNTS_X = (0, 1, 33, 65, 97, 129, 161, 193, 225)      # live patches per row: ceil(c / 32) = 0 .. 8
+MATCH_COUNTS_Y = (0, 32, 64, 96, 128, 160, 192, 224, 256)
+MATCH_DUP_TMPL = (7, 200)                            # template patch 200 is a copy of patch 7 (row ties)
+MATCH_DUP_QUERY = (11, 250)                          # query patch 250 is a copy of patch 11 (column ties across row groups)
+MATCH_FRAC_ROWS = (5, 6)                             # the query row / the template row whose live mask values are fractional
+MATCH_NEAR = 4e-6                                    # the fixed distance of the precondition "few decisions sit on a margin"
+MATCH_EXCUSED_CAP = 0.005                            # at most 0.5 % of the checked entries may be excused
+MATCH_O3_LABELS = (2, 0, 1, 2, 2, 0, 1, 0, 2)
+
+
+def _unit_rows(x):
+    return x / np.linalg.norm(x, axis=-1, keepdims=True)
+
+
+def match_live_masks(counts, seed, frac_row=None, keep=()):
+    """(len(counts), 256) f32 masks with exactly counts[r] live patches in row r at seeded positions.  Patches 0 (the "no match"
+    sentinel) and 255 are live in odd rows and dead in even rows wherever the count allows; the patches `keep` are live wherever the
+    count leaves room for them.  Row `frac_row` carries values in [0.75, 1) instead of 1."""
+    rs = np.random.RandomState(seed)
+    m = np.zeros((len(counts), P), np.float32)
+    for r, c in enumerate(counts):
+        order = rs.permutation(P)
+        want_live = [p for p in (0, 255) if r % 2 == 1]
+        want_dead = [p for p in (0, 255) if r % 2 == 0]
+        live = []
+        for p in want_live + list(keep):
+            if len(live) < c and p not in live and p not in want_dead:
+                live.append(p)
+        dead = set(want_dead) if P - len(want_dead) >= c else set()
+        for p in order:
+            if len(live) >= c:
+                break
+            if p not in live and p not in dead:
+                live.append(int(p))
+        for p in order:                  # a full row: the forced-dead patches come last
+            if len(live) >= c:
+                break
+            if p not in live:
+                live.append(int(p))
+        m[r, live] = 1.0
+        if r == frac_row:
+            m[r, live] = rs.uniform(0.75, 1.0, len(live)).astype(np.float32)
+    return m
+
+
+def match_blocks_case(which, C, seed=11, O=1, labels=None, anti=False, B=9, N=9):
+    """The block cases of tests/test_gpu_matcher_f64.py.  which = "a": query rows with MATCH_COUNTS_X live patches, template rows with
+    MATCH_COUNTS_Y; "b": the two sides exchanged -- every pair (ceil(live_t / 32), ceil(live_s / 32)) in 0..8 x 0..8 is a tile.
+    Features: per object a base of 256 random unit vectors; template n = unit(base + tn[n] r), query b = unit(base[perm_b] + qn[b] r')
+    with |r| ~ 1 and the noise levels spread so that the tile's similarity at a true match runs from ~0.95 to below the 0.5
+    threshold; template patch 200 = patch 7 and query patch 250 = patch 11, bit for bit.  anti: every query close to one direction u
+    and the templates 2, 5, 8 anti-correlated with it (similarities around -0.12, tests/test_gpu_matcher.py: _negative_case), for
+    negative thresholds.  Returns f32 unit features q (B, 256, C), t (O, N, 256, C), masks qm (B, 256), tm (O, N, 256), labels (B,),
+    and their x 32 planes (host split)."""
+    rs = np.random.RandomState(seed + (0 if which == "a" else 1000) + C)
+    qc, tc = (MATCH_COUNTS_X, MATCH_COUNTS_Y) if which == "a" else (MATCH_COUNTS_Y, MATCH_COUNTS_X)
+    qc, tc = qc[:B], tc[:N]
+    labels = np.zeros(B, np.int32) if labels is None else np.asarray(labels, np.int32)
+    base = _unit_rows(rs.standard_normal((O, P, C)))
+    tn, qn = rs.permutation(np.linspace(0.15, 1.1, N)), rs.permutation(np.linspace(0.15, 1.1, B))
+    t = _unit_rows(base[:, None] + tn[None, :, None, None] * rs.standard_normal((O, N, P, C)) / np.sqrt(C))
+    q = np.empty((B, P, C))
+    for b in range(B):
+        q[b] = _unit_rows(base[labels[b], rs.permutation(P)] + qn[b] * rs.standard_normal((P, C)) / np.sqrt(C))
+    if anti:
+        u = _unit_rows(rs.standard_normal(C))
+
+        def around(mean, shape):
+            v = rs.standard_normal(shape + (C,))
+            v = _unit_rows(v - (v @ u)[..., None] * u)
+            return mean * u + np.sqrt(1.0 - mean * mean) * v
+        q = around(0.98, (B, P))
+        for n in (2, 5, 8):
+            if n < N:
+                t[:, n] = around(-0.12, (O, P))
+    q, t = q.astype(np.float32), t.astype(np.float32)
+    t[:, :, MATCH_DUP_TMPL[1]] = t[:, :, MATCH_DUP_TMPL[0]]
+    q[:, MATCH_DUP_QUERY[1]] = q[:, MATCH_DUP_QUERY[0]]
+    qm = match_live_masks(qc, seed + 1, frac_row=MATCH_FRAC_ROWS[0], keep=MATCH_DUP_QUERY)
+    tm = np.stack([match_live_masks(tc, seed + 2 + o, frac_row=MATCH_FRAC_ROWS[1], keep=MATCH_DUP_TMPL) for o in range(O)])
+    case = dict(q=q, t=t, qm=qm, tm=tm, labels=labels, B=B, N=N, O=O, C=C)
+    case["q_hi"], case["q_lo"] = split_planes_host(torch.from_numpy(q), MATCH_SCALE)
+    case["b_hi"], case["b_lo"] = split_planes_host(torch.from_numpy(t), MATCH_SCALE)
+    return case
+
+
+def match_case_layouts(qm, tm, labels):
+    """{(ceil(live_t / 32), ceil(live_s / 32))} over all tiles (b, n)."""
+    lt = (np.asarray(qm) != 0).sum(-1)
+    ls = (np.asarray(tm) != 0).sum(-1)
+    return {(int(-(-lt[b] // 32)), int(-(-ls[labels[b], n] // 32))) for b in range(lt.shape[0]) for n in range(ls.shape[1])}
+
+
+def match_value_coeff(q_hi, q_lo, b_hi, b_lo, labels, scale=MATCH_SCALE, tiles=None):
+    """The value-error coefficient c of a case: 2 x the largest |e| / mag of torch's own float32 evaluation of the products the kernel
+    forms -- hi hi + hi lo + lo hi (hi hi + lo hi for a one-plane bank; one f32 product for f32 features, q_lo = None) scaled by
+    1 / scale^2 -- against the float64 product of the full values, mag = |q| |b|^T, over the tiles (b, n) given (default all).  The
+    factor 2 covers another summation order.  Never derived from the kernel's output."""
+    labels = np.asarray(labels)
+    if tiles is None:
+        tiles = [(b, n) for b in range(q_hi.shape[0]) for n in range(b_hi.shape[1])]
+    inv = 1.0 / (scale * scale)
+    worst = 0.0
+    for b, n in tiles:
+        o = int(labels[b])
+        qh, bh = torch.as_tensor(q_hi[b]).cpu().float(), torch.as_tensor(b_hi[o, n]).cpu().float()
+        ql = None if q_lo is None else torch.as_tensor(q_lo[b]).cpu().float()
+        bl = None if b_lo is None else torch.as_tensor(b_lo[o, n]).cpu().float()
+        s32 = qh @ bh.t()
+        if bl is not None:
+            s32 = s32 + qh @ bl.t()
+        if ql is not None:
+            s32 = s32 + ql @ bh.t()
+        s32 = s32 * torch.tensor(inv, dtype=torch.float32)
+        q64 = qh.double() + (0.0 if ql is None else ql.double())
+        b64 = bh.double() + (0.0 if bl is None else bl.double())
+        s64 = (q64 @ b64.t()) * inv
+        mag = (q64.abs() @ b64.abs().t()) * inv
+        worst = max(worst, float(((s32.double() - s64).abs() / mag.clamp_min(1e-300)).max()))
+    return 2.0 * worst
+
+
+def _first_of_identical_rows(x):
+    """x (rows, K) -> for every row the index of the first row with the same bits."""
+    x = np.ascontiguousarray(x)
+    keys = x.view(np.uint8).reshape(x.shape[0], -1)
+    first, out = {}, np.empty(x.shape[0], np.int64)
+    for i in range(x.shape[0]):
+        out[i] = first.setdefault(keys[i].tobytes(), i)
+    return out
+
+
+def _two_largest(T, axis):
+    """first argmax, maximum and runner-up value (the maximum of the others) along `axis` of a 2-D array."""
+    T = T if axis == 1 else T.T
+    i = T.argmax(1)
+    v = T[np.arange(T.shape[0]), i]
+    rest = T.copy()
+    rest[np.arange(T.shape[0]), i] = -np.inf
+    return i, v, rest.max(1)
+
+
+def _match_decisions(U, qm, sm, thr, patch_thr, src2tar, drop_rows=None):
+    """One tile in float64.  U (256 t, 256 s): masked, unthresholded similarities.  Returns the reference's records and margins.
+    drop_rows (mutant (c)): query patches whose values the column maxima do not see."""
+    T = np.where(U < thr, 0.0, U)
+    ri, rv, r2 = _two_largest(T, 1)
+    Tc = T if drop_rows is None else np.where(drop_rows[:, None], -np.inf, T)
+    ci, cv, c2 = _two_largest(Tc, 0)
+    if drop_rows is not None:
+        empty = ~np.isfinite(cv)
+        cv, ci = np.where(empty, 0.0, cv), np.where(empty, 0, ci)
+    ia, va, ib, vb = (ci, cv, ri, rv) if src2tar else (ri, rv, ci, cv)
+    p = np.arange(P)
+    js = ia
+    ok = va >= thr
+    if patch_thr > 0:
+        t2 = ib[js]
+        dist = np.sqrt(((t2 % G) - (p % G)).astype(np.float64) ** 2 + ((t2 // G) - (p // G)).astype(np.float64) ** 2)
+        ok = ok & (dist <= patch_thr) & (vb[js] >= thr)
+    nz = (qm.astype(np.float32) * sm.astype(np.float32)[js]) * (ib != 0).astype(np.float32) * (js != 0).astype(np.float32)
+    mask = ok.astype(np.float32) * nz
+    contrib = va * mask.astype(np.float64)
+    avg = contrib.sum() / 256.0 if mask.sum() > 0 else 0.0
+    return dict(idx=js, score=va, mask=mask, sim_avg=avg, row_i=ri, row_v=rv, row_2=r2, col_i=ci, col_v=cv, col_2=c2)
+
+
+def match_tiles_f64(q_hi, q_lo, b_hi, b_lo, qmask, bmask, labels, thr, patch_thr, direction, scale=MATCH_SCALE, tiles=None,
+                    _drop=None):
+    """The reference matcher (matching.py:233-278, find_consistency_patches :80-113) in float64 on the values the kernel reads.
+    q_hi / q_lo (B, 256, C), b_hi / b_lo (O, N, 256, C) planes (lo may be None: value = hi / scale), qmask (B, 256), bmask (O, N, 256),
+    labels (B,) 0-based, direction "tar2src" | "src2tar"; tiles: the (b, n) to evaluate (default all, b-major).
+    value = (hi + lo) / scale; sim = q b^T; sim *= both patch masks (fractional values multiply, :234-235); sim[sim < thr] = 0 (:236);
+    row / column maxima, the first maximum wins (:240-241); src2tar exchanges the two (:242-244); mask_sim (:246), the cycle check
+    with dist <= patch_thr (:249-255, skipped for patch_thr <= 0, :256-257), `idx_b != 0` read at POSITION p, `idx_a != 0`, the mask
+    product (:258-266); sim_avg = sum(score * mask) / 256, 0 when no mask is set (:267-271).  Rows of a plane pair that are
+    bit-identical give bit-identical similarities here too (the float64 product is formed once per distinct row).
+    Returns a dict of arrays over the T tiles: idx, score, mask (f32 exactly as the f32 product of the mask values), sim_avg; U and
+    mag (T, 256, 256) [t][s] = the masked unthresholded similarity and |q| |b|^T x |masks|; per row / column the first argmax, maximum
+    and runner-up; row_margin / col_margin (best - runner-up), row_thr / col_thr (distance of the largest unthresholded value
+    both masks keep from thr; inf where there is none); mag_at (T, 256) = mag at the chosen entries."""
+    as64 = lambda x: None if x is None else torch.as_tensor(x).double().numpy()
+    qh, ql, bh, bl = as64(q_hi), as64(q_lo), as64(b_hi), as64(b_lo)
+    qv = (qh if ql is None else qh + ql) / scale
+    bv = (bh if bl is None else bh + bl) / scale
+    qmask, bmask, labels = np.asarray(qmask, np.float32), np.asarray(bmask, np.float32), np.asarray(labels)
+    B, N = qv.shape[0], bv.shape[1]
+    if tiles is None:
+        tiles = [(b, n) for b in range(B) for n in range(N)]
+    tiles = np.asarray(tiles, np.int64).reshape(-1, 2)
+    src2tar = direction == "src2tar"
+    assert direction in ("tar2src", "src2tar")
+    keys = ["idx", "score", "mask", "sim_avg", "row_i", "row_v", "row_2", "col_i", "col_v", "col_2"]
+    out = {k: [] for k in keys + ["U", "mag"]}
+    for b, n in tiles:
+        o = int(labels[b])
+        q, t = qv[b], bv[o, n]
+        fq, ft = _first_of_identical_rows(q), _first_of_identical_rows(t)
+        S = (q @ t.T)[fq][:, ft]
+        mm = qmask[b].astype(np.float64)[:, None] * bmask[o, n].astype(np.float64)[None, :]
+        U = S * mm
+        drop = None
+        if _drop is not None:
+            drop = _drop(qmask[b], bmask[o, n])
+        d = _match_decisions(U, qmask[b], bmask[o, n], thr, patch_thr, src2tar, drop)
+        for k in keys:
+            out[k].append(d[k])
+        out["U"].append(U)
+        out["mag"].append((np.abs(q) @ np.abs(t).T) * np.abs(mm))
+    out = {k: np.stack(v) if np.ndim(v[0]) else np.asarray(v) for k, v in out.items()}
+    out["row_margin"], out["col_margin"] = out["row_v"] - out["row_2"], out["col_v"] - out["col_2"]
+    live = np.where(out["mag"] > 0, out["U"], -np.inf)            # the entries both masks keep (a masked-out entry is an exact 0, no decision)
+    out["row_live_max"], out["col_live_max"] = live.max(2), live.max(1)
+    out["row_thr"], out["col_thr"] = np.abs(out["row_live_max"] - thr), np.abs(out["col_live_max"] - thr)
+    ar = np.arange(P)
+    ii = out["idx"]
+    out["mag_at"] = np.stack([(m.T if src2tar else m)[ar, i] for m, i in zip(out["mag"], ii)])
+    out.update(tiles=tiles, thr=float(thr), patch_thr=float(patch_thr), direction=direction, qm=qmask[tiles[:, 0]],
+               sm=bmask[labels[tiles[:, 0]], tiles[:, 1]])
+    return out
+
+
+def match_ref_as_ours(ref, B, N):
+    """The float64 records as a kernel would return them: idx u8, score / mask f32 (B, N, 256), sim_avg f32 (B, N)."""
+    assert ref["tiles"].shape[0] == B * N
+    return dict(idx=ref["idx"].reshape(B, N, P).astype(np.uint8), score=ref["score"].reshape(B, N, P).astype(np.float32),
+                mask=ref["mask"].reshape(B, N, P).astype(np.float32), sim_avg=ref["sim_avg"].reshape(B, N).astype(np.float32))
+
+
+def match_near_margin_share(ref, near=MATCH_NEAR):
+    """Share of the row and column decisions of `ref` that sit within `near` of a margin: a runner-up (exact ties -- planted copies and
+    all-zero rows -- excepted: they are decided by the index rule, not by a value) or the threshold."""
+    close = 0
+    total = 0
+    for side in ("row", "col"):
+        m, d = ref[side + "_margin"], ref[side + "_thr"]
+        close += int((((m > 0) & (m <= near)) | (d <= near)).sum())
+        total += m.size
+    return close / max(total, 1)
+
+
+class _Lazy:
+    """A failure text that is formatted only when a failure is reported."""
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __radd__(self, other):
+        return other + self.fn()
+
+    def __add__(self, other):
+        return self.fn() + other
+
+
+def match_tiles_check(ours, ref, c):
+    """ours: idx, score, mask (B, N, 256), sim_avg (B, N) (numpy) of the kernel; ref: match_tiles_f64's dict (its tiles are the ones
+    checked); c: the value-error coefficient (match_value_coeff): the kernel's similarity may be off by c mag, so two values within
+    eps = 2 c mag of each other may be ordered either way.  Per (b, n, p):
+      * the index is the float64 first argmax of its row (column for src2tar); or its float64 value lies within eps of that maximum
+        (EXCUSED); or the decision sits within eps of the threshold and the kernel returned (0, 0) / a value that close to the
+        largest (EXCUSED).  An exact float64 tie -- planted copies, all-zero rows -- is never excused: the lower index must come back;
+      * the score lies within c mag + 2^-23 |v| of the float64 value at the returned index (or is the exact 0 of a zeroed entry if
+        that value is within the same distance of the threshold);
+      * a row whose float64 maximum is more than eps below thr returns index 0 and score 0 exactly;
+      * mask_all equals the float64 mask, unless a decision it depends on -- the row at p, the column at the matched index, the column
+        at p, each against its runner-up and against the threshold -- is within eps of its margin (EXCUSED; exact ties are not);
+      * sim_avg equals the float64 sum of the kernel's OWN score * mask / 256 to 256 * 2^-24 relative, and is exactly 0 when no mask is set.
+    Returns dict(checked, excused, failed, max_ratio = max |score err| / bound, first = a readable first failure or None)."""
+    tiles, thr, src2tar = ref["tiles"], ref["thr"], ref["direction"] == "src2tar"
+    ar = np.arange(P)
+    checked = excused = failed = 0
+    max_ratio, first = 0.0, None
+
+    def fail(msg):
+        nonlocal failed, first
+        failed += 1
+        if first is None:
+            first = msg
+    for k, (b, n) in enumerate(tiles):
+        U = ref["U"][k].T if src2tar else ref["U"][k]            # rows = the positions p of side A, columns = the matched index
+        mag = ref["mag"][k].T if src2tar else ref["mag"][k]
+        T = np.where(U < thr, 0.0, U)
+        a_i, a_v, a_2 = (ref["col_i"][k], ref["col_v"][k], ref["col_2"][k]) if src2tar else (ref["row_i"][k], ref["row_v"][k], ref["row_2"][k])
+        a_m, a_t = (ref["col_margin"][k], ref["col_thr"][k]) if src2tar else (ref["row_margin"][k], ref["row_thr"][k])
+        b_m, b_t = (ref["row_margin"][k], ref["row_thr"][k]) if src2tar else (ref["col_margin"][k], ref["col_thr"][k])
+        j = ours["idx"][b, n].astype(np.int64)
+        sc = ours["score"][b, n].astype(np.float64)
+        mk = ours["mask"][b, n]
+        umax = U.max(1)
+        lmax = ref["col_live_max"][k] if src2tar else ref["row_live_max"][k]
+        mag_row = mag.max(1)
+        eps_row = 2.0 * c * np.maximum(mag_row, 1e-300)
+        idx_state = np.zeros(P, np.int8)       # 0 equal, 1 excused, 2 failed
+        for p in ar:
+            checked += 1
+            jj, best = int(j[p]), int(a_i[p])
+            eps = 2.0 * c * max(mag[p, jj], mag[p, best])
+            where = _Lazy(lambda: f"det {b} template {n} patch {p}: ours idx {jj} score {sc[p]:.9g}; float64 best {best} ({a_v[p]:.12g}) "
+                          f"runner-up {a_2[p]:.12g} margin {a_m[p]:.3g}, max - thr {umax[p] - thr:.3g}, eps {eps:.3g}")
+            # the score at the returned index
+            tol = c * mag[p, jj] + 2.0 ** -23 * abs(U[p, jj])
+            err = abs(sc[p] - T[p, jj])
+            if tol > 0:
+                max_ratio = max(max_ratio, err / tol)
+            near_thr_here = abs(U[p, jj] - thr) <= tol
+            score_ok = err <= tol or (near_thr_here and (sc[p] == 0.0 or abs(sc[p] - U[p, jj]) <= tol))
+            if not score_ok:
+                fail("score: " + where + f"; float64 value at ours {T[p, jj]:.12g}, |err| {err:.3g} > bound {tol:.3g}")
+                idx_state[p] = 2
+                continue
+            if umax[p] < thr - eps_row[p] and (jj != 0 or sc[p] != 0.0):
+                fail("a row below the threshold must return (0, 0): " + where)
+                idx_state[p] = 2
+                continue
+            if jj == best and (sc[p] != 0.0) == (a_v[p] != 0.0):
+                continue
+            tj = U[p, jj] if sc[p] != 0.0 else 0.0                  # the float64 value of what the kernel says it found
+            d = a_v[p] - tj
+            on_thr = abs(lmax[p] - thr) <= eps_row[p] and ((jj == 0 and sc[p] == 0.0) or U[p, jj] >= lmax[p] - eps)
+            if jj != best and d == 0.0:
+                fail("exact tie resolved to the higher index: " + where)
+                idx_state[p] = 2
+            elif (jj == best) or (0.0 < d <= eps) or on_thr:
+                if jj != best or on_thr or abs(U[p, jj] - thr) <= eps:
+                    excused += 1
+                    idx_state[p] = 1
+                else:
+                    fail("score zeroed / kept against the threshold: " + where)
+                    idx_state[p] = 2
+            else:
+                fail("index: " + where)
+                idx_state[p] = 2
+        # mask_all
+        want = ref["mask"][k]
+        diff = np.flatnonzero(mk != want)
+        for p in diff:
+            if idx_state[p] == 2:
+                continue                 # already counted
+            cols = {int(j[p]), int(ref["idx"][k][p]), int(p)}
+            eb = 2.0 * c * max(mag_row[p], max(mag[:, s].max() for s in cols), 1e-300)
+            near = (0.0 < a_m[p] <= eb) or a_t[p] <= eb or any((0.0 < b_m[s] <= eb) or b_t[s] <= eb for s in cols)
+            if near:
+                if idx_state[p] == 0:
+                    excused += 1
+            else:
+                fail(f"mask: det {b} template {n} patch {p}: ours {mk[p]:.6g} float64 {want[p]:.6g}; ours idx {int(j[p])} float64 idx "
+                     f"{int(ref['idx'][k][p])}; row margin {a_m[p]:.3g} / thr {a_t[p]:.3g}; column margins "
+                     + ", ".join(f"[{s}] {b_m[s]:.3g} / thr {b_t[s]:.3g}" for s in sorted(cols)) + f"; eps {eb:.3g}")
+        # sim_avg: the reduction alone, on the kernel's own records
+        terms = sc * mk.astype(np.float64)
+        want_avg = terms.sum() / 256.0 if mk.sum() > 0 else 0.0
+        got = float(ours["sim_avg"][b, n])
+        checked += 1
+        if (mk.sum() == 0 and got != 0.0) or abs(got - want_avg) > 256.0 * 2.0 ** -24 * np.abs(terms).sum() / 256.0 + 1e-45:
+            fail(f"sim_avg: det {b} template {n}: ours {got:.9g}, float64 sum of ours score * mask / 256 = {want_avg:.12g} "
+                 f"({int((mk != 0).sum())} masks set)")
+    return dict(checked=checked, excused=excused, failed=failed, max_ratio=max_ratio, first=first)
+
+
+MATCH_MUTANTS = ("tie_higher", "zero_row_first_live", "colmax_drops_a_row_group", "last_band_transposed", "wrong_direction",
+                 "avg_by_count", "score_offset")
+
+
+def match_mutant(kind, case, ref, thr=0.5, patch_thr=3.0, direction="tar2src"):
+    """Subtly wrong matcher results derived from the float64 ones -- each a bug match_tiles_split_kernel could have; the checker must
+    reject every one (tests/test_stage_refs.py).  case: match_blocks_case's dict, ref: match_tiles_f64 of it over all tiles."""
+    B, N = case["B"], case["N"]
+    ours = match_ref_as_ours(ref, B, N)
+    if kind == "tie_higher":                   # (a) a planted tie resolved to the higher index
+        lo_, hi_ = MATCH_DUP_TMPL
+        tm = case["tm"][case["labels"]]                                               # (B, N, 256)
+        tied = (ours["idx"] == lo_) & (ours["score"] != 0) & (tm[:, :, lo_] == tm[:, :, hi_])[:, :, None]
+        assert tied.any()
+        ours["idx"][tied] = hi_
+    elif kind == "zero_row_first_live":        # (b) "maximum 0 means index 0" dropped: an all-zero row returns the first live patch
+        tm = case["tm"][case["labels"]]
+        first_live = np.where((tm != 0).any(-1), (tm != 0).argmax(-1), 0)              # (B, N)
+        zero = ours["score"] == 0
+        ours["idx"] = np.where(zero, first_live[:, :, None], ours["idx"]).astype(np.uint8)
+    elif kind == "colmax_drops_a_row_group":   # (c) the column maxima miss the first row group (compacted rows 0..63), tiles with nrb >= 6
+        def drop(qm, sm):
+            live = np.flatnonzero(qm != 0)
+            d = np.zeros(P, bool)
+            if -(-live.size // 32) >= 6:
+                d[live[:64]] = True
+            return d
+        bad = match_tiles_f64(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["qm"], case["tm"], case["labels"], thr, patch_thr,
+                              direction, _drop=drop)
+        ours = match_ref_as_ours(bad, B, N)
+    elif kind == "last_band_transposed":       # (d) tile (b, n) of the ragged last band of 8 crops computed as tile (n, b)
+        good = match_ref_as_ours(ref, B, N)
+        for b in range(8 * ((B - 1) // 8), B):
+            for n in range(min(N, B)):
+                for k in ours:
+                    ours[k][b, n] = good[k][n, b]
+    elif kind == "wrong_direction":            # (e) the other search direction
+        other = "src2tar" if direction == "tar2src" else "tar2src"
+        bad = match_tiles_f64(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["qm"], case["tm"], case["labels"], thr, patch_thr, other)
+        ours = match_ref_as_ours(bad, B, N)
+    elif kind == "avg_by_count":               # (f) sim_avg = the mean over the valid patches instead of sum / 256
+        cnt = (ours["mask"] != 0).sum(-1)
+        ours["sim_avg"] = np.where(cnt > 0, ours["sim_avg"] * 256.0 / np.maximum(cnt, 1), 0.0).astype(np.float32)
+    elif kind == "score_offset":               # (g) scores off by 8e-6
+        ours["score"] = np.where(ours["score"] != 0, ours["score"] + np.float32(8e-6), ours["score"]).astype(np.float32)
+    else:
+        raise ValueError(kind)
+    return ours
+
+
+# name -> (which, C, sim_threshold, patch_threshold, direction, two-plane bank, objects, anti-correlated, more than this many valid
+# correspondences): the cases of tests/test_gpu_matcher_f64.py; tests/test_stage_refs.py asserts their preconditions on the CPU
+MATCH_CASES = {
+    "blocks_a": ("a", 64, 0.5, 3.0, "tar2src", True, 1, False, 600),
+    "blocks_b": ("b", 64, 0.5, 3.0, "tar2src", True, 1, False, 600),
+    "blocks_a_c1024": ("a", 1024, 0.5, 3.0, "tar2src", True, 1, False, 600),
+    "blocks_a_c32": ("a", 32, 0.5, 3.0, "tar2src", True, 1, False, 600),
+    "blocks_a_c96": ("a", 96, 0.5, 3.0, "tar2src", True, 1, False, 600),
+    "src2tar": ("a", 64, 0.5, 3.0, "src2tar", True, 1, False, 600),
+    "no_cycle_check": ("a", 64, 0.5, 0.0, "tar2src", True, 1, False, 600),
+    "thr_zero": ("a", 64, 0.0, 3.0, "tar2src", True, 1, False, 600),
+    "thr_negative": ("a", 64, -0.25, 3.0, "tar2src", True, 1, True, 100),
+    "one_plane_bank": ("a", 64, 0.5, 3.0, "tar2src", False, 1, False, 600),
+    "three_objects": ("a", 64, 0.5, 3.0, "tar2src", True, 3, False, 600),
+}
+_match_cache = {}
+
+
+def match_case(name):
+    """-> (case, ref, c) of MATCH_CASES[name], computed once per process and shared (treat as read-only): the inputs, the float64
+    records of every tile and the value coefficient."""
+    if name not in _match_cache:
+        which, C, thr, pthr, direction, two_plane, O, anti, _ = MATCH_CASES[name]
+        case = match_blocks_case(which, C, O=O, labels=MATCH_O3_LABELS if O == 3 else None, anti=anti)
+        if not two_plane:
+            case["b_lo"] = None
+        case.update(thr=thr, patch_thr=pthr, direction=direction)
+        ref = match_tiles_f64(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["qm"], case["tm"], case["labels"], thr, pthr, direction)
+        c = match_value_coeff(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["labels"])
+        _match_cache[name] = (case, ref, c)
+    return _match_cache[name]

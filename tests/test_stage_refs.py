@@ -296,3 +296,144 @@ def test_attention_preconditions_reject_another_class():
 def test_attention_bound_is_the_stage_bound_for_plain_inputs():
     assert sr.attention_bound(9.0e-7, 8.0) == 2e-6 + 2.0 ** -21 and sr.attention_bound(9.0e-7, 0.5) == 4e-6 + 2.0 ** -21
     assert sr.attention_bound(7.2e-5, 8.0) == 1.44e-4 + 2.0 ** -21
+
+
+# ---------------------------------------------------------------------------------------------------------------- the split matcher
+def _as_ours(name):
+    case, ref, c = sr.match_case(name)
+    return case, ref, c, sr.match_ref_as_ours(ref, case["B"], case["N"])
+
+
+def test_match_tiles_f64_is_the_reference_formula_in_torch_float64():
+    """The restatement against an independent one written with torch operators the way matching.py:233-278 does (masks multiply, threshold,
+    torch.max first maximum, gather, cycle distance), on one tile with fractional masks, in both directions."""
+    case, ref, _ = sr.match_case("blocks_a")
+    b, n = 5, 6                                         # the two fractional rows
+    q = (case["q_hi"][b].double() + case["q_lo"][b].double()) / 32.0
+    t = (case["b_hi"][0, n].double() + case["b_lo"][0, n].double()) / 32.0
+    qm, tm = torch.from_numpy(case["qm"][b]).double(), torch.from_numpy(case["tm"][0, n]).double()
+    assert 0 < qm[qm > 0].min() < 1 and 0 < tm[tm > 0].min() < 1
+    for direction in ("tar2src", "src2tar"):
+        sim = (q @ t.t()) * tm[None, :] * qm[:, None]
+        sim[sim < 0.3] = 0
+        s_row, i_row = torch.max(sim, dim=1)
+        s_col, i_col = torch.max(sim, dim=0)
+        (sa, ia, sb, ib) = (s_row, i_row, s_col, i_col) if direction == "tar2src" else (s_col, i_col, s_row, i_row)
+        p = torch.arange(256)
+        back = ib[ia]
+        dist = torch.sqrt(((back % 16 - p % 16) ** 2 + (back // 16 - p // 16) ** 2).double())
+        m = (sa >= 0.3) & (dist <= 3.0) & (sb[ia] >= 0.3)
+        mask = m.double() * qm * tm[ia] * (ib != 0).double() * (ia != 0).double()
+        got = sr.match_tiles_f64(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["qm"], case["tm"], case["labels"], 0.3, 3.0,
+                                 direction, tiles=[(b, n)])
+        assert np.array_equal(got["idx"][0], ia.numpy())
+        assert np.abs(got["score"][0] - sa.numpy()).max() < 1e-14
+        assert np.abs(got["mask"][0].astype(np.float64) - mask.numpy()).max() < 1e-7 and (got["mask"][0] != 0).sum() == int((mask != 0).sum()) > 0
+        assert abs(float(got["sim_avg"][0]) - float((sa * mask).sum() / 256.0)) < 1e-9
+
+
+@pytest.mark.parametrize("name", list(sr.MATCH_CASES))
+def test_match_cases_hold_their_preconditions_and_the_checker_accepts_the_reference(name):
+    """Every case of tests/test_gpu_matcher_f64.py, on the CPU: what makes it the case it is named after holds, few decisions sit on a
+    margin (so the cap on excused entries is a condition the reference alone meets by far), and match_tiles_check accepts
+    match_tiles_f64's own records with nothing excused."""
+    case, ref, c, ours = _as_ours(name)
+    which, C, thr, pthr, direction, two_plane, O, anti, min_valid = sr.MATCH_CASES[name]
+    assert (case["b_lo"] is not None) == two_plane and case["q_hi"].shape == (9, 256, C) and case["b_hi"].shape == (O, 9, 256, C)
+    assert sr.planes_well_formed(case["q_hi"], case["q_lo"]) and (not two_plane or sr.planes_well_formed(case["b_hi"], case["b_lo"]))
+    assert 2e-7 < c < 3e-6, c                                                  # a few f32 ulp of sum |q||b|
+    valid = int((ref["mask"] != 0).sum())
+    assert valid > min_valid, valid
+    share = sr.match_near_margin_share(ref)
+    assert share < sr.MATCH_EXCUSED_CAP / 10, share
+    # live counts per row, the sentinel patches, the fractional rows
+    qc, tc = (sr.MATCH_COUNTS_X, sr.MATCH_COUNTS_Y) if which == "a" else (sr.MATCH_COUNTS_Y, sr.MATCH_COUNTS_X)
+    assert tuple((case["qm"] != 0).sum(-1)) == qc and all(tuple((case["tm"][o] != 0).sum(-1)) == tc for o in range(O))
+    for m, counts in [(case["qm"], qc)] + [(case["tm"][o], tc) for o in range(O)]:
+        for r, cnt in enumerate(counts):
+            for p in (0, 255):
+                if r % 2 == 1 and cnt >= 2:
+                    assert m[r, p] != 0
+                if r % 2 == 0 and cnt <= 254:
+                    assert m[r, p] == 0
+    fq, ft = sr.MATCH_FRAC_ROWS
+    assert ((case["qm"][fq] > 0) & (case["qm"][fq] < 1)).sum() == qc[fq] and ((case["tm"][0, ft] > 0) & (case["tm"][0, ft] < 1)).sum() == tc[ft]
+    assert set(np.unique(np.delete(case["qm"], fq, 0))) <= {0.0, 1.0}
+    # the planted copies: bit-identical plane rows, live together, in different 32-row blocks of the compacted tile
+    (t0, t1), (q0, q1) = sr.MATCH_DUP_TMPL, sr.MATCH_DUP_QUERY
+    assert torch.equal(case["b_hi"][:, :, t0], case["b_hi"][:, :, t1]) and torch.equal(case["q_hi"][:, q0], case["q_hi"][:, q1])
+    assert torch.equal(case["q_lo"][:, q0], case["q_lo"][:, q1]) and (not two_plane or torch.equal(case["b_lo"][:, :, t0], case["b_lo"][:, :, t1]))
+    def blocks_apart(m, a, b):
+        live = m != 0
+        rank = np.cumsum(live, -1) - 1
+        return (live[:, a] & live[:, b] & (rank[:, a] // 32 != rank[:, b] // 32)).sum()
+    assert blocks_apart(case["tm"][0], t0, t1) >= 4 and blocks_apart(case["qm"], q0, q1) >= 4
+    tie_rows = int(((ref["row_margin"] == 0) & (ref["row_v"] > 0)).sum())
+    tie_cols = int(((ref["col_margin"] == 0) & (ref["col_v"] > 0)).sum())
+    assert (tie_rows >= 5 or anti) and tie_cols >= 5, (tie_rows, tie_cols)    # exact ties between positive values exist on both sides (anti: the copies seldom lead a row)
+    if anti:      # live rows whose maximum is a masked-out patch's exact zero, and live negative maxima where nothing is masked out
+        live_rows = ref["qm"] != 0
+        assert ((ref["score"] == 0) & (ref["idx"] != 0) & live_rows).sum() > 100 and (ref["score"] < 0).sum() > 100
+    if thr == 0.0:
+        assert (ref["U"] < 0).sum() > 10000                                   # negative similarities exist and are zeroed
+    rep = sr.match_tiles_check(ours, ref, c)
+    assert rep["failed"] == 0 and rep["excused"] == 0 and rep["checked"] == 81 * 257, rep
+
+
+def test_match_block_cases_cover_all_81_live_block_layouts():
+    seen = set()
+    for name in ("blocks_a", "blocks_b"):
+        case, _, _ = sr.match_case(name)
+        lay = sr.match_case_layouts(case["qm"], case["tm"], case["labels"])
+        assert len(lay) == 81                                                 # each of the two alone, the other with the sides exchanged
+        seen |= lay
+    assert seen == {(r, c) for r in range(9) for c in range(9)}
+    case, _, _ = sr.match_case("three_objects")
+    assert tuple(case["labels"]) == sr.MATCH_O3_LABELS and not torch.equal(case["b_hi"][0], case["b_hi"][1])
+    assert len(sr.match_case_layouts(case["qm"], case["tm"], case["labels"])) == 81
+
+
+@pytest.mark.parametrize("kind", sr.MATCH_MUTANTS)
+def test_match_checker_rejects_subtly_wrong_matchers(kind):
+    """Seven wrong results derived from the float64 one, each a bug the kernel could have: the checker reports failures for every one and
+    excuses none of them away (the failures are not near any margin)."""
+    case, ref, c = sr.match_case("blocks_a")
+    rep = sr.match_tiles_check(sr.match_mutant(kind, case, ref), ref, c)
+    assert rep["failed"] > 0 and rep["first"], (kind, rep)
+    floor = {"tie_higher": 10, "zero_row_first_live": 1000, "colmax_drops_a_row_group": 100, "last_band_transposed": 100,
+             "wrong_direction": 1000, "avg_by_count": 30, "score_offset": 1000}[kind]
+    assert rep["failed"] >= floor, (kind, rep)
+
+
+def test_match_checker_rejects_column_ties_and_wrong_direction_in_src2tar():
+    """The column side of the tie rule shows in the index output of src2tar: query patch 250 (the copy) returned where 11 must be."""
+    case, ref, c, ours = _as_ours("src2tar")
+    q0, q1 = sr.MATCH_DUP_QUERY
+    tied = (ours["idx"] == q0) & (ours["score"] != 0) & ((case["qm"][:, q0] == case["qm"][:, q1]) & (case["qm"][:, q1] != 0))[:, None, None]
+    assert tied.sum() >= 5
+    ours["idx"][tied] = q1
+    rep = sr.match_tiles_check(ours, ref, c)
+    assert rep["failed"] >= tied.sum() and "exact tie" in rep["first"]
+    rep = sr.match_tiles_check(sr.match_mutant("wrong_direction", case, ref, direction="src2tar"), ref, c)
+    assert rep["failed"] > 1000
+
+
+def test_match_checker_excuses_only_what_sits_on_a_margin():
+    """A flip to the runner-up passes as EXCUSED when the float64 margin is below eps = 2 c mag and fails when it is not; a score
+    zeroed against the threshold likewise."""
+    case, ref, c, ours = _as_ours("blocks_a")
+    k = int(np.argmax((ref["mask"] != 0).sum(-1)))
+    b, n = ref["tiles"][k]
+    p = int(np.flatnonzero(ref["mask"][k] != 0)[0])
+    U = ref["U"][k]
+    second = int(np.argsort(U[p])[-2])
+    margin = U[p, ref["idx"][k][p]] - U[p, second]
+    assert margin > 1e-3
+    ours["idx"][b, n, p], ours["score"][b, n, p] = second, np.float32(U[p, second])
+    bad = sr.match_tiles_check(ours, ref, c)
+    assert bad["failed"] >= 1 and bad["excused"] == 0 and f"det {b} template {n} patch {p}" in bad["first"]
+    wide = sr.match_tiles_check(ours, ref, margin)             # the same flip under a coefficient as large as the margin: on the margin
+    assert wide["excused"] >= 1 and "index" not in (wide["first"] or "")
+    ours = sr.match_ref_as_ours(ref, 9, 9)
+    ours["idx"][b, n, p], ours["score"][b, n, p] = 0, 0.0      # zeroed although the maximum is far above the threshold
+    assert sr.match_tiles_check(ours, ref, c)["failed"] >= 1
