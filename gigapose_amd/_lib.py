@@ -99,8 +99,8 @@ STATUS_BITS = {1: "a stream-K accumulator hand-over of the split GEMM timed out 
                4: "an activation is not finite, or (split numerics) left the range of the f16 planes (|x| >= 8190 at the default plane scale; GigaPose "
                   "re-calibrates the plane scales / falls back to Dinov2ViT.set_split_gemm('128') by itself, a bare ViT call does not)",
                8: "a detection label / template id lies outside the onboarded bank (the reference raises IndexError)",
-               16: "split numerics: an IST activation left the range of the f16 planes (|x| >= 8190) or is not finite -- "
-                   "use numerics 'chain' or ResNet.conv_kernel = '128' for this checkpoint (GigaPose falls back by itself)"}
+               16: "split numerics: an IST activation left the range of the f16 planes (|x| >= 8190; on ResNet.conv_kernel = '128': |x| > 65504) "
+                   "or is not finite -- use ResNet.conv_kernel = '128' for this checkpoint (GigaPose falls back by itself), beyond that numerics 'chain'"}
 SPLIT_RANGE_BITS = 4 | 16
 _status = {}          # device index -> the int32 word on that device
 _registered = set()   # device indices whose word the ACTIVE library has in its per-device table

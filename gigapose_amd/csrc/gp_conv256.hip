@@ -409,9 +409,9 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
                                 v[2] = __builtin_fmaf(cv_sum_planes<0>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[2]);
                                 v[3] = __builtin_fmaf(cv_sum_planes<1>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[3]);
                             }
-                            if (a.relu)
+                            if (a.relu)  // NaN-propagating maximum (v_maximum3_f32): fmaxf would hand the range guard below a 0 for a NaN
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                                for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
                             if (a.of32) {  // (B, Cout, OH, OW): the last layer only
                                 const int b = pix / OHW, rem = pix - b * OHW;
 #pragma unroll
@@ -857,9 +857,9 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
                                 v[2] = __builtin_fmaf(cv_sum_planes<0>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[2]);
                                 v[3] = __builtin_fmaf(cv_sum_planes<1>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[3]);
                             }
-                            if (a.relu)
+                            if (a.relu)  // NaN-propagating maximum (v_maximum3_f32): fmaxf would hand the range guard below a 0 for a NaN
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                                for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
                             if (a.of32) {  // (B, Cout, OH, OW)
                                 const int bb = pix / OHW, rem = pix - bb * OHW;
 #pragma unroll

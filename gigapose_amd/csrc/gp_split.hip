@@ -29,22 +29,27 @@ __device__ __forceinline__ void split1(float x, _Float16& hi, _Float16& lo)
 }
 
 // W^T [K][n] f32 (k-major) -> hi/lo [n][K] f16.  One 32x32 tile per block through LDS (coalesced both ways).
+// A value beyond the largest finite f16, or a non-finite one, would become inf / NaN in the hi plane: raise GP_ST_SPLIT_RANGE_CONV (the
+// IST stem's output goes through here on its way into conv_split_kernel, ist_net.py; no legal weight is that large either).
 __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ Wt, int K, int n, int ldw,
-                                                             _Float16* __restrict__ hi, _Float16* __restrict__ lo)
+                                                             _Float16* __restrict__ hi, _Float16* __restrict__ lo, int* __restrict__ status)
 {
     __shared__ float t[32][33];
     const int k0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
     for (int r = ty; r < 32; r += 8) t[r][tx] = (k0 + r < K && n0 + tx < n) ? Wt[(size_t)(k0 + r) * ldw + n0 + tx] : 0.f;
     __syncthreads();
+    int bad = 0;
     for (int r = ty; r < 32; r += 8) {
         if (n0 + r < n && k0 + tx < K) {
             _Float16 h, l;
             split1(t[tx][r], h, l);
             hi[(size_t)(n0 + r) * K + k0 + tx] = h;
             lo[(size_t)(n0 + r) * K + k0 + tx] = l;
+            bad |= !(fabsf(t[tx][r]) <= kSplitPlaneLimit);  // !(<=): NaN counts
         }
     }
+    if (bad) gp_raise(status, GP_ST_SPLIT_RANGE_CONV);
 }
 
 enum { SEPI_NONE = 0, SEPI_BIAS_I = 1, SEPI_BIAS_I_GELU = 2, SEPI_BIAS_I_SCALE_RES = 3, SEPI_BIAS_J = 4, SEPI_BIAS_I_RELU = 5 };
@@ -339,6 +344,7 @@ struct ConvSplitArgs {
     const _Float16* rhi; const _Float16* rlo;
     _Float16* ohi; _Float16* olo; float* of32;
     int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, relu, K, tiles_co, tiles_pix;
+    int* status;  // GP_ST_SPLIT_RANGE_CONV: an output beyond the largest finite f16 (or a non-finite one) went into the planes
 };
 
 // 8 waves as 4 (co) x 2 (pixels), wave tile 32 x 64 (two MFMA tiles, hh + xx = 64 accumulator registers): <= 128 VGPRs,
@@ -435,6 +441,7 @@ __global__ __launch_bounds__(512, 4) void conv_split_kernel(const ConvSplitArgs 
     }
 
     // epilogue: lane = pixel column, registers = 4 x (4 consecutive output channels)
+    int bad = 0;  // range guard of the plane output: hi = f16(v) is inf beyond 65504 (the f32 NCHW output has no such limit)
 #pragma unroll
     for (int mi = 0; mi < 1; ++mi)
 #pragma unroll
@@ -471,12 +478,14 @@ __global__ __launch_bounds__(512, 4) void conv_split_kernel(const ConvSplitArgs 
                         split1(v[e], h_, l_);
                         oh[e] = h_;
                         ol[e] = l_;
+                        bad |= !(fabsf(v[e]) <= kSplitPlaneLimit);  // !(<=): NaN counts
                     }
                     *reinterpret_cast<f16x4*>(a.ohi + (size_t)pix * a.Cout + co) = oh;
                     *reinterpret_cast<f16x4*>(a.olo + (size_t)pix * a.Cout + co) = ol;
                 }
             }
         }
+    if (bad) gp_raise(a.status, GP_ST_SPLIT_RANGE_CONV);
 }
 
 // internal entry (gp_vit.hip).  act: f32 k-major activations [K][ld_act]; whi/wlo: pre-split weights [n_w][K].
@@ -527,7 +536,7 @@ int gp_split_weights(const float* Wt, int K, int n, int ldw, void* hi, void* lo,
 {
     GP_REQUIRE(Wt && hi && lo && K > 0 && n > 0 && ldw >= n, "gp_split_weights: bad arguments");
     hipLaunchKernelGGL(split_weights_kernel, dim3((n + 31) / 32, (K + 31) / 32), dim3(256), 0, (hipStream_t)stream, Wt, K, n,
-                       ldw, (_Float16*)hi, (_Float16*)lo);
+                       ldw, (_Float16*)hi, (_Float16*)lo, gp_status_buffer());
     GP_CHECK_LAUNCH("gp_split_weights");
     return GP_OK;
 }
@@ -556,6 +565,7 @@ int gp_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* w_hi, c
                "gp_conv2d_nhwc_split: alpha/beta and res_hi/res_lo go together");
     a.tiles_co = (Cout + SBM - 1) / SBM;
     a.tiles_pix = (int)(npix / SBN);
+    a.status = gp_status_buffer();
     GpProfScope prof(GP_PROF_CONV, 2.0 * Cout * (double)npix * a.K, (hipStream_t)stream);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               SLDS_BYTES);

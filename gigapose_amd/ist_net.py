@@ -282,7 +282,7 @@ class ResNet(nn.Module):
                       _lib.ptr(self._conv_scratch), ctypes.c_size_t(need), _lib.stream_ptr())
         elif use256:   # [C][npix] f32 -> [npix][C] planes of 8 x (single-accumulator convention)
             _lib.call("gp_planes_from_cm", _lib.ptr(stem_out), _lib.i(c0), _lib.i(npix), _lib.ptr(cur[0]), _lib.ptr(cur[1]), _lib.stream_ptr())
-        else:        # ... of x with the low half scaled by 2^11 (two-accumulator convention)
+        else:        # ... of x with the low half scaled by 2^11 (two-accumulator convention; |x| > 65504 raises status bit 16)
             _lib.call("gp_split_weights", _lib.ptr(stem_out), _lib.i(c0), _lib.i(npix), _lib.i(npix), _lib.ptr(cur[0]),
                       _lib.ptr(cur[1]), _lib.stream_ptr())
         for (c1, c2, ds), (w1, w2, wd) in zip(pk["blocks"], weights["blocks"]):

@@ -859,3 +859,276 @@ def match_case(name):
         c = match_value_coeff(case["q_hi"], case["q_lo"], case["b_hi"], case["b_lo"], case["labels"])
         _match_cache[name] = (case, ref, c)
     return _match_cache[name]
+
+
+# ---------------------------------------------------------------------------------------------------------------- IST convolutions at the ends of the plane range
+# (tests/test_gpu_ist_range.py.)  Two plane conventions: "planes" = hi = f16(8 x), lo = f16(8 x - hi), value (hi + lo) / 8, legal while
+# |8 x| <= 65504 (gp_conv2d_planes, the default kernels); "wide" = hi = f16(x), lo = f16((x - hi) 2^11), value hi + lo / 2048, legal while
+# |x| <= 65504 (gp_conv2d_nhwc_split, the fallback).
+F16_MAX = 65504.0
+ACT_LIMIT = F16_MAX / 8.0                    # 8188: the largest |x| of the default kernels' planes
+WIDE_LO = 2048.0
+PLANES_FLOOR = (2.0 ** -22, 2.0 ** -28)      # (relative, absolute) term of a plane OUTPUT (hi + lo) / 8: 22 bits of 8 y; the lo plane's f16 subnormal floor, 2^-25 / 8
+WIDE_FLOOR = (2.0 ** -22, 2.0 ** -35)        # hi + lo / 2048: 22 bits; the lo plane's f16 subnormal spacing 2^-24 / 2048
+
+# route -> (Cin, Cout, k, stride, pad, H = W, B): the smallest launches of gp_conv2d_planes that reach each kernel instantiation
+# (Cin % 32 = 0, Cout % 64 = 0, B OH OW % 256 = 0; gp_conv256.hip: conv_halo_usable / conv_halo_launch / gp_conv2d_planes)
+CONV_GUARD_ROUTES = {
+    "gather_ni2": (32, 128, 3, 2, 1, 32, 1),
+    "gather_ni3_1x1": (32, 192, 1, 2, 0, 32, 1),
+    "gather_ni4_two_channel_tiles": (32, 512, 3, 2, 1, 32, 1),
+    "gather_3x3_s1_not_16": (32, 128, 3, 1, 1, 8, 4),
+    "gather_cut_tiles": (256, 512, 3, 2, 1, 32, 4),
+    "halo_cout64": (32, 64, 3, 1, 1, 16, 1),
+    "halo_ni2_serial": (64, 128, 3, 1, 1, 16, 1),
+    "halo_ni2_parallel": (64, 128, 3, 1, 1, 16, 8),
+    "halo_ni3_parallel": (64, 192, 3, 1, 1, 16, 8),
+    "halo_ni4_parallel": (64, 256, 3, 1, 1, 16, 8),
+}
+RES_PLANT_BETA = 150.0                       # see conv_guard_residual_case
+
+
+def conv_out_size(hw, k, stride, pad):
+    return (hw + 2 * pad - k) // stride + 1
+
+
+def split_wide_host(x):
+    """The two-accumulator convention on the host: hi = f16(x), lo = f16((x - hi) * 2048), one IEEE operation per step."""
+    x = torch.as_tensor(x, dtype=torch.float32)
+    hi = x.to(torch.float16)
+    lo = ((x - hi.to(torch.float32)) * torch.tensor(WIDE_LO, dtype=torch.float32)).to(torch.float16)
+    return hi, lo
+
+
+def wide_value(hi, lo):
+    return hi.double() + lo.double() / WIDE_LO
+
+
+def _guard_base(route, seed):
+    cin, cout, k, stride, pad, hw, B = CONV_GUARD_ROUTES[route]
+    rs = np.random.RandomState(seed + cin + cout + 7 * k + hw + B)
+    X = rs.standard_normal((B, hw, hw, cin)).astype(np.float32)
+    Wt = (rs.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
+    oh = conv_out_size(hw, k, stride, pad)
+    return rs, dict(X=X, Wt=Wt, R=None, stride=stride, pad=pad, oh=oh, npix=B * oh * oh, cout=cout, route=route)
+
+
+def conv_guard_zero_channel_case(route, v, seed=0):
+    """Small random inputs and weights, alpha = 1, and ONE output channel `co` (the third from the end: inside the last 4-channel quad
+    of the last channel tile) whose weights are all zero and whose beta is v: that channel's epilogue value is 0 * 1 + v = v exactly
+    at every pixel, 8 v exactly in f32."""
+    rs, case = _guard_base(route, seed)
+    cout = case["cout"]
+    co = cout - 3
+    case["Wt"][co] = 0.0
+    beta = rs.standard_normal(cout).astype(np.float32)
+    beta[co] = v
+    case.update(alpha=np.ones(cout, np.float32), beta=beta, co=co, v=float(v))
+    return case
+
+
+def conv_guard_residual_case(route, where, over, seed=1):
+    """Small random inputs, weights, BatchNorm and residual; ONE output is pushed to about 8300 (over = True: above the limit 8188 by
+    more than 1 %) or about 8000 (clean twin: below it by more than 1 %) through the residual: where = "first" -> pixel 0 / channel 0 (the
+    first row and column of the first tile), "last" -> the last pixel / last valid channel of the last tile.
+    A residual of 8300 itself cannot be written into the x 8 planes (66400 > 65504: the residual's own hi plane would hold inf), so the
+    planted element carries 8150 / 7850 and beta of that channel the other RES_PLANT_BETA = 150: the float64 OUTPUT is 8300 / 8000 plus
+    the convolution's few units, every operand is a legal plane value."""
+    rs, case = _guard_base(route, seed)
+    cout, npix, oh = case["cout"], case["npix"], case["oh"]
+    alpha = rs.uniform(0.5, 1.5, cout).astype(np.float32)
+    beta = rs.standard_normal(cout).astype(np.float32)
+    R = rs.standard_normal((npix, cout)).astype(np.float32)
+    pix, co = (0, 0) if where == "first" else (npix - 1, cout - 1)
+    beta[co] = RES_PLANT_BETA
+    R[pix, co] = (8300.0 if over else 8000.0) - RES_PLANT_BETA
+    case.update(alpha=alpha, beta=beta, R=R.reshape(-1, oh, oh, cout), pix=pix, co=co, over=bool(over))
+    return case
+
+
+def conv_range_case(cin, cout, k, stride, pad, hw, B, seed, top=3.5, limit=ACT_LIMIT, res=True):
+    """Convolution + BatchNorm + residual + ReLU far from unit scale.  NHWC inputs and a residual of per-pixel scale 10^U(-4, top) times
+    U(-1, 1) (top = 3.5: values from 1e-4 to about 3000), weights N(0, 1) / sqrt(K), alpha in [0.5, 1.5], beta N(0, 1) x the median
+    pixel scale; the special values of split_values_case (exact f16 values, ties of the hi rounding, lo-plane subnormals) planted into
+    the channels of one input pixel and -- those up to 4096 -- of one residual pixel.  Inputs, beta and residual (not the planted values)
+    are then multiplied by ONE factor (0.3 .. 3) so that the float64 output peaks near 0.8 of `limit` (ReLU is homogeneous: the output
+    scales with them); tests/test_stage_refs.py asserts the peak of |y| between 0.5 and 0.95 of it on the values the planes hold."""
+    rs = np.random.RandomState(seed)
+    oh = conv_out_size(hw, k, stride, pad)
+    K = cin * k * k
+    sx = 10.0 ** rs.uniform(-4.0, top, (B, hw, hw, 1))
+    X = rs.uniform(-1.0, 1.0, (B, hw, hw, cin)) * sx
+    Wt = (rs.standard_normal((cout, cin, k, k)) / np.sqrt(K)).astype(np.float32)
+    alpha = rs.uniform(0.5, 1.5, cout).astype(np.float32)
+    beta = rs.standard_normal(cout) * np.median(sx)
+    R = rs.uniform(-1.0, 1.0, (B, oh, oh, cout)) * 10.0 ** rs.uniform(-4.0, top, (B, oh, oh, 1)) if res else None
+    special = split_values_case(40, seed)[1:23].astype(np.float64)
+    n = min(len(special), cin)
+    px = (B - 1, hw // 2, hw // 3)
+    pr = (0, oh // 3, oh // 2)
+    rspecial = special[np.abs(special) <= 4096.0][:cout]
+
+    def peak(s):
+        x, r = X * s, (None if R is None else R * s)
+        x[px][:n] = special[:n]
+        if r is not None:
+            r[pr][:len(rspecial)] = rspecial
+        x, b, r = x.astype(np.float32), (beta * s).astype(np.float32), (None if r is None else r.astype(np.float32))
+        y = torch.nn.functional.conv2d(torch.from_numpy(x).double().permute(0, 3, 1, 2), torch.from_numpy(Wt).double(), stride=stride, padding=pad)
+        y = y * torch.from_numpy(alpha).double()[None, :, None, None] + torch.from_numpy(b).double()[None, :, None, None]
+        if r is not None:
+            y = y + torch.from_numpy(r).double().permute(0, 3, 1, 2)
+        return float(torch.relu(y).max()), x, b, r
+
+    s = 1.0
+    for _ in range(3):          # the planted values do not scale: a second and third pass settle the factor
+        p, x, b, r = peak(s)
+        s *= 0.8 * limit / p
+    p, x, b, r = peak(s)
+    return dict(X=x, Wt=Wt, alpha=alpha, beta=b, R=r, stride=stride, pad=pad, oh=oh, npix=B * oh * oh, cout=cout, factor=s, limit=limit,
+                planted_x=px, planted_r=pr, n_special=n)
+
+
+def conv_case_values(case, wide=False):
+    """The float64 values the kernel reads: the host split of the case's f32 arrays (bit for bit the planes gp_split_planes /
+    split_planes make on the device; the GPU tests pass the device's planes instead) -> (x, w, r) float64 tensors, x / r NHWC."""
+    if wide:
+        val = lambda t, _s: wide_value(*split_wide_host(t))                                  # noqa: E731
+    else:
+        val = lambda t, s: planes_value(*split_planes_host(t, s), s)                          # noqa: E731
+    return val(case["X"], 8.0), val(case["Wt"], 64.0), None if case["R"] is None else val(case["R"], 8.0)
+
+
+def conv_range_reference(x, w, alpha, beta, r, stride, pad, relu=True):
+    """float64 reference and per-output bound coefficient of conv + BN + residual + ReLU on the values given (x (B, H, W, Cin), w (Cout,
+    Cin, k, k), r (B, OH, OW, Cout) or None: float64, what the planes hold) -> dict of (B, Cout, OH, OW) float64 tensors
+      y    the float64 result,
+      mag  conv(|x|, |w|) |alpha| + |beta| + |r|, the magnitude every rounding error of an evaluation scales with,
+      y32  torch's own float32 evaluation of the same expression (operands converted exactly: plane values fit 24 bits),
+    and c = 2 x max |y32 - y| / mag (match_value_coeff's method; the factor 2 covers another summation order).  Nothing here comes from
+    the kernel under test."""
+    F = torch.nn.functional
+    a, b = torch.as_tensor(alpha).double()[None, :, None, None], torch.as_tensor(beta).double()[None, :, None, None]
+    xc, rc = x.permute(0, 3, 1, 2), (None if r is None else r.permute(0, 3, 1, 2))
+    y = F.conv2d(xc, w, stride=stride, padding=pad) * a + b
+    mag = F.conv2d(xc.abs(), w.abs(), stride=stride, padding=pad) * a.abs() + b.abs()
+    y32 = F.conv2d(xc.float(), w.float(), stride=stride, padding=pad) * a.float() + b.float()
+    if rc is not None:
+        y, mag, y32 = y + rc, mag + rc.abs(), y32 + rc.float()
+    if relu:
+        y, y32 = torch.relu(y), torch.relu(y32)
+    ratio = (y32.double() - y).abs() / mag.clamp_min(1e-300)
+    ok = torch.isfinite(ratio)
+    return dict(y=y, mag=mag, y32=y32.double(), c=2.0 * float(ratio[ok].max()))
+
+
+def conv_bound(ref, floor=None):
+    """c mag + floor per output; floor = (relative, absolute) of the output's plane format, None for the f32 output."""
+    bound = ref["c"] * ref["mag"]
+    if floor is not None:
+        bound = bound + floor[0] * ref["y"].abs() + floor[1]
+    return bound
+
+
+def conv_bound_worst(got, ref, floor=None, where=None):
+    """-> (worst err / bound, its index) over the outputs selected by `where` (default: all).  A non-finite `got` counts as inf."""
+    err = (got - ref["y"]).abs()
+    err = torch.where(torch.isfinite(got), err, torch.full_like(err, float("inf")))
+    q = err / conv_bound(ref, floor)
+    if where is not None:
+        q = torch.where(where, q, torch.zeros_like(q))
+    i = int(q.argmax())
+    return float(q.flatten()[i]), tuple(int(v) for v in np.unravel_index(i, q.shape))
+
+
+CONV_MUTANTS = ("lo_planes_dropped", "residual_hi_only", "small_outputs_flushed")
+
+
+def conv_mutant(kind, case, wide=False):
+    """Three subtly wrong results, derived from float64 (no other error): the activations' lo planes dropped, the residual added as its
+    hi plane only, outputs below 2^-10 max |y| flushed to zero.  (B, Cout, OH, OW) float64."""
+    x, w, r = conv_case_values(case, wide)
+    if kind == "lo_planes_dropped":
+        hi = split_wide_host(case["X"])[0].double() if wide else split_planes_host(case["X"], 8.0)[0].double() / 8.0
+        return conv_range_reference(hi, w, case["alpha"], case["beta"], r, case["stride"], case["pad"])["y"]
+    if kind == "residual_hi_only":
+        hi = split_wide_host(case["R"])[0].double() if wide else split_planes_host(case["R"], 8.0)[0].double() / 8.0
+        return conv_range_reference(x, w, case["alpha"], case["beta"], hi, case["stride"], case["pad"])["y"]
+    if kind == "small_outputs_flushed":
+        y = conv_range_reference(x, w, case["alpha"], case["beta"], r, case["stride"], case["pad"])["y"]
+        return torch.where(y.abs() < 2.0 ** -10 * y.abs().max(), torch.zeros_like(y), y)
+    raise ValueError(kind)
+
+
+# part B's runs: name -> (route or shape, top exponent, wide); shapes (Cin, Cout, k, stride, pad, H = W, B)
+CONV_RANGE_CASES = {
+    "gather_ni2": (CONV_GUARD_ROUTES["gather_ni2"], 3.5, False),
+    "gather_ni3_1x1": (CONV_GUARD_ROUTES["gather_ni3_1x1"], 3.5, False),
+    "halo_ni2_serial": (CONV_GUARD_ROUTES["halo_ni2_serial"], 3.5, False),
+    "halo_ni4_parallel": (CONV_GUARD_ROUTES["halo_ni4_parallel"], 3.5, False),
+    "wide_3x3_s1": ((32, 64, 3, 1, 1, 16, 2), 4.4, True),
+    "wide_1x1_s2": ((64, 192, 1, 2, 0, 16, 2), 4.4, True),
+}
+_conv_range_cache = {}
+
+
+def conv_range_named(name):
+    """-> the case of CONV_RANGE_CASES[name], built once per process (treat as read-only)."""
+    if name not in _conv_range_cache:
+        shape, top, wide = CONV_RANGE_CASES[name]
+        _conv_range_cache[name] = conv_range_case(*shape, seed=1000 + len(name) + shape[1], top=top, limit=F16_MAX if wide else ACT_LIMIT)
+    return _conv_range_cache[name]
+
+
+def resize_guard_image(over, IH=24, IW=40, seed=5):
+    """(2, 3, IH, IW) f32 noise whose first pixel of crop 1 / channel 2 is 8300 (over) or 8100: align_corners maps a corner onto itself
+    (source coordinate 0, interpolation weights exactly 1 and 0), so the bilinear resize peaks at exactly that value in any precision."""
+    x = torch.randn(2, 3, IH, IW, generator=torch.Generator().manual_seed(seed))
+    x[1, 2, 0, 0] = 8300.0 if over else 8100.0
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------- the IST ResNet, layer by layer
+def resnet_layer_maxima(backbone, x):
+    """The float64 / float32 torch forward of oracle/ist_torch.py (whatever dtype `backbone` and `x` hold) with the largest |value| of every
+    tensor on the way -> (rec, written, features):
+      rec      {name: max |.|} of the resized input, every Conv2d and BatchNorm2d output (forward hooks), the stem's and every block's output;
+      written  the subset the split path stores as f16 PLANES -- the resized input, relu(bn1(.)) of the stem and of every block (the maximum
+               of the positive part: ReLU runs before the store), the downsample shortcut's BatchNorm output, every block's output.  Convolution
+               outputs before BatchNorm and bn2 before the residual live in f32 accumulators only; the head's output is f32;
+      features the (b, D, 16, 16) output."""
+    from oracle import ist_torch
+
+    F = torch.nn.functional
+    rec, written, hooks = {}, {}, []
+
+    def hook(name):
+        def fn(_mod, _inp, out):
+            rec[name] = max(rec.get(name, 0.0), float(out.abs().max()))
+            if name.endswith("bn1"):
+                written["relu(" + name + ")"] = max(written.get("relu(" + name + ")", 0.0), float(out.max()))
+            elif name.endswith("downsample.1"):
+                written[name] = rec[name]
+        return fn
+
+    for name, m in backbone.named_modules():
+        if isinstance(m, (torch.nn.Conv2d, torch.nn.BatchNorm2d)):
+            hooks.append(m.register_forward_hook(hook(name)))
+    try:
+        with torch.no_grad():
+            y = F.interpolate(x, (backbone.input_size, backbone.input_size), mode="bilinear", align_corners=True)
+            rec["resize"] = written["resize"] = float(y.abs().max())
+            y = F.relu(backbone.bn1(backbone.conv1(y)))
+            for li, stage in enumerate((backbone.layer1, backbone.layer2, backbone.layer3, backbone.layer4), 1):
+                for bi, blk in enumerate(stage):
+                    y = ist_torch.basic_block(blk, y)
+                    rec[f"layer{li}.{bi}.out"] = written[f"layer{li}.{bi}.out"] = float(y.abs().max())
+            feats = backbone.layer4_outconv(y)
+    finally:
+        for h in hooks:
+            h.remove()
+    return rec, written, feats
+
+
+def maxima_line(d):
+    return ", ".join(f"{n} {v:.4g}" for n, v in d.items())

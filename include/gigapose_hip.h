@@ -165,6 +165,8 @@ int gp_gemm_kmajor_sk(const float* A, int lda, const float* B, int ldb, float* D
  *     act_is_b != 0: D[i][j] = sum_k W[i][k] act[k][j];  act_is_b == 0: D[i][j] = sum_k act[k][i] W[j][k].
  *     epilogues as gp_gemm_kmajor.  Requires I, J % 128 == 0, K % 32 == 0. */
 int gp_split_weights(const float* Wt, int K, int n, int ldw, void* hi, void* lo, void* stream);
+/* (Also splits the ACTIVATIONS that feed gp_conv2d_nhwc_split.  A value with |x| > 65504 -- the hi plane would hold inf -- or a non-finite
+ * one raises bit 16 of the status word, GP_STATUS_SPLIT_RANGE_CONV; the planes written are the same either way.) */
 int gp_gemm_split(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
                   int act_is_b, int epilogue, const float* bias, const float* scale, const float* residual, int ldr,
                   void* stream);
@@ -276,7 +278,8 @@ int gp_conv2d_cm(const float* X, const float* Wt, float* Y, const float* alpha, 
  *   alpha/beta (Cout) folded BN or NULL; res_hi/res_lo (B,OH,OW,Cout) or NULL;
  *   output: planes out_hi/out_lo (B,OH,OW,Cout), or -- when out_f32_nchw != NULL -- f32 (B,Cout,OH,OW).
  * Requires Cin % 32 == 0, Cout % 64 == 0, B*OH*OW % 128 == 0.  (A CNHW f32 tensor [C][npix] becomes planes [npix][C]
- * with gp_split_weights(x, C, npix, npix, hi, lo).) */
+ * with gp_split_weights(x, C, npix, npix, hi, lo), which raises the same bit for an input beyond 65504.)  A plane output with |y| > 65504 (inf in the hi plane) or a non-finite one
+ * raises bit 16 of the status word (GP_STATUS_SPLIT_RANGE_CONV); the f32 output has no such limit. */
 int gp_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* alpha,
                          const float* beta, const void* res_hi, const void* res_lo, int B, int H, int W, int Cin, int Cout,
                          int KH, int KW, int stride, int pad, int relu, void* out_hi, void* out_lo, float* out_f32_nchw,

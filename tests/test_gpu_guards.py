@@ -211,11 +211,26 @@ def test_range_trip_falls_back_to_the_wide_kernels_automatically():
     model = _gigapose_with_vit(small_vitl(seed=11))
     model.template_datasets = {"syn": tset}
     model.set_template_data("syn")
+    # (the crop was x 1e5 until the wide IST kernels got a range guard of their own: by the float64 forward that crop puts 1.1e7 into the
+    # ResNet's planes, 170 x beyond the WIDE kernels' 65504 -- the step passed on inf / NaN that nothing reported.  x 1e5 now has to raise:
+    # tests/test_gpu_ist_range.py::test_beyond_the_wide_range_raises_instead_of_returning_garbage.  Here: a scale that float64 puts over the
+    # planes' 8190 and inside the wide range, and the outputs that come from the ResNet must be finite.)
+    from gigapose_testing import stage_refs as sr
+
+    from gigapose_amd.ist_net import ISTNet, Regressor, ResNet
+
+    ist64 = syn.fill_state_dict(ISTNet("resnet", ResNet(dict(factory.IST_CFG)), Regressor(256, 256, True, True), 64), 9).eval().double().backbone   # _gigapose_with_vit's
+    top = {s: max(sr.resnet_layer_maxima(ist64, q["tar_img"][3:4].double() * s)[1].values()) for s in (112.0, 1.0e5)}
+    print(f"crop 3, float64 forward of the ResNet, largest activation written as planes: x 112 -> {top[112.0]:.4g}, x 1e5 -> {top[1.0e5]:.4g}")
+    assert 1.05 * 8190.0 <= top[112.0] <= 0.5 * 65504.0 and top[1.0e5] > 65504.0
     big = {n: (v.numpy().copy() if torch.is_tensor(v) else v) for n, v in q.items()}
-    big["tar_img"][3] *= 1.0e5
+    big["tar_img"][3] *= 112.0
     with pytest.warns(RuntimeWarning, match="falling back"):
         model.eval_retrieval(make_batch(big), 2, "syn")
     _lib.check_status()
+    assert model.ist_net.backbone.conv_kernel == "128"
+    for n in ("relScale", "relInplane", "pred_poses"):
+        assert torch.isfinite(model.last_predictions.tensors[n]).all(), f"{n} is not finite after the IST fallback"
     # not a range problem: NaN pixels trip the guard again after the fallback -> raises
     bad = {n: (v.numpy().copy() if torch.is_tensor(v) else v) for n, v in q.items()}
     bad["tar_img"][2, 0, 50, 50] = float("nan")

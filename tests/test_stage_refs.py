@@ -437,3 +437,114 @@ def test_match_checker_excuses_only_what_sits_on_a_margin():
     ours = sr.match_ref_as_ours(ref, 9, 9)
     ours["idx"][b, n, p], ours["score"][b, n, p] = 0, 0.0      # zeroed although the maximum is far above the threshold
     assert sr.match_tiles_check(ours, ref, c)["failed"] >= 1
+
+
+# ---------------------------------------------------------------------------------------------------------------- IST convolutions at the ends of the range
+def _range_ref(name):
+    case = sr.conv_range_named(name)
+    wide = sr.CONV_RANGE_CASES[name][2]
+    x, w, r = sr.conv_case_values(case, wide)
+    return case, wide, sr.conv_range_reference(x, w, case["alpha"], case["beta"], r, case["stride"], case["pad"])
+
+
+def test_wide_host_split_reconstructs_to_22_bits():
+    x = torch.from_numpy(sr.split_values_case(4096, 3)) * 8.0          # up to 64000
+    hi, lo = sr.split_wide_host(x)
+    assert bool(torch.isfinite(hi.float()).all()) and bool(torch.isfinite(lo.float()).all())
+    err = (sr.wide_value(hi, lo) - x.double()).abs()
+    assert bool((err <= sr.WIDE_FLOOR[0] * x.double().abs() + sr.WIDE_FLOOR[1]).all())
+    assert bool((sr.wide_value(hi, lo).float().double() == sr.wide_value(hi, lo)).all())       # the values fit f32: torch's f32 evaluation reads them exactly
+
+
+@pytest.mark.parametrize("name", list(sr.CONV_RANGE_CASES))
+def test_conv_range_cases_hold_their_preconditions(name):
+    """Values from 1e-4 to the thousands, the planted specials where the builder says, a float64 peak of |format y| between 0.5 and 0.95 of 65504,
+    outputs 1000 times smaller than the largest present, and torch's own f32 evaluation inside the bound with err / bound <= 0.5 by construction."""
+    case, wide, ref = _range_ref(name)
+    X = np.abs(case["X"])
+    assert X[X > 0].min() < 1e-3 and (2000.0 if not wide else 15000.0) < X.max() < case["limit"] and 0.3 < case["factor"] < 3.0
+    special = sr.split_values_case(40, 0)[1:23]                               # the specials do not depend on the seed
+    assert np.array_equal(case["X"][case["planted_x"]][:case["n_special"]], special[:case["n_special"]])
+    assert 1024.0 in case["R"][case["planted_r"]] and 1.0 + 2.0 ** -11 in case["R"][case["planted_r"]]
+    peak = float(ref["y"].abs().max()) * (1.0 if wide else 8.0) / sr.F16_MAX
+    y = ref["y"]
+    small = int(((y > 0) & (y < 1e-3 * y.max())).sum())
+    worst32, _ = sr.conv_bound_worst(ref["y32"], ref, None)
+    print(f"{name}: factor {case['factor']:.3f}, peak {peak:.3f} of 65504, c {ref['c']:.3e}, outputs below 1e-3 max: {small}, torch f32 err / bound {worst32:.3f}")
+    assert 0.5 <= peak <= 0.95 and small >= 10
+    assert worst32 <= 0.5 + 1e-12
+    floor = sr.WIDE_FLOOR if wide else sr.PLANES_FLOOR
+    assert sr.conv_bound_worst(ref["y"], ref, floor)[0] == 0.0
+    # the plane format's own rounding of the float64 result sits inside its floor term
+    yh = ref["y"].float()
+    back = sr.wide_value(*sr.split_wide_host(yh)) if wide else sr.planes_value(*sr.split_planes_host(yh, 8.0), 8.0)
+    assert bool(((back - yh.double()).abs() <= floor[0] * yh.double().abs() + floor[1]).all())
+
+
+@pytest.mark.parametrize("kind", sr.CONV_MUTANTS)
+@pytest.mark.parametrize("name", list(sr.CONV_RANGE_CASES))
+def test_conv_bound_rejects_subtly_wrong_convolutions(name, kind):
+    """Activation lo planes dropped / the residual added as its hi plane only / outputs below 2^-10 max |y| flushed to zero: each derived from
+    the float64 result, each outside the bound (plane floor included) on every case."""
+    case, wide, ref = _range_ref(name)
+    worst, at = sr.conv_bound_worst(sr.conv_mutant(kind, case, wide), ref, sr.WIDE_FLOOR if wide else sr.PLANES_FLOOR)
+    print(f"{name} / {kind}: worst err / bound {worst:.3g} at {at}")
+    assert worst > 2.0
+
+
+def test_conv_bound_counts_a_non_finite_output_as_a_miss():
+    case, wide, ref = _range_ref("gather_ni3_1x1")
+    bad = ref["y"].clone()
+    bad[0, 5, 3, 3] = float("inf")
+    assert sr.conv_bound_worst(bad, ref, sr.PLANES_FLOOR)[0] == float("inf")
+    assert sr.conv_bound_worst(bad, ref, sr.PLANES_FLOOR, where=torch.isfinite(bad))[0] == 0.0
+
+
+@pytest.mark.parametrize("route", list(sr.CONV_GUARD_ROUTES))
+def test_conv_guard_cases_sit_where_they_say(route):
+    """Launch preconditions of gp_conv2d_planes; the zero-weight channel's float64 value is v exactly at every pixel and everything else small;
+    the residual cases' float64 output is beyond 8190 x 1.01 (over) / everything below 8190 x 0.99 (clean), every OPERAND a legal plane value."""
+    cin, cout, k, stride, pad, hw, B = sr.CONV_GUARD_ROUTES[route]
+    assert cin % 32 == 0 and cout % 64 == 0 and (B * sr.conv_out_size(hw, k, stride, pad) ** 2) % 256 == 0
+    for v in (8188.0, 8188.5, -8188.5):
+        case = sr.conv_guard_zero_channel_case(route, v)
+        x, w, _ = sr.conv_case_values(case)
+        y = sr.conv_range_reference(x, w, case["alpha"], case["beta"], None, case["stride"], case["pad"], relu=False)["y"]
+        assert bool((y[:, case["co"]] == v).all())
+        rest = torch.cat([y[:, :case["co"]], y[:, case["co"] + 1:]], dim=1)
+        assert float(rest.abs().max()) < 20.0
+    for where in ("first", "last"):
+        for over in (False, True):
+            case = sr.conv_guard_residual_case(route, where, over)
+            assert (case["pix"], case["co"]) == ((0, 0) if where == "first" else (case["npix"] - 1, cout - 1))
+            assert np.abs(case["R"]).max() * 8.0 < sr.F16_MAX and np.abs(case["X"]).max() < 10.0
+            x, w, r = sr.conv_case_values(case)
+            y = sr.conv_range_reference(x, w, case["alpha"], case["beta"], r, case["stride"], case["pad"])["y"]
+            y = y.permute(0, 2, 3, 1).reshape(case["npix"], cout)
+            at = float(y[case["pix"], case["co"]])
+            y[case["pix"], case["co"]] = 0.0
+            assert float(y.max()) < 0.99 * 8190.0 and (at > 1.01 * 8190.0 if over else at < 0.99 * 8190.0)
+
+
+def test_resize_guard_images_peak_where_they_say():
+    for over, peak in ((False, 8100.0), (True, 8300.0)):
+        assert float(sr.resize_f64(sr.resize_guard_image(over), 32).abs().max()) == peak
+    assert 8300.0 >= 8190.0 * 1.01 and 8100.0 <= 8190.0 * 0.99
+
+
+def test_resnet_layer_maxima_is_the_torch_forward():
+    """The traced forward returns ist_torch.resnet_forward's features, and `written` holds what the split path stores: the positive part after
+    bn1, the shortcut's BatchNorm output, block outputs -- on a tiny ResNet."""
+    from gigapose_amd.ist_net import ResNet
+    from gigapose_testing import synthetic as syn
+    from oracle import ist_torch
+
+    net = syn.fill_state_dict(ResNet(dict(n_heads=0, input_dim=3, input_size=32, initial_dim=8, block_dims=[8, 16, 16, 32], descriptor_size=8)), 4).eval().double()
+    x = torch.randn(2, 3, 20, 28, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
+    rec, written, feats = sr.resnet_layer_maxima(net, x)
+    with torch.no_grad():
+        assert torch.equal(feats, ist_torch.resnet_forward(net, x))
+    assert "relu(bn1)" in written and "relu(layer3.1.bn1)" in written and "layer2.0.downsample.1" in written and "layer4.1.out" in written
+    assert "conv1" in rec and "conv1" not in written and "layer1.0.bn2" in rec and "layer1.0.bn2" not in written
+    assert all(v <= rec[n[5:-1]] for n, v in written.items() if n.startswith("relu("))
+    assert len(written) == 1 + 1 + 8 + 3 + 8
