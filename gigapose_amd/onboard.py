@@ -13,7 +13,7 @@ it).  The results equal the reference's bit for bit (tests/test_gpu_onboard.py a
   TemplateOnboarder                    renders (+ optional boxes) -> {"rgb", "mask", "M", "box"}
   load_renders(template_dir)           {view_id:06d}.png of one object -> u8 (N,H,W,4) numpy array
   RenderedTemplates                    drop-in for model.template_datasets[name]: item i has .rgb .mask .K .M .poses
-Out of scope: rendering, pose files and the composition of poses (the caller passes what the reference's load_pose returns, in
+Rendering is gigapose_amd/render.py's (MeshTemplates: mesh in, the same item out).  Out of scope here: pose files and the composition of poses (the caller passes what the reference's load_pose returns, in
 bank order), template depth maps.  There is no CPU fallback: the kernels need the GPU, a missing library is an error.
 """
 import ctypes
