@@ -1,4 +1,5 @@
-"""ctypes binding of libgigapose_hip.so (C-ABI: include/gigapose_hip.h).
+"""ctypes binding of libgigapose_hip.so (C-ABI: include/gigapose_hip.h), and SideLibrary: the loader of the front-end libraries
+(libgigapose_ingest / _rlestr / _onboard / _render.so), whose modules hold one instance each.
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  torch must be imported first so the library binds to the HIP runtime torch already
@@ -56,6 +57,45 @@ def _load(path):
     h = ctypes.CDLL(path)
     h.gp_last_error.restype = ctypes.c_char_p
     return h
+
+
+class SideLibrary:
+    """A front-end library next to this file, exporting `<prefix>_*`: loaded on first use; a missing file is an error."""
+
+    def __init__(self, file_name, prefix, restypes=None):
+        self.path = os.path.join(_HERE, file_name)
+        self.prefix = prefix
+        self._restypes = dict(restypes or {}, **{prefix + "_last_error": ctypes.c_char_p})   # entry points that do not return an int
+        self._handle = None
+
+    def lib(self):
+        if self._handle is None:
+            if not os.path.exists(self.path):
+                raise GigaPoseHipError(f"{self.path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                       "(there is deliberately no CPU / PyTorch fallback)")
+            self._handle = ctypes.CDLL(self.path)
+            for name, restype in self._restypes.items():
+                getattr(self._handle, name).restype = restype
+        return self._handle
+
+    def call(self, name, *args):
+        rc = getattr(self.lib(), name)(*args)
+        if rc != 0:
+            raise GigaPoseHipError(f"{name} failed (rc={rc}): {getattr(self.lib(), self.prefix + '_last_error')().decode()}")
+
+
+def chunked(N, limit):
+    """The launches of N items at `limit` per launch (the grid's second dimension holds 65535): yields (chunk index, a, b)."""
+    for c, a in enumerate(range(0, N, limit)):
+        yield c, a, min(N, a + limit)
+
+
+def first_bad(flags, limit):
+    """Per-chunk error flags (n + 1 inside the chunk, 0 = none) -> index of a bad item, or None."""
+    for c, f in enumerate(flags):
+        if f:
+            return c * limit + f - 1
+    return None
 
 
 def lib():

@@ -24,15 +24,7 @@ __global__ __launch_bounds__(256) void crop_resize_pad_kernel(const float* __res
 {
     __shared__ CropGeom g;
     const int d = blockIdx.y, y = blockIdx.x;
-    if (threadIdx.x == 0) {
-        make_geom(boxes + 4 * d, H, W, target, g);
-        if (y == 0) {
-            if (g.bad) atomicExch(err, d + 1);
-            else write_M(g, M + 9 * d);
-        }
-    }
-    __syncthreads();
-    if (g.bad) return;
+    if (!crop_block_enter(g, boxes, d, y, H, W, target, false, M, err)) return;
     const int sy = source_y(g, y);
     for (int x = threadIdx.x; x < target; x += blockDim.x) {
         const int sx = sy < 0 ? -1 : source_x(g, x);
@@ -44,6 +36,20 @@ __global__ __launch_bounds__(256) void crop_resize_pad_kernel(const float* __res
     }
 }
 
+// the dense source: masks[d][sy][sx] and the frame's pixel times it
+struct DenseSource {
+    const uint8_t* frame;
+    const float* mask;
+    int W;
+    size_t plane;
+    __device__ __forceinline__ void fetch(int sy, int sx, float (&v)[3], float& m) const
+    {
+        const size_t o = (size_t)sy * W + sx;
+        m = mask[o];
+        masked_rgb(frame, plane, o, m, v);
+    }
+};
+
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ rgb, const float* __restrict__ masks,
                                                           const long long* __restrict__ boxes, const int* __restrict__ im_id,
                                                           int n_img, int H, int W, int target, float m0, float m1, float m2,
@@ -54,37 +60,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
     __shared__ CropGeom g;
     __shared__ int img;
     const int d = blockIdx.y, y = blockIdx.x;
-    if (threadIdx.x == 0) {
-        make_geom(boxes + 4 * d, H, W, target, g);
-        img = im_id[d];
-        if (img < 0 || img >= n_img) g.bad = 1;
-        if (y == 0) {
-            if (g.bad) atomicExch(err, d + 1);
-            else write_M(g, M + 9 * d);
-        }
-    }
-    __syncthreads();
-    if (g.bad) return;
-    const int sy = source_y(g, y);
-    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+    if (threadIdx.x == 0) img = im_id[d];
+    if (!crop_block_enter(g, boxes, d, y, H, W, target, threadIdx.x == 0 && (img < 0 || img >= n_img), M, err)) return;
     const size_t plane = (size_t)H * W;
-    for (int x = threadIdx.x; x < target; x += blockDim.x) {
-        const int sx = sy < 0 ? -1 : source_x(g, x);
-        float m = 0.f;
-        float v[3] = {0.f, 0.f, 0.f};
-        if (sx >= 0) {
-            const size_t o = (size_t)sy * W + sx;
-            m = masks[(size_t)d * plane + o];
-#pragma unroll
-            for (int c = 0; c < 3; ++c)  // rgb / 255.0 * mask (train.py:83,107)
-                v[c] = ((float)rgb[((size_t)img * 3 + c) * plane + o] / 255.0f) * m;
-        }
-        const size_t po = (size_t)y * target + x, tt = (size_t)target * target;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)  // torchvision Normalize: (x - mean) / std
-            tar_img[((size_t)d * 3 + c) * tt + po] = (v[c] - mean[c]) / stdv[c];
-        tar_mask[(size_t)d * tt + po] = m;
-    }
+    const DenseSource src = {rgb + (size_t)img * 3 * plane, masks + (size_t)d * plane, W, plane};
+    crop_row_normalized(g, d, y, target, src, m0, m1, m2, s0, s1, s2, tar_img, tar_mask);
 }
 
 }  // namespace

@@ -1,10 +1,14 @@
-// Source-index arithmetic of the detection crop, shared by gp_crop.hip (dense masks) and ingest/gpi_ingest.hip (run-length
-// masks): both resizes of CropResizePad.__call__ (src/utils/crop.py:11-61) are nearest-neighbour, so output pixel (y, x) maps
-// to one source pixel through the composed index maps below -- exactly the integer / float arithmetic of ATen's nearest
-// kernels, restated in oracle/crop_numpy.py.  Written ONCE: the two translation units must never disagree on a pixel.
+// The crop kernels' common part, shared by gp_crop.hip (dense masks), ingest/gpi_ingest.hip (run-length masks) and
+// onboard/gpo_onboard.hip (RGBA renders).  Header only; written ONCE: the translation units must never disagree on a pixel.
+//   - the source-index arithmetic: both resizes of CropResizePad.__call__ (src/utils/crop.py:11-61) are nearest-neighbour, so
+//     output pixel (y, x) maps to one source pixel through the composed index maps below -- exactly the integer / float
+//     arithmetic of ATen's nearest kernels, restated in oracle/crop_numpy.py;
+//   - the kernel skeleton, grid (target rows, items), block = 256 threads, thread = output column: crop_block_enter (geometry,
+//     error flag or M, barrier) and crop_row_normalized (the row loop over a pixel source, Normalize's stores).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 
 namespace {
 
@@ -92,6 +96,52 @@ __device__ __forceinline__ void write_M(const CropGeom& g, float* M)
     M[0] = s; M[1] = 0.f; M[2] = s * (-(float)g.x0) + pl;
     M[3] = 0.f; M[4] = s; M[5] = s * (-(float)g.y0) + pt;
     M[6] = 0.f; M[7] = 0.f; M[8] = 1.f;
+}
+
+// Block entry of a crop kernel, called by every thread: thread 0 builds the geometry of item d from its box, `also_bad` (thread
+// 0's value counts: a frame id out of range, an invalid run list) marks the item bad as well, and the block of row 0 reports --
+// d + 1 into *err for a bad item, which is then left unwritten, or the item's M.  Returns whether the block proceeds.
+__device__ __forceinline__ bool crop_block_enter(CropGeom& g, const long long* __restrict__ boxes, int d, int y, int H, int W,
+                                                 int target, bool also_bad, float* __restrict__ M, int* __restrict__ err)
+{
+    if (threadIdx.x == 0) {
+        make_geom(boxes + 4 * d, H, W, target, g);
+        if (also_bad) g.bad = 1;
+        if (y == 0) {
+            if (g.bad) atomicExch(err, d + 1);
+            else write_M(g, M + 9 * d);
+        }
+    }
+    __syncthreads();
+    return !g.bad;
+}
+
+// rgb / 255.0 * mask (train.py:83,107) of pixel o of a planar u8 frame: the colour of the detection crops
+__device__ __forceinline__ void masked_rgb(const uint8_t* __restrict__ frame, size_t plane, size_t o, float m, float (&v)[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = ((float)frame[c * plane + o] / 255.0f) * m;
+}
+
+// Row y of item d: every output pixel takes colour and mask of its source pixel from `src.fetch(sy, sx, v, m)` -- the zero
+// padding has none and keeps v = 0, m = 0 -- and stores torchvision's Normalize of the colour, (v - mean) / std, and the mask.
+template <typename Source>
+__device__ __forceinline__ void crop_row_normalized(const CropGeom& g, int d, int y, int target, const Source& src, float m0,
+                                                    float m1, float m2, float s0, float s1, float s2, float* __restrict__ out_rgb,
+                                                    float* __restrict__ out_mask)
+{
+    const int sy = source_y(g, y);
+    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+    for (int x = threadIdx.x; x < target; x += blockDim.x) {
+        const int sx = sy < 0 ? -1 : source_x(g, x);
+        float m = 0.f;
+        float v[3] = {0.f, 0.f, 0.f};
+        if (sx >= 0) src.fetch(sy, sx, v, m);
+        const size_t po = (size_t)y * target + x, tt = (size_t)target * target;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out_rgb[((size_t)d * 3 + c) * tt + po] = (v[c] - mean[c]) / stdv[c];
+        out_mask[(size_t)d * tt + po] = m;
+    }
 }
 
 }  // namespace

@@ -4,47 +4,15 @@
 //              TemplateSet.__getitem__       src/dataloader/template.py:55-81                 (CropResizePad per render + normalize)
 //              CropResizePad.__call__        src/utils/crop.py:11-61
 // gpo_alpha_boxes is getbbox() on the alpha channel: a pure read of H*W*4 bytes per render, min / max of the columns and rows that
-// hold alpha > 0.  gpo_crop_templates is gp_crop.hip's preprocess_kernel with the interleaved u8 pixel as its source: the four
-// channels of a source pixel are ONE 4-byte load, the mask keeps its 256 levels and the colour is not multiplied by it.  The
-// source-index arithmetic is shared with the detection crops (gp_crop_geom.h), so the three routes agree on every pixel.
+// hold alpha > 0.  gpo_crop_templates is the crop skeleton of gp_crop_geom.h, shared with the detection crops, over the interleaved
+// u8 pixel as its source: the four channels of a source pixel are ONE 4-byte load, the mask keeps its 256 levels and the colour
+// is not multiplied by it.  So the three routes agree on every pixel.  The host-side plumbing is gp_front.h's.
 // This library links no object of libgigapose_hip.so or libgigapose_ingest.so and exports only gpo_* names.
-#include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 
+#define GP_FRONT_PREFIX gpo
+#include "../gp_front.h"
 #include "../gp_crop_geom.h"
-
-#define GPO_OK 0
-#define GPO_EINVAL -1
-#define GPO_ELAUNCH -2
-
-static thread_local char g_err[512] = "";
-static void gpo_set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-#define GPO_REQUIRE(cond, ...)          \
-    do {                                \
-        if (!(cond)) {                  \
-            gpo_set_error(__VA_ARGS__); \
-            return GPO_EINVAL;          \
-        }                               \
-    } while (0)
-
-#define GPO_CHECK_LAUNCH(name)                                                   \
-    do {                                                                         \
-        hipError_t e_ = hipGetLastError();                                       \
-        if (e_ != hipSuccess) {                                                  \
-            gpo_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); \
-            return GPO_ELAUNCH;                                                  \
-        }                                                                        \
-    } while (0)
 
 namespace {
 
@@ -165,7 +133,20 @@ __global__ __launch_bounds__(kThreads) void alpha_box_kernel(const uint32_t* __r
     }
 }
 
-// grid (target rows, N); block = 256 threads, thread = output column -- the shape of gp_crop.hip's preprocess_kernel
+// the interleaved-u8 source: R | G << 8 | B << 16 | A << 24 in one word
+struct RgbaSource {
+    const uint32_t* img;
+    int W;
+    __device__ __forceinline__ void fetch(int sy, int sx, float (&v)[3], float& m) const
+    {
+        const uint32_t px = img[(size_t)sy * W + sx];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = (float)((px >> (8 * c)) & 0xffu) / 255.0f;   // rgba / 255 (template_dataset.py:103)
+        m = (float)(px >> 24) / 255.0f;
+    }
+};
+
+// grid (target rows, N); block = 256 threads, thread = output column
 __global__ __launch_bounds__(kThreads) void crop_templates_kernel(const uint32_t* __restrict__ rgba, const long long* __restrict__ boxes,
                                                                   int H, int W, int target, float m0, float m1, float m2, float s0,
                                                                   float s1, float s2, float* __restrict__ rgb,
@@ -174,44 +155,23 @@ __global__ __launch_bounds__(kThreads) void crop_templates_kernel(const uint32_t
 {
     __shared__ CropGeom g;
     const int n = blockIdx.y, y = blockIdx.x;
-    if (threadIdx.x == 0) {
-        make_geom(boxes + 4 * n, H, W, target, g);
-        if (y == 0) {
-            if (g.bad) atomicExch(err, n + 1);
-            else write_M(g, M + 9 * n);
-        }
-    }
-    __syncthreads();
-    if (g.bad) return;
-    const int sy = source_y(g, y);
-    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-    const uint32_t* img = rgba + (size_t)n * H * W;
-    for (int x = threadIdx.x; x < target; x += blockDim.x) {
-        const int sx = sy < 0 ? -1 : source_x(g, x);
-        const uint32_t px = sx >= 0 ? img[(size_t)sy * W + sx] : 0u;   // R | G << 8 | B << 16 | A << 24; padding is all zero
-        const size_t po = (size_t)y * target + x, tt = (size_t)target * target;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)  // rgba / 255 (template_dataset.py:103), then torchvision Normalize: (x - mean) / std
-            rgb[((size_t)n * 3 + c) * tt + po] = ((float)((px >> (8 * c)) & 0xffu) / 255.0f - mean[c]) / stdv[c];
-        mask[(size_t)n * tt + po] = (float)(px >> 24) / 255.0f;
-    }
+    if (!crop_block_enter(g, boxes, n, y, H, W, target, false, M, err)) return;
+    const RgbaSource src = {rgba + (size_t)n * H * W, W};
+    crop_row_normalized(g, n, y, target, src, m0, m1, m2, s0, s1, s2, rgb, mask);
 }
-
-bool sizes_ok(int N, int H, int W) { return N >= 0 && N <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31); }
 
 }  // namespace
 
 extern "C" {
 
 int gpo_abi_version(void) { return 1; }
-const char* gpo_last_error(void) { return g_err; }
 
 int gpo_alpha_boxes(const uint8_t* rgba, int N, int H, int W, long long* boxes, int* err_flag, void* stream)
 {
-    GPO_REQUIRE(sizes_ok(N, H, W), "gpo_alpha_boxes: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31)");
-    if (N == 0) return GPO_OK;
-    GPO_REQUIRE(rgba && boxes && err_flag, "gpo_alpha_boxes: null pointer");
-    GPO_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpo_alpha_boxes: rgba is not 4-byte aligned (one pixel is one word)");
+    GPF_REQUIRE(frame_sizes_ok(N, H, W), "gpo_alpha_boxes: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31)");
+    if (N == 0) return GPF_OK;
+    GPF_REQUIRE(rgba && boxes && err_flag, "gpo_alpha_boxes: null pointer");
+    GPF_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpo_alpha_boxes: rgba is not 4-byte aligned (one pixel is one word)");
     const hipStream_t s = (hipStream_t)stream;
     const bool vec = (W & 3) == 0 && ((uintptr_t)rgba & 15) == 0;   // then every template and every row starts 16-byte aligned
     const int vw = vec ? W / 4 : W;
@@ -223,28 +183,28 @@ int gpo_alpha_boxes(const uint8_t* rgba, int N, int H, int W, long long* boxes, 
     const dim3 small((N + kThreads - 1) / kThreads);
     const uint32_t* px = reinterpret_cast<const uint32_t*>(rgba);
     hipLaunchKernelGGL(alpha_box_init, small, dim3(kThreads), 0, s, boxes, N, H, W);
-    GPO_CHECK_LAUNCH("gpo_alpha_boxes");
+    GPF_CHECK_LAUNCH("gpo_alpha_boxes");
     if (vec) hipLaunchKernelGGL(alpha_box_kernel<uint4>, dim3(bands, N), dim3(kThreads), 0, s, px, H, W, rows_per_band, boxes);
     else hipLaunchKernelGGL(alpha_box_kernel<uint32_t>, dim3(bands, N), dim3(kThreads), 0, s, px, H, W, rows_per_band, boxes);
-    GPO_CHECK_LAUNCH("gpo_alpha_boxes");
+    GPF_CHECK_LAUNCH("gpo_alpha_boxes");
     hipLaunchKernelGGL(alpha_box_finish, small, dim3(kThreads), 0, s, boxes, N, err_flag);
-    GPO_CHECK_LAUNCH("gpo_alpha_boxes");
-    return GPO_OK;
+    GPF_CHECK_LAUNCH("gpo_alpha_boxes");
+    return GPF_OK;
 }
 
 int gpo_crop_templates(const uint8_t* rgba, const long long* boxes, int N, int H, int W, int target, const float* mean3_host,
                        const float* std3_host, float* rgb, float* mask, float* M, int* err_flag, void* stream)
 {
-    GPO_REQUIRE(sizes_ok(N, H, W) && target > 0 && target <= 4096,
+    GPF_REQUIRE(frame_sizes_ok(N, H, W) && target > 0 && target <= 4096,
                 "gpo_crop_templates: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31, 0 < target <= 4096)");
-    if (N == 0) return GPO_OK;
-    GPO_REQUIRE(rgba && boxes && mean3_host && std3_host && rgb && mask && M && err_flag, "gpo_crop_templates: null pointer");
-    GPO_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpo_crop_templates: rgba is not 4-byte aligned (one pixel is one word)");
+    if (N == 0) return GPF_OK;
+    GPF_REQUIRE(rgba && boxes && mean3_host && std3_host && rgb && mask && M && err_flag, "gpo_crop_templates: null pointer");
+    GPF_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpo_crop_templates: rgba is not 4-byte aligned (one pixel is one word)");
     hipLaunchKernelGGL(crop_templates_kernel, dim3(target, N), dim3(kThreads), 0, (hipStream_t)stream,
                        reinterpret_cast<const uint32_t*>(rgba), boxes, H, W, target, mean3_host[0], mean3_host[1], mean3_host[2],
                        std3_host[0], std3_host[1], std3_host[2], rgb, mask, M, err_flag);
-    GPO_CHECK_LAUNCH("gpo_crop_templates");
-    return GPO_OK;
+    GPF_CHECK_LAUNCH("gpo_crop_templates");
+    return GPF_OK;
 }
 
 }  // extern "C"

@@ -6,52 +6,12 @@
 // bounding box, a triangle with a large box goes to a list and a second launch gives it a whole workgroup.  gpr_resolve: one
 // thread per pixel turns the key into colour, alpha and depth.  The arithmetic (int64 edge functions, float64 interpolation in
 // a fixed order) is spelled out in the header and restated in gigapose_testing/raster_ref.py; the two agree bit for bit.
-// This library links no object of the other libraries and exports only gpr_* names.
-#include <hip/hip_runtime.h>
+// The host-side plumbing is gp_front.h's.  This library links no object of the other libraries and exports only gpr_* names.
 #include <limits.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 
-#define GPR_OK 0
-#define GPR_EINVAL -1
-#define GPR_ELAUNCH -2
-
-static thread_local char g_err[512] = "";
-static void gpr_set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-#define GPR_REQUIRE(cond, ...)          \
-    do {                                \
-        if (!(cond)) {                  \
-            gpr_set_error(__VA_ARGS__); \
-            return GPR_EINVAL;          \
-        }                               \
-    } while (0)
-
-#define GPR_CHECK_LAUNCH(name)                                                   \
-    do {                                                                         \
-        hipError_t e_ = hipGetLastError();                                       \
-        if (e_ != hipSuccess) {                                                  \
-            gpr_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); \
-            return GPR_ELAUNCH;                                                  \
-        }                                                                        \
-    } while (0)
-
-#define GPR_CHECK_HIP(name, call)                                         \
-    do {                                                                  \
-        hipError_t e_ = (call);                                           \
-        if (e_ != hipSuccess) {                                           \
-            gpr_set_error("%s: %s", name, hipGetErrorString(e_));         \
-            return GPR_ELAUNCH;                                           \
-        }                                                                 \
-    } while (0)
+#define GP_FRONT_PREFIX gpr
+#include "../gp_front.h"
 
 namespace {
 
@@ -259,14 +219,12 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const u64* __restrict
     zdepth[o] = z;
 }
 
-bool sizes_ok(int N, int H, int W) { return N >= 0 && N <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31); }
 
 }  // namespace
 
 extern "C" {
 
 int gpr_abi_version(void) { return 1; }
-const char* gpr_last_error(void) { return g_err; }
 int gpr_small_triangle_pixels(void) { return kSmallPixels; }
 
 size_t gpr_raster_workspace_bytes(int N, int F)
@@ -278,59 +236,59 @@ size_t gpr_raster_workspace_bytes(int N, int F)
 int gpr_project(const float* vertices, int V, const float* poses, int N, const float* K_host, float znear, int* xy, float* depth,
                 void* stream)
 {
-    GPR_REQUIRE(V >= 0 && N >= 0 && N <= 65535, "gpr_project: bad sizes (V >= 0, 0 <= N <= 65535)");
-    GPR_REQUIRE(znear >= 1e-30f && znear <= 3.0e38f, "gpr_project: znear must be finite and >= 1e-30");
-    if (N == 0 || V == 0) return GPR_OK;
-    GPR_REQUIRE(vertices && poses && K_host && xy && depth, "gpr_project: null pointer");
-    GPR_REQUIRE(K_host[6] == 0.0f && K_host[7] == 0.0f && K_host[8] == 1.0f, "gpr_project: the last row of K must be 0, 0, 1");
+    GPF_REQUIRE(V >= 0 && N >= 0 && N <= 65535, "gpr_project: bad sizes (V >= 0, 0 <= N <= 65535)");
+    GPF_REQUIRE(znear >= 1e-30f && znear <= 3.0e38f, "gpr_project: znear must be finite and >= 1e-30");
+    if (N == 0 || V == 0) return GPF_OK;
+    GPF_REQUIRE(vertices && poses && K_host && xy && depth, "gpr_project: null pointer");
+    GPF_REQUIRE(K_host[6] == 0.0f && K_host[7] == 0.0f && K_host[8] == 1.0f, "gpr_project: the last row of K must be 0, 0, 1");
     const Cam K = {K_host[0], K_host[1], K_host[2], K_host[3], K_host[4], K_host[5]};
     hipLaunchKernelGGL(project_kernel, dim3((V + kThreads - 1) / kThreads, N), dim3(kThreads), 0, (hipStream_t)stream, vertices, V,
                        poses, K, znear, xy, depth);
-    GPR_CHECK_LAUNCH("gpr_project");
-    return GPR_OK;
+    GPF_CHECK_LAUNCH("gpr_project");
+    return GPF_OK;
 }
 
 int gpr_raster(const int* xy, const float* depth, int V, const int* faces, int F, int N, int H, int W, unsigned long long* vis,
                int* clipped, void* workspace, void* stream)
 {
-    GPR_REQUIRE(sizes_ok(N, H, W) && V >= 0 && F >= 0, "gpr_raster: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31, V, F >= 0)");
-    if (N == 0) return GPR_OK;
-    GPR_REQUIRE(vis && clipped, "gpr_raster: null pointer");
-    GPR_REQUIRE(((uintptr_t)vis & 7) == 0, "gpr_raster: vis is not 8-byte aligned");
+    GPF_REQUIRE(frame_sizes_ok(N, H, W) && V >= 0 && F >= 0, "gpr_raster: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31, V, F >= 0)");
+    if (N == 0) return GPF_OK;
+    GPF_REQUIRE(vis && clipped, "gpr_raster: null pointer");
+    GPF_REQUIRE(((uintptr_t)vis & 7) == 0, "gpr_raster: vis is not 8-byte aligned");
     const hipStream_t s = (hipStream_t)stream;
     if (F > 0) {   // checked before anything is enqueued
-        GPR_REQUIRE(xy && depth && faces && workspace, "gpr_raster: null pointer");
-        GPR_REQUIRE(((uintptr_t)workspace & 7) == 0, "gpr_raster: workspace is not 8-byte aligned");
+        GPF_REQUIRE(xy && depth && faces && workspace, "gpr_raster: null pointer");
+        GPF_REQUIRE(((uintptr_t)workspace & 7) == 0, "gpr_raster: workspace is not 8-byte aligned");
     }
-    GPR_CHECK_HIP("gpr_raster", hipMemsetAsync(vis, 0xff, (size_t)N * H * W * sizeof(u64), s));
-    GPR_CHECK_HIP("gpr_raster", hipMemsetAsync(clipped, 0, (size_t)N * sizeof(int), s));
-    if (F == 0) return GPR_OK;
+    GPF_CHECK_HIP("gpr_raster", hipMemsetAsync(vis, 0xff, (size_t)N * H * W * sizeof(u64), s));
+    GPF_CHECK_HIP("gpr_raster", hipMemsetAsync(clipped, 0, (size_t)N * sizeof(int), s));
+    if (F == 0) return GPF_OK;
     u64* count = reinterpret_cast<u64*>(workspace);
     u64* list = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + kListHeader);
-    GPR_CHECK_HIP("gpr_raster", hipMemsetAsync(workspace, 0, kListHeader, s));
+    GPF_CHECK_HIP("gpr_raster", hipMemsetAsync(workspace, 0, kListHeader, s));
     hipLaunchKernelGGL(raster_small_kernel, dim3((F + kThreads - 1) / kThreads, N), dim3(kThreads), 0, s, xy, depth, V, faces, F, H, W,
                        vis, clipped, count, list);
-    GPR_CHECK_LAUNCH("gpr_raster");
+    GPF_CHECK_LAUNCH("gpr_raster");
     const u64 slots = (u64)N * (u64)F;
     const int blocks = slots < (u64)kLargeBlocks ? (int)slots : kLargeBlocks;
     hipLaunchKernelGGL(raster_large_kernel, dim3(blocks), dim3(kThreads), 0, s, xy, depth, V, faces, F, N, H, W, vis, count, list);
-    GPR_CHECK_LAUNCH("gpr_raster");
-    return GPR_OK;
+    GPF_CHECK_LAUNCH("gpr_raster");
+    return GPF_OK;
 }
 
 int gpr_resolve(const unsigned long long* vis, const int* xy, const float* depth, int V, const int* faces, int F,
                 const uint8_t* colours, int N, int H, int W, uint8_t* rgba, float* zdepth, void* stream)
 {
-    GPR_REQUIRE(sizes_ok(N, H, W) && V >= 0 && F >= 0, "gpr_resolve: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31, V, F >= 0)");
-    if (N == 0) return GPR_OK;
-    GPR_REQUIRE(vis && rgba && zdepth, "gpr_resolve: null pointer");
-    GPR_REQUIRE(F == 0 || (xy && depth && faces && colours), "gpr_resolve: null pointer");
-    GPR_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpr_resolve: rgba is not 4-byte aligned (one pixel is one word)");
+    GPF_REQUIRE(frame_sizes_ok(N, H, W) && V >= 0 && F >= 0, "gpr_resolve: bad sizes (0 <= N <= 65535, H, W > 0, H*W < 2^31, V, F >= 0)");
+    if (N == 0) return GPF_OK;
+    GPF_REQUIRE(vis && rgba && zdepth, "gpr_resolve: null pointer");
+    GPF_REQUIRE(F == 0 || (xy && depth && faces && colours), "gpr_resolve: null pointer");
+    GPF_REQUIRE(((uintptr_t)rgba & 3) == 0, "gpr_resolve: rgba is not 4-byte aligned (one pixel is one word)");
     const unsigned blocks = (unsigned)(((long long)H * W + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(resolve_kernel, dim3(blocks, N), dim3(kThreads), 0, (hipStream_t)stream, vis, xy, depth, V, faces, F, colours, H,
                        W, reinterpret_cast<uint32_t*>(rgba), zdepth);
-    GPR_CHECK_LAUNCH("gpr_resolve");
-    return GPR_OK;
+    GPF_CHECK_LAUNCH("gpr_resolve");
+    return GPF_OK;
 }
 
 }  // extern "C"

@@ -10,85 +10,25 @@
 //      m, the thread that owns a terminator assembles the token by looking BACK (at most 7 bytes, never before the slice start) and
 //      stores x[m] in the detection's slot of `counts`;
 //   2. over the tokens: two running sums (one per parity) turn x into counts, a third one counts into cum.
-// A detection without bytes is an uncompressed list: only pass 2's third sum runs over it, which is gpi_rle_scan's kernel
-// (csrc/ingest/gpi_ingest.hip) restated, so one launch serves a mixed batch and cum has the same bits either way.
+// A detection without bytes is an uncompressed list: only pass 2's third sum runs over it.  That sum is gp_rle_scan.h's, the
+// code gpi_rle_scan (csrc/ingest/gpi_ingest.hip) runs, so one launch serves a mixed batch and cum has the same bits either way.
+// The host-side plumbing is gp_front.h's.
 // This library links no object of the other libraries and exports only gps_* names.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#define GPS_OK 0
-#define GPS_EINVAL -1
-#define GPS_ELAUNCH -2
-
-static thread_local char g_err[512] = "";
-static void gps_set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-#define GPS_REQUIRE(cond, ...)          \
-    do {                                \
-        if (!(cond)) {                  \
-            gps_set_error(__VA_ARGS__); \
-            return GPS_EINVAL;          \
-        }                               \
-    } while (0)
-
-#define GPS_CHECK_LAUNCH(name)                                                   \
-    do {                                                                         \
-        hipError_t e_ = hipGetLastError();                                       \
-        if (e_ != hipSuccess) {                                                  \
-            gps_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); \
-            return GPS_ELAUNCH;                                                  \
-        }                                                                        \
-    } while (0)
+#define GP_FRONT_PREFIX gps
+#include "../gp_front.h"
+#include "../gp_rle_scan.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kScanThreads;
+constexpr int kWaves = kScanWaves;
 constexpr int kByteItems = 8;                       // bytes per thread and chunk of pass 1: one aligned 64-bit load
 constexpr int kByteChunk = kThreads * kByteItems;
-constexpr int kScanItems = 4;                       // tokens per thread and chunk of pass 2 (even: a thread's first token has even m)
-constexpr int kScanChunk = kThreads * kScanItems;
 constexpr int kMaxToken = 7;                        // characters of a value below 2^31 (35 bits)
+static_assert(kScanItems % 2 == 0, "pass 2: a thread's first token has even m");
 
-template <typename T>
-__device__ __forceinline__ T wave_inclusive(T v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-// Inclusive scan of `v` over the block's threads plus the running `carry` of the earlier chunks (every thread keeps it in a
-// register).  wave totals go through `lds`; the barrier after the reads lets the next call reuse it.
-template <typename T>
-__device__ __forceinline__ T block_inclusive(T v, T& carry, T* lds, int lane, int wave)
-{
-    T incl = wave_inclusive(v, lane);
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    incl += carry;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const T t = lds[w];
-        if (w < wave) incl += t;
-        carry += t;
-    }
-    __syncthreads();
-    return incl;
-}
-
-// The same for two sums at once (one hand-over, one pair of barriers): the even and the odd chain of pass 2.
+// gp_rle_scan.h's block_inclusive for two sums at once, the even and the odd chain of pass 2, on ONE slot: the second barrier
+// lets the next call reuse it.
 __device__ __forceinline__ void block_inclusive2(long long& a, long long& b, long long& carry_a, long long& carry_b, long long (*lds)[2],
                                                  int lane, int wave)
 {
@@ -136,12 +76,12 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
                                                                    int n_bytes, const int* __restrict__ offsets, int total, int HW,
                                                                    int* counts, int* __restrict__ cum, int* __restrict__ err)
 {
-    __shared__ long long lds_sum[kWaves], lds_pair[kWaves][2];
-    __shared__ int lds_cnt[kWaves];
+    __shared__ long long lds_sum[2][kWaves], lds_pair[kWaves][2];
+    __shared__ int lds_cnt[2][kWaves];
     __shared__ int bad_any;
     const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lo = offsets[d], hi = offsets[d + 1];
-    if (!(0 <= lo && lo < hi && hi <= total)) {     // no slot at all, or a slice outside the arrays: nothing is written
+    int lo, hi;
+    if (!list_range(offsets, d, total, lo, hi)) {   // no slot at all, or a slice outside the arrays: nothing is written
         if (tid == 0) atomicExch(err, d + 1);
         return;
     }
@@ -161,8 +101,8 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
         // pass 1.  Chunks start on an 8-byte ADDRESS boundary at or before the slice, so that a thread whose 8 bytes lie wholly
         // inside the slice loads them as one word; the threads at the two ends load byte by byte, and only bytes of the slice.
         const long long first = ba - (long long)(((uintptr_t)bytes + (uintptr_t)ba) & 7);
-        int n_tokens = 0;                            // carry: terminators in the earlier chunks
-        for (long long base = first; base < bb; base += kByteChunk) {
+        int n_tokens = 0, buf = 0;                   // carry: terminators in the earlier chunks; the slot of lds_cnt in turn
+        for (long long base = first; base < bb; base += kByteChunk, buf ^= 1) {
             const long long p0 = base + (long long)tid * kByteItems;
             unsigned long long w = 0;
             if (p0 >= ba && p0 + kByteItems <= bb) {
@@ -183,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
                 if (p0 + k == bb - 1) bad |= more;   // the string stops inside a token
             }
             const int mine = __popc(ends);
-            int m = block_inclusive(mine, n_tokens, lds_cnt, lane, wave) - mine;
+            int m = block_inclusive(mine, n_tokens, lds_cnt[buf], lane, wave) - mine;
 #pragma unroll
             for (int k = 0; k < kByteItems; ++k) {
                 if (!(ends & (1 << k))) continue;
@@ -207,9 +147,10 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
     }
     // pass 2.  Chunk = 1024 list entries, 4 consecutive ones per thread, the first at an even position.  A string's entries hold x:
     // counts[m] is the running sum of its parity's x (position 0 stands alone, the even chain starts at 2); 64-bit, so that garbage
-    // cannot wrap into a plausible value.  A count outside [0, H*W] is bad and stored clamped to [-1, H*W].  Then cum as
-    // gpi_rle_scan builds it: inclusive 64-bit sums, clamped to H*W.
-    long long carry_even = 0, carry_odd = 0, carry = 0;
+    // cannot wrap into a plausible value.  A count outside [0, H*W] is bad and stored clamped to [-1, H*W].  Then cum by the
+    // scan gpi_rle_scan runs (gp_rle_scan.h): inclusive 64-bit sums, clamped to H*W.
+    long long carry_even = 0, carry_odd = 0;
+    CumScan scan;
     for (int base = lo; base < hi; base += kScanChunk) {
         const int i0 = base + tid * kScanItems;
         long long v[kScanItems];
@@ -228,33 +169,15 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
             v[1] = odd0 + v[1];
 #pragma unroll
             for (int k = 0; k < kScanItems; ++k) {
-                bad |= i0 + k < hi && (v[k] < 0 || v[k] > HW);
+                scan.bad |= i0 + k < hi && (v[k] < 0 || v[k] > HW);
                 v[k] = v[k] < 0 ? -1 : (v[k] > HW ? HW : v[k]);
                 if (i0 + k < hi) counts[i0 + k] = (int)v[k];
                 else v[k] = 0;
             }
         }
-        long long s = 0;
-#pragma unroll
-        for (int k = 0; k < kScanItems; ++k) {
-            bad |= v[k] < 0;
-            s += v[k];
-            v[k] = s;
-        }
-        const long long before = block_inclusive(s, carry, lds_sum, lane, wave) - s;
-#pragma unroll
-        for (int k = 0; k < kScanItems; ++k) {
-            const long long c = before + v[k];
-            bad |= c > HW;
-            if (i0 + k < hi) cum[i0 + k] = c > HW ? HW : (int)c;   // clamped: a bad list is marked below and never searched
-        }
+        scan.chunk(v, i0, hi, HW, cum, lds_sum, lane, wave);
     }
-    if (bad) bad_any = 1;
-    __syncthreads();
-    if (tid == 0 && (bad_any || carry != HW)) {
-        cum[hi - 1] = -1;
-        atomicExch(err, d + 1);
-    }
+    scan.finish(d, hi, HW, cum, err, &bad_any);
 }
 
 }  // namespace
@@ -262,19 +185,18 @@ __global__ __launch_bounds__(kThreads) void rle_string_scan_kernel(const uint8_t
 extern "C" {
 
 int gps_abi_version(void) { return 1; }
-const char* gps_last_error(void) { return g_err; }
 
 int gps_rle_string_scan(const uint8_t* bytes, const int* byte_offsets, int n_bytes, const int* offsets, int total, int D, int H, int W,
                         int* counts, int* cum, int* err_flag, void* stream)
 {
-    GPS_REQUIRE(D >= 0 && D <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 31) && total >= 0 && total < (1 << 30) && n_bytes >= 0,
+    GPF_REQUIRE(frame_sizes_ok(D, H, W) && total >= 0 && total < (1 << 30) && n_bytes >= 0,
                 "gps_rle_string_scan: bad sizes (0 <= D <= 65535, H, W > 0, H*W < 2^31, 0 <= total < 2^30, 0 <= n_bytes < 2^31)");
-    if (D == 0) return GPS_OK;
-    GPS_REQUIRE(byte_offsets && offsets && counts && cum && err_flag && (bytes || n_bytes == 0), "gps_rle_string_scan: null pointer");
+    if (D == 0) return GPF_OK;
+    GPF_REQUIRE(byte_offsets && offsets && counts && cum && err_flag && (bytes || n_bytes == 0), "gps_rle_string_scan: null pointer");
     hipLaunchKernelGGL(rle_string_scan_kernel, dim3(D), dim3(kThreads), 0, (hipStream_t)stream, bytes, byte_offsets, n_bytes, offsets, total,
                        H * W, counts, cum, err_flag);
-    GPS_CHECK_LAUNCH("gps_rle_string_scan");
-    return GPS_OK;
+    GPF_CHECK_LAUNCH("gps_rle_string_scan");
+    return GPF_OK;
 }
 
 }  // extern "C"

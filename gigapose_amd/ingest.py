@@ -23,7 +23,6 @@ Compressed string `counts` (pycocotools' byte coding) are out of scope: `pack_rl
 There is no CPU fallback: the kernels need the GPU, a missing library is an error.
 """
 import ctypes
-import os
 
 import numpy as np
 import pandas as pd
@@ -33,25 +32,8 @@ from . import _lib
 from .crop import CLIP_MEAN, CLIP_STD
 from .tensor_collection import PandasTensorCollection
 
-INGEST_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgigapose_ingest.so")
-_ingest = None
-
-
-def lib():
-    global _ingest
-    if _ingest is None:
-        if not os.path.exists(INGEST_LIB_PATH):
-            raise _lib.GigaPoseHipError(f"{INGEST_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                        "(there is deliberately no CPU / PyTorch fallback)")
-        _ingest = ctypes.CDLL(INGEST_LIB_PATH)
-        _ingest.gpi_last_error.restype = ctypes.c_char_p
-    return _ingest
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise _lib.GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gpi_last_error().decode()}")
+_ingest = _lib.SideLibrary("libgigapose_ingest.so", "gpi")
+INGEST_LIB_PATH, lib, _call = _ingest.path, _ingest.lib, _ingest.call
 
 
 # ------------------------------------------------------------------------------------------------ host side: the format
@@ -160,53 +142,84 @@ class RleDetectionPreprocessor:
               _lib.i(W), _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())
         return cum
 
+    def _inputs(self, counts, offsets, dev):
+        """What the scan reads, on the device; the last two are (counts, offsets)."""
+        counts, offsets = self._dev(counts, dev, torch.int32), self._dev(offsets, dev, torch.int32)
+        assert counts.dim() == 1 and offsets.dim() == 1
+        return counts, offsets
+
+    def _scan(self, lists, H, W, err):
+        """The step a subclass replaces: what _inputs returned -> cum."""
+        return self.scan(*lists, H, W, err)
+
     @torch.no_grad()
     def decode(self, counts, offsets, H, W):
         """The dense masks (D,H,W) f32 the lists encode (gpi_rle_decode): the reference's scene_obs.binary_masks."""
-        dev = counts.device
+        return self._decode((counts, offsets), counts.device, H, W)
+
+    def _decode(self, lists, dev, H, W):
+        lists = self._inputs(*lists, dev)
+        counts, offsets = lists[-2:]
         D = offsets.numel() - 1
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        cum = self.scan(counts, offsets, H, W, err)
+        cum = self._scan(lists, H, W, err)
         masks = torch.zeros(D, H, W, device=dev)
         _call("gpi_rle_decode", _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.i(D), _lib.i(H), _lib.i(W),
               _lib.ptr(masks), _lib.stream_ptr())
         bad = int(err.item())
         if bad:
-            raise ValueError(f"RleDetectionPreprocessor.decode: detection {bad - 1} has a bad run-length list (no run, a negative "
+            raise ValueError(f"{type(self).__name__}.decode: detection {bad - 1} has a bad run-length list (no run, a negative "
                              f"run or a total other than H*W = {H * W})")
         return masks
 
     @torch.no_grad()
     def __call__(self, rgb_u8, counts, offsets, xyxy_boxes, batch_im_id):
+        return self._crop(rgb_u8, (counts, offsets), xyxy_boxes, batch_im_id)
+
+    def _crop(self, rgb_u8, lists, xyxy_boxes, batch_im_id, **how):
+        who = type(self).__name__
         if not (isinstance(rgb_u8, torch.Tensor) and rgb_u8.is_cuda):
-            raise _lib.GigaPoseHipError("RleDetectionPreprocessor needs the frames on the GPU (no CPU fallback)")
+            raise _lib.GigaPoseHipError(f"{who} needs the frames on the GPU (no CPU fallback)")
         dev = rgb_u8.device
         assert rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[1] == 3
         rgb_u8 = rgb_u8.contiguous()
-        counts = self._dev(counts, dev, torch.int32)
-        offsets = self._dev(offsets, dev, torch.int32)
+        lists = self._inputs(*lists, dev, **how)
+        counts, offsets = lists[-2:]
         boxes = self._dev(xyxy_boxes, dev, torch.int64)
         im_id = self._dev(batch_im_id, dev, torch.int32)
         n_img, _, H, W = rgb_u8.shape
         D, T = offsets.numel() - 1, self.target_size
-        assert counts.dim() == 1 and offsets.dim() == 1 and D >= 0 and boxes.shape == (D, 4) and im_id.shape == (D,)
+        assert D >= 0 and boxes.shape == (D, 4) and im_id.shape == (D,)
         tar_img = torch.empty(D, 3, T, T, device=dev)
         tar_mask = torch.empty(D, T, T, device=dev)
         M = torch.empty(D, 3, 3, device=dev)
         if D == 0:
             return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}
         err = torch.zeros(2, dtype=torch.int32, device=dev)     # [0]: the scan's flag, [1]: the crop's
-        cum = self.scan(counts, offsets, H, W, err[0:1])
+        cum = self._scan(lists, H, W, err[0:1])
         _call("gpi_preprocess_detections_rle", _lib.ptr(rgb_u8), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()),
               _lib.ptr(boxes), _lib.ptr(im_id), _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), self._mean, self._std,
               _lib.ptr(tar_img), _lib.ptr(tar_mask), _lib.ptr(M), _lib.ptr(err[1:2]), _lib.stream_ptr())
         bad_list, bad_box = err.tolist()  # one host sync per batch, where DetectionPreprocessor has its own
         if bad_list:
-            raise ValueError(f"RleDetectionPreprocessor: detection {bad_list - 1} has a bad run-length list (no run, a negative run "
+            raise ValueError(f"{who}: detection {bad_list - 1} has a bad run-length list (no run, a negative run "
                              f"or a total other than H*W = {H * W})")
         if bad_box:
-            raise ValueError(f"RleDetectionPreprocessor: detection {bad_box - 1} has an empty / out-of-frame box")
+            raise ValueError(f"{who}: detection {bad_box - 1} has an empty / out-of-frame box")
         return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}
+
+
+def lay_pinned(parts):
+    """(name, array) parts laid end to end into ONE pinned u8 buffer -> (buffer, {name: (first byte, past the last, shape)})."""
+    spans, at = {}, 0
+    for name, a in parts:
+        spans[name] = (at, at + a.nbytes, a.shape)
+        at += a.nbytes
+    buf = torch.empty(max(at, 1), dtype=torch.uint8, pin_memory=True)
+    view = buf.numpy()
+    for name, a in parts:
+        view[spans[name][0]:spans[name][1]] = a.reshape(-1).view(np.uint8)
+    return buf, spans
 
 
 class FrameIngest:
@@ -225,47 +238,54 @@ class FrameIngest:
     @staticmethod
     def stage(counts, offsets, xyxy, im_id, K):
         """The pinned staging buffer: [boxes i64 | counts i32 | offsets i32 | im_id i32 | K f32] and the byte spans of its parts."""
-        parts = [("boxes", np.ascontiguousarray(xyxy, np.int64)), ("counts", np.ascontiguousarray(counts, np.int32)),
-                 ("offsets", np.ascontiguousarray(offsets, np.int32)), ("im_id", np.ascontiguousarray(im_id, np.int32)),
-                 ("K", np.ascontiguousarray(K, np.float32))]
-        spans, at = {}, 0
-        for name, a in parts:
-            spans[name] = (at, at + a.nbytes, a.shape)
-            at += a.nbytes
-        buf = torch.empty(max(at, 1), dtype=torch.uint8, pin_memory=True)
-        view = buf.numpy()
-        for name, a in parts:
-            view[spans[name][0]:spans[name][1]] = a.reshape(-1).view(np.uint8)
-        return buf, spans
+        return lay_pinned([("boxes", np.ascontiguousarray(xyxy, np.int64)), ("counts", np.ascontiguousarray(counts, np.int32)),
+                           ("offsets", np.ascontiguousarray(offsets, np.int32)), ("im_id", np.ascontiguousarray(im_id, np.int32)),
+                           ("K", np.ascontiguousarray(K, np.float32))])
 
-    @torch.no_grad()
-    def __call__(self, frames_u8, K, infos, detections, test_list=None, label_map=None):
-        """frames_u8 (n_img,3,H,W) u8 (host, ideally pinned, or already on the device), K (n_img,3,3), infos: per image scene_id
-        and view_id, detections: per image the list of CNOS dicts (bbox xywh, category_id, score, segmentation, optional time)."""
+    @staticmethod
+    def _frames(frames_u8, K, detections):
+        """The frame / K checks -> (frames tensor, K as numpy, H, W)."""
         if isinstance(frames_u8, np.ndarray):
             frames_u8 = torch.from_numpy(frames_u8)
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[1] == 3
         n_img, _, H, W = frames_u8.shape
         K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
         assert K.shape == (n_img, 3, 3) and len(detections) == n_img
-        counts, offsets, xyxy, im_id, frame = host_batch(infos, detections, H, W, label_map)
-        dev, T, D = self.device, self.target_size, len(im_id)
-        if D == 0:
-            batch = PandasTensorCollection(infos=frame, tar_img=torch.empty(0, 3, T, T, device=dev), tar_mask=torch.empty(0, T, T, device=dev),
-                                           tar_K=torch.empty(0, 3, 3, device=dev), tar_M=torch.empty(0, 3, 3, device=dev))
-            batch.test_list = test_list
-            return batch
-        buf, spans = self.stage(counts, offsets, xyxy, im_id, K)
-        dbuf = buf.to(dev, non_blocking=True)
-        frames = frames_u8.to(dev, non_blocking=True)
+        return frames_u8, K, H, W
 
+    @staticmethod
+    def _batch(frame, test_list, **tensors):
+        batch = PandasTensorCollection(infos=frame, **tensors)
+        batch.test_list = test_list
+        return batch
+
+    def _empty(self, frame, test_list):
+        dev, T = self.device, self.target_size
+        return self._batch(frame, test_list, tar_img=torch.empty(0, 3, T, T, device=dev), tar_mask=torch.empty(0, T, T, device=dev),
+                           tar_K=torch.empty(0, 3, 3, device=dev), tar_M=torch.empty(0, 3, 3, device=dev))
+
+    def _preprocess(self, frames, part, boxes, im):
+        return self.preprocess(frames, part("counts", torch.int32), part("offsets", torch.int32), boxes, im)
+
+    def _finish(self, dbuf, spans, frame, frames, test_list):
+        """The staged buffer on the device -> the batch."""
         def part(name, dtype):
             a, b, shape = spans[name]
             return dbuf[a:b].view(dtype).view(shape)
 
         im = part("im_id", torch.int32)
-        out = self.preprocess(frames, part("counts", torch.int32), part("offsets", torch.int32), part("boxes", torch.int64), im)
+        out = self._preprocess(frames, part, part("boxes", torch.int64), im)
         tar_K = part("K", torch.float32).index_select(0, im.long())        # data.K[idx_selected].float() (train.py:102)
-        batch = PandasTensorCollection(infos=frame, tar_img=out["tar_img"], tar_mask=out["tar_mask"], tar_K=tar_K, tar_M=out["tar_M"])
-        batch.test_list = test_list
-        return batch
+        return self._batch(frame, test_list, tar_img=out["tar_img"], tar_mask=out["tar_mask"], tar_K=tar_K, tar_M=out["tar_M"])
+
+    @torch.no_grad()
+    def __call__(self, frames_u8, K, infos, detections, test_list=None, label_map=None):
+        """frames_u8 (n_img,3,H,W) u8 (host, ideally pinned, or already on the device), K (n_img,3,3), infos: per image scene_id
+        and view_id, detections: per image the list of CNOS dicts (bbox xywh, category_id, score, segmentation, optional time)."""
+        frames_u8, K, H, W = self._frames(frames_u8, K, detections)
+        counts, offsets, xyxy, im_id, frame = host_batch(infos, detections, H, W, label_map)
+        if len(im_id) == 0:
+            return self._empty(frame, test_list)
+        buf, spans = self.stage(counts, offsets, xyxy, im_id, K)
+        dbuf = buf.to(self.device, non_blocking=True)
+        return self._finish(dbuf, spans, frame, frames_u8.to(self.device, non_blocking=True), test_list)

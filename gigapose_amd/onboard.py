@@ -28,27 +28,10 @@ from . import _lib
 from .crop import CLIP_MEAN, CLIP_STD
 from .tensor_collection import PandasTensorCollection
 
-ONBOARD_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgigapose_onboard.so")
 MAX_TEMPLATES_PER_CALL = 65535                      # the grid's second dimension (gigapose_onboard.h: Limits)
 TEMPLATE_K = ((572.4114, 0.0, 320.0), (0.0, 573.57043, 240.0), (0.0, 0.0, 1.0))   # template_dataset.py:194-196
-_onboard = None
-
-
-def lib():
-    global _onboard
-    if _onboard is None:
-        if not os.path.exists(ONBOARD_LIB_PATH):
-            raise _lib.GigaPoseHipError(f"{ONBOARD_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                        "(there is deliberately no CPU / PyTorch fallback)")
-        _onboard = ctypes.CDLL(ONBOARD_LIB_PATH)
-        _onboard.gpo_last_error.restype = ctypes.c_char_p
-    return _onboard
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise _lib.GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gpo_last_error().decode()}")
+_onboard = _lib.SideLibrary("libgigapose_onboard.so", "gpo")
+ONBOARD_LIB_PATH, lib, _call = _onboard.path, _onboard.lib, _onboard.call
 
 
 def _device_renders(rgba_u8, who):
@@ -65,18 +48,9 @@ def _device_renders(rgba_u8, who):
 def _alpha_boxes(rgba_u8, boxes, err):
     """boxes (N,4) int64 and err (chunks,) int32 on the device; chunk c of 65535 renders reports into err[c]."""
     N, H, W, _ = rgba_u8.shape
-    for c, a in enumerate(range(0, N, MAX_TEMPLATES_PER_CALL)):
-        b = min(N, a + MAX_TEMPLATES_PER_CALL)
+    for c, a, b in _lib.chunked(N, MAX_TEMPLATES_PER_CALL):
         _call("gpo_alpha_boxes", _lib.ptr(rgba_u8[a:b]), _lib.i(b - a), _lib.i(H), _lib.i(W), _lib.ptr(boxes[a:b]), _lib.ptr(err[c:c + 1]),
               _lib.stream_ptr())
-
-
-def _first_bad(flags):
-    """Per-chunk flags (n + 1 inside the chunk, 0 = none) -> index of a bad template, or None."""
-    for c, f in enumerate(flags):
-        if f:
-            return c * MAX_TEMPLATES_PER_CALL + f - 1
-    return None
 
 
 @torch.no_grad()
@@ -88,7 +62,7 @@ def alpha_boxes(rgba_u8):
     boxes = torch.empty(N, 4, dtype=torch.int64, device=rgba_u8.device)
     err = torch.zeros(max(1, -(-N // MAX_TEMPLATES_PER_CALL)), dtype=torch.int32, device=rgba_u8.device)
     _alpha_boxes(rgba_u8, boxes, err)
-    bad = _first_bad(err.tolist())
+    bad = _lib.first_bad(err.tolist(), MAX_TEMPLATES_PER_CALL)
     if bad is not None:
         raise ValueError(f"alpha_boxes: template {bad} is fully transparent")
     return boxes
@@ -128,16 +102,15 @@ class TemplateOnboarder:
         else:
             boxes = torch.empty(N, 4, dtype=torch.int64, device=dev)
             _alpha_boxes(rgba_u8, boxes, err[0])
-        for c, a in enumerate(range(0, N, MAX_TEMPLATES_PER_CALL)):
-            b = min(N, a + MAX_TEMPLATES_PER_CALL)
+        for c, a, b in _lib.chunked(N, MAX_TEMPLATES_PER_CALL):
             _call("gpo_crop_templates", _lib.ptr(rgba_u8[a:b]), _lib.ptr(boxes[a:b]), _lib.i(b - a), _lib.i(H), _lib.i(W), _lib.i(T),
                   self._mean, self._std, _lib.ptr(out["rgb"][a:b]), _lib.ptr(out["mask"][a:b]), _lib.ptr(out["M"][a:b]),
                   _lib.ptr(err[1, c:c + 1]), _lib.stream_ptr())
         no_alpha, no_crop = err.tolist()
-        bad = _first_bad(no_alpha)
+        bad = _lib.first_bad(no_alpha, MAX_TEMPLATES_PER_CALL)
         if bad is not None:
             raise ValueError(f"TemplateOnboarder: template {bad} is fully transparent (PIL getbbox() returns None for it)")
-        bad = _first_bad(no_crop)
+        bad = _lib.first_bad(no_crop, MAX_TEMPLATES_PER_CALL)
         if bad is not None:
             why = "has an empty / out-of-frame box, or its " if given else "has a "
             raise ValueError(f"TemplateOnboarder: template {bad} {why}box scales to an empty crop (the short side times "

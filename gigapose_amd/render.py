@@ -28,28 +28,10 @@ from . import _lib
 from .onboard import TEMPLATE_K, TemplateOnboarder
 from .tensor_collection import PandasTensorCollection
 
-RENDER_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgigapose_render.so")
 MAX_VIEWS_PER_CALL = 65535                          # the grid's second dimension (gigapose_render.h: Limits)
 VIS_BYTES_PER_CALL = 1 << 30                        # default chunking: the visibility buffer of one call stays below this
-_render = None
-
-
-def lib():
-    global _render
-    if _render is None:
-        if not os.path.exists(RENDER_LIB_PATH):
-            raise _lib.GigaPoseHipError(f"{RENDER_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                        "(there is deliberately no CPU / PyTorch fallback)")
-        _render = ctypes.CDLL(RENDER_LIB_PATH)
-        _render.gpr_last_error.restype = ctypes.c_char_p
-        _render.gpr_raster_workspace_bytes.restype = ctypes.c_size_t
-    return _render
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise _lib.GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gpr_last_error().decode()}")
+_render = _lib.SideLibrary("libgigapose_render.so", "gpr", {"gpr_raster_workspace_bytes": ctypes.c_size_t})
+RENDER_LIB_PATH, lib, _call = _render.path, _render.lib, _render.call
 
 
 def small_triangle_pixels():
@@ -320,8 +302,7 @@ class MeshRenderer:
         vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
         vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
         work = torch.empty(max(1, -(-int(lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
-        for a in range(0, N, step):
-            b = min(N, a + step)
+        for _, a, b in _lib.chunked(N, step):
             pxy, pz = project(vertices, poses[a:b], self._K, self.znear, out=(xy, vdepth))
             keys, _ = raster(pxy, pz, faces, H, W, out=(vis, clipped[a:b]), workspace=work)
             resolve(keys, pxy, pz, faces, colours, out=(rgba[a:b], depth[a:b]))

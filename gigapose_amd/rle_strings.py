@@ -19,38 +19,16 @@ most 7.
   CocoFrameIngest                     FrameIngest that accepts string, bytes and list counts, mixed within a batch
 There is no CPU fallback: the kernel needs the GPU, a missing library is an error.
 """
-import ctypes
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
-from .ingest import FrameIngest, RleDetectionPreprocessor, host_batch, mask_to_rle_counts
-from .ingest import _call as _ingest_call
+from .ingest import FrameIngest, RleDetectionPreprocessor, host_batch, lay_pinned, mask_to_rle_counts
 from .crop import CLIP_MEAN, CLIP_STD
-from .tensor_collection import PandasTensorCollection
 
-RLESTR_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgigapose_rlestr.so")
 MAX_TOKEN = 7                                         # characters of one value (35 bits)
-_rlestr = None
-
-
-def lib():
-    global _rlestr
-    if _rlestr is None:
-        if not os.path.exists(RLESTR_LIB_PATH):
-            raise _lib.GigaPoseHipError(f"{RLESTR_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                        "(there is deliberately no CPU / PyTorch fallback)")
-        _rlestr = ctypes.CDLL(RLESTR_LIB_PATH)
-        _rlestr.gps_last_error.restype = ctypes.c_char_p
-    return _rlestr
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise _lib.GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gps_last_error().decode()}")
+_rlestr = _lib.SideLibrary("libgigapose_rlestr.so", "gps")
+RLESTR_LIB_PATH, lib, _call = _rlestr.path, _rlestr.lib, _rlestr.call
 
 
 # ------------------------------------------------------------------------------------------------ host side: the codec
@@ -179,6 +157,9 @@ class StringRleDetectionPreprocessor(RleDetectionPreprocessor):
               _lib.stream_ptr())
         return cum
 
+    def _scan(self, lists, H, W, err):
+        return self.scan_strings(*lists, H, W, err)
+
     def _inputs(self, data, byte_offsets, counts, offsets, dev, in_place=False):
         data = self._dev(data, dev, torch.uint8)
         byte_offsets = self._dev(byte_offsets, dev, torch.int32)
@@ -194,51 +175,12 @@ class StringRleDetectionPreprocessor(RleDetectionPreprocessor):
         """The dense masks (D,H,W) f32 the strings and lists encode (gps_rle_string_scan, then gpi_rle_decode)."""
         if not (isinstance(data, torch.Tensor) and data.is_cuda):
             raise _lib.GigaPoseHipError("StringRleDetectionPreprocessor.decode needs the strings on the GPU (no CPU fallback)")
-        dev = data.device
-        data, byte_offsets, counts, offsets = self._inputs(data, byte_offsets, counts, offsets, dev)
-        D = offsets.numel() - 1
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-        cum = self.scan_strings(data, byte_offsets, counts, offsets, H, W, err)
-        masks = torch.zeros(D, H, W, device=dev)
-        _ingest_call("gpi_rle_decode", _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.i(D), _lib.i(H), _lib.i(W),
-                     _lib.ptr(masks), _lib.stream_ptr())
-        bad = int(err.item())
-        if bad:
-            raise ValueError(f"StringRleDetectionPreprocessor.decode: detection {bad - 1} has a bad run-length list (no run, a negative "
-                             f"run or a total other than H*W = {H * W})")
-        return masks
+        return self._decode((data, byte_offsets, counts, offsets), data.device, H, W)
 
     @torch.no_grad()
     def __call__(self, rgb_u8, data, byte_offsets, counts, offsets, xyxy_boxes, batch_im_id, in_place=False):
         """in_place: a `counts` tensor that already sits on the device receives the decoded lists instead of a copy of it."""
-        if not (isinstance(rgb_u8, torch.Tensor) and rgb_u8.is_cuda):
-            raise _lib.GigaPoseHipError("StringRleDetectionPreprocessor needs the frames on the GPU (no CPU fallback)")
-        dev = rgb_u8.device
-        assert rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[1] == 3
-        rgb_u8 = rgb_u8.contiguous()
-        data, byte_offsets, counts, offsets = self._inputs(data, byte_offsets, counts, offsets, dev, in_place)
-        boxes = self._dev(xyxy_boxes, dev, torch.int64)
-        im_id = self._dev(batch_im_id, dev, torch.int32)
-        n_img, _, H, W = rgb_u8.shape
-        D, T = offsets.numel() - 1, self.target_size
-        assert D >= 0 and boxes.shape == (D, 4) and im_id.shape == (D,)
-        tar_img = torch.empty(D, 3, T, T, device=dev)
-        tar_mask = torch.empty(D, T, T, device=dev)
-        M = torch.empty(D, 3, 3, device=dev)
-        if D == 0:
-            return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}
-        err = torch.zeros(2, dtype=torch.int32, device=dev)     # [0]: the scan's flag, [1]: the crop's
-        cum = self.scan_strings(data, byte_offsets, counts, offsets, H, W, err[0:1])
-        _ingest_call("gpi_preprocess_detections_rle", _lib.ptr(rgb_u8), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()),
-                     _lib.ptr(boxes), _lib.ptr(im_id), _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), self._mean, self._std,
-                     _lib.ptr(tar_img), _lib.ptr(tar_mask), _lib.ptr(M), _lib.ptr(err[1:2]), _lib.stream_ptr())
-        bad_list, bad_box = err.tolist()  # one host sync per batch, as RleDetectionPreprocessor
-        if bad_list:
-            raise ValueError(f"StringRleDetectionPreprocessor: detection {bad_list - 1} has a bad run-length list (no run, a negative "
-                             f"run or a total other than H*W = {H * W})")
-        if bad_box:
-            raise ValueError(f"StringRleDetectionPreprocessor: detection {bad_box - 1} has an empty / out-of-frame box")
-        return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}
+        return self._crop(rgb_u8, (data, byte_offsets, counts, offsets), xyxy_boxes, batch_im_id, in_place=in_place)
 
 
 class CocoFrameIngest(FrameIngest):
@@ -266,51 +208,27 @@ class CocoFrameIngest(FrameIngest):
         parts = [("boxes", np.ascontiguousarray(xyxy, np.int64)), ("offsets", offsets), ("byte_offsets", byte_offsets),
                  ("im_id", np.ascontiguousarray(im_id, np.int32)), ("K", np.ascontiguousarray(K, np.float32)), ("bytes", data),
                  ("pad", np.zeros(-data.size % 4, np.uint8)), ("counts", counts[:head])]
-        spans, at = {}, 0
-        for name, a in parts:
-            spans[name] = (at, at + a.nbytes, a.shape)
-            at += a.nbytes
-        buf = torch.empty(max(at, 1), dtype=torch.uint8, pin_memory=True)
-        view = buf.numpy()
-        for name, a in parts:
-            view[spans[name][0]:spans[name][1]] = a.reshape(-1).view(np.uint8)
+        buf, spans = lay_pinned(parts)
         a = spans["counts"][0]
         spans["counts"] = (a, a + counts.nbytes, counts.shape)
         return buf, spans, max(a + counts.nbytes, 1)
 
+    def _preprocess(self, frames, part, boxes, im):
+        return self.preprocess(frames, part("bytes", torch.uint8), part("byte_offsets", torch.int32), part("counts", torch.int32),
+                               part("offsets", torch.int32), boxes, im, in_place=True)
+
     @torch.no_grad()
     def __call__(self, frames_u8, K, infos, detections, test_list=None, label_map=None):
-        if isinstance(frames_u8, np.ndarray):
-            frames_u8 = torch.from_numpy(frames_u8)
-        assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[1] == 3
-        n_img, _, H, W = frames_u8.shape
-        K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
-        assert K.shape == (n_img, 3, 3) and len(detections) == n_img
+        frames_u8, K, H, W = self._frames(frames_u8, K, detections)
         if len(infos) != len(detections):
             raise ValueError(f"CocoFrameIngest: {len(infos)} image infos for {len(detections)} detection lists")
         data, byte_offsets, counts, offsets = pack_rle_any([det["segmentation"] for dets in detections for det in dets], H, W)
         # boxes, frame ids and the infos rows are host_batch's; it gets a one-run list in place of every mask, which it only packs
         blank = dict(counts=[H * W], size=[H, W])
         _, _, xyxy, im_id, frame = host_batch(infos, [[dict(det, segmentation=blank) for det in dets] for dets in detections], H, W, label_map)
-        dev, T, D = self.device, self.target_size, len(im_id)
-        if D == 0:
-            batch = PandasTensorCollection(infos=frame, tar_img=torch.empty(0, 3, T, T, device=dev), tar_mask=torch.empty(0, T, T, device=dev),
-                                           tar_K=torch.empty(0, 3, 3, device=dev), tar_M=torch.empty(0, 3, 3, device=dev))
-            batch.test_list = test_list
-            return batch
+        if len(im_id) == 0:
+            return self._empty(frame, test_list)
         buf, spans, device_bytes = self.stage(data, byte_offsets, counts, offsets, xyxy, im_id, K)
-        dbuf = torch.empty(device_bytes, dtype=torch.uint8, device=dev)
+        dbuf = torch.empty(device_bytes, dtype=torch.uint8, device=self.device)
         dbuf[:buf.numel()].copy_(buf, non_blocking=True)
-        frames = frames_u8.to(dev, non_blocking=True)
-
-        def part(name, dtype):
-            a, b, shape = spans[name]
-            return dbuf[a:b].view(dtype).view(shape)
-
-        im = part("im_id", torch.int32)
-        out = self.preprocess(frames, part("bytes", torch.uint8), part("byte_offsets", torch.int32), part("counts", torch.int32),
-                              part("offsets", torch.int32), part("boxes", torch.int64), im, in_place=True)
-        tar_K = part("K", torch.float32).index_select(0, im.long())        # data.K[idx_selected].float() (train.py:102)
-        batch = PandasTensorCollection(infos=frame, tar_img=out["tar_img"], tar_mask=out["tar_mask"], tar_K=tar_K, tar_M=out["tar_M"])
-        batch.test_list = test_list
-        return batch
+        return self._finish(dbuf, spans, frame, frames_u8.to(self.device, non_blocking=True), test_list)

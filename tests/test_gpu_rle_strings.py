@@ -145,6 +145,32 @@ def test_noise_mask_of_150k_tokens_straddles_every_chunk_of_both_passes():
     assert len(strings[1]) < 2 * len(noise)                         # about one character per run: a quarter of the int32 list
 
 
+def test_uncompressed_lists_get_the_same_cum_and_flag_from_both_scans_at_the_chunk_and_thread_boundaries():
+    """The same uncompressed lists through gpi_rle_scan and through gps_rle_string_scan with an empty byte slice for every
+    detection, one launch per route: the shared scan (csrc/gp_rle_scan.h) at lengths that straddle its 1024-count chunk and its
+    4-count thread, and a bad list (total H*W + 1) that both routes flag and mark."""
+    H, W = 48, 64
+    HW = H * W
+    lengths = [1, 4, 1023, 1024, 1025, 2048, 2049]
+    lists = [[1] * (L - 1) + [HW - (L - 1)] for L in lengths]
+    lists.append([1] * 1024 + [HW + 1 - 1024])                       # 1025 counts that sum to H*W + 1
+    bad = len(lists) - 1
+    assert all(sum(c) == HW for c in lists[:bad]) and sum(lists[bad]) == HW + 1 and len(lists[bad]) == 1025
+    data, byte_offsets, counts, offsets = layout([np.asarray(c) for c in lists])
+    assert len(data) == 0 and not byte_offsets.any()
+    flag, got_counts, got_cum = string_scan(data, byte_offsets, counts, offsets, H, W)
+    ref_flag, ref_cum, ref_offsets = list_scan(lists, H, W)
+    np.testing.assert_array_equal(offsets, ref_offsets)
+    assert flag == ref_flag == bad + 1
+    np.testing.assert_array_equal(got_counts, counts)                # a list's slots are read, not written
+    got_cum = got_cum.cpu().numpy()
+    assert got_cum.dtype == ref_cum.dtype == np.int32
+    np.testing.assert_array_equal(got_cum, ref_cum)
+    assert got_cum[offsets[bad + 1] - 1] == -1 and ref_cum[offsets[bad + 1] - 1] == -1
+    for d, c in enumerate(lists[:bad]):                              # and the valid ones are the prefix sums
+        np.testing.assert_array_equal(ref_cum[offsets[d]:offsets[d + 1]], np.cumsum(c), err_msg=f"detection {d}")
+
+
 def test_mixed_batch_of_strings_and_lists_in_one_launch():
     from gigapose_amd import ingest
 

@@ -11,6 +11,7 @@ import pytest
 
 from gigapose_amd import ingest
 from gigapose_testing import synthetic as syn
+from gigapose_testing.symbols import exported_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,11 +142,6 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(gpi_[a-z0-9_]+)\s*\(", src)))
 
 
-def exported_symbols(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TDBW")
-
-
 def test_ingest_library_exports_exactly_its_header_and_no_product_symbol():
     names = declared_symbols()
     assert names == ["gpi_abi_version", "gpi_last_error", "gpi_preprocess_detections_rle", "gpi_rle_decode", "gpi_rle_scan"]
@@ -156,6 +152,20 @@ def test_ingest_library_exports_exactly_its_header_and_no_product_symbol():
     for n in names:
         assert hasattr(lib, n)
     assert lib.gpi_abi_version() >= 1
+
+
+def test_a_side_library_that_is_not_built_is_an_error_that_names_the_file_and_the_build_command():
+    from gigapose_amd import _lib
+
+    missing = _lib.SideLibrary("libgigapose_nowhere.so", "gpx")
+    assert missing.path == os.path.join(os.path.dirname(ingest.INGEST_LIB_PATH), "libgigapose_nowhere.so")
+    for use in (missing.lib, lambda: missing.call("gpx_abi_version")):
+        with pytest.raises(_lib.GigaPoseHipError) as e:
+            use()
+        assert str(e.value) == (f"{missing.path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                                "(there is deliberately no CPU / PyTorch fallback)")
+    assert list(_lib.chunked(5, 2)) == [(0, 0, 2), (1, 2, 4), (2, 4, 5)] and list(_lib.chunked(0, 2)) == []
+    assert _lib.first_bad([0, 3, 1], 10) == 12 and _lib.first_bad([0, 0], 10) is None
 
 
 def test_the_two_existing_libraries_carry_no_ingest_symbol():

@@ -12,6 +12,7 @@ import pytest
 
 from gigapose_amd import _lib, ingest, onboard, render
 from gigapose_testing import meshes, raster_ref
+from gigapose_testing.symbols import exported_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,11 +22,6 @@ def declared_symbols():
     src = open(os.path.join(ROOT, "include", "gigapose_render.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(gpr_[a-z0-9_]+)\s*\(", src)))
-
-
-def exported_symbols(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TDBW")
 
 
 def test_render_library_exports_exactly_its_header_and_no_symbol_of_the_other_libraries():

@@ -4,7 +4,6 @@ a numpy model of the kernel's two passes, and libgigapose_rlestr.so against incl
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 from gigapose_amd import ingest
 from gigapose_amd import rle_strings as rs
 from gigapose_testing import rle_string_ref as ref
+from gigapose_testing.symbols import exported_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -203,11 +203,6 @@ def declared_symbols():
     src = open(os.path.join(ROOT, "include", "gigapose_rlestr.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(gps_[a-z0-9_]+)\s*\(", src)))
-
-
-def exported_symbols(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TDBW")
 
 
 def test_rlestr_library_exports_exactly_its_header_and_no_other_librarys_symbol():
