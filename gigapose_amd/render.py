@@ -13,7 +13,8 @@ gigapose_testing/raster_ref.py; tests/test_gpu_render.py holds the kernels to it
   template_object_poses(poses, zoom)    a copy with the translation scaled (render_bop_templates.py:69-70)
   MeshTemplates                         drop-in for model.template_datasets[name], beside onboard.RenderedTemplates
   save_renders(out_dir, rgba, depth)    {view:06d}.png + {view:06d}_depth.png, the reference's layout; onboard.load_renders reads it
-Out of scope: textures (YCB-V, HB), shading other than ambient, near-plane clipping (a triangle with a vertex behind znear is
+Textured models (YCB-V, HB) are drawn by texture.py (libgigapose_texture.so), which takes gpr_project's and gpr_raster's output and
+resolves it through a mip-mapped texture; this module stays with vertex colours.  Out of scope here: shading other than ambient, near-plane clipping (a triangle with a vertex behind znear is
 dropped and counted), anti-aliasing, big-endian PLY, generating the icosphere poses (the caller passes them).  There is no CPU
 fallback: the kernels need the GPU, a missing library is an error.
 """

@@ -1,0 +1,298 @@
+"""Templates from a TEXTURED CAD model (YCB-V, HB: PLY files with texture_u / texture_v per vertex and `comment TextureFile
+obj_0000NN.png`, no usable vertex colours): mesh + per-corner UVs + one texture image + object poses -> the RGBA renders and depth
+maps the reference gets from Panda3D with mip-mapped texture filtering (src/megapose/panda3d_renderer/
+panda3d_scene_renderer.py:70-71), drawn ON the GPU.  render.py's gpr_project and gpr_raster give the visibility keys;
+libgigapose_texture.so (C-ABI: include/gigapose_texture.h) builds the mip pyramid (gpt_build_mips) and turns the keys into
+colours with perspective-correct UVs, an analytic level of detail and trilinear, repeat-wrapped sampling (gpt_resolve).  The
+arithmetic is written out in the header and restated in numpy in gigapose_testing/texture_ref.py; tests/test_gpu_texture.py
+holds the kernels to it bit for bit.
+
+  load_textured_ply(path)     PLY -> {"vertices", "faces", "colours" | None, "corner_uv" f32 (F,3,2), "texture_file" | None}
+  load_texture(path)          any PIL-readable image -> rgb u8 (Ht,Wt,3)
+  corner_uv_from_vertices     per-vertex UVs (V,2) + faces -> per-corner UVs (F,3,2)
+  build_mips / resolve_textured  thin wrappers of the two entry points
+  TexturedMeshRenderer        mesh + UVs + texture + poses on the device -> {"rgba", "depth", "clipped"}
+  TexturedMeshTemplates       drop-in for model.template_datasets[name], beside render.MeshTemplates
+Vertex colours are IGNORED when a texture is given (BOP's textured models carry none).  Out of scope: anisotropic filtering,
+several textures per model (a `texnumber` other than 0 is an error), vertex colour x texture modulation, OBJ / MTL files, and as in
+render.py near-plane clipping, shading other than ambient and anti-aliasing.  There is no CPU fallback.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pandas as pd
+import torch
+
+from . import _lib, render
+from .onboard import TEMPLATE_K, TemplateOnboarder
+from .render import _on_device
+from .tensor_collection import PandasTensorCollection
+
+MAX_TEXTURE = 16384                                 # gigapose_texture.h: GPT_MAX_TEXTURE
+MAX_UV = 32768.0                                    # gigapose_texture.h: GPT_MAX_UV
+_texture = _lib.SideLibrary("libgigapose_texture.so", "gpt", {"gpt_mip_texels": ctypes.c_size_t})
+TEXTURE_LIB_PATH, lib, _call = _texture.path, _texture.lib, _texture.call
+
+
+def mip_levels(Ht, Wt):
+    return int(lib().gpt_mip_levels(_lib.i(Ht), _lib.i(Wt)))
+
+
+def mip_texels(Ht, Wt):
+    return int(lib().gpt_mip_texels(_lib.i(Ht), _lib.i(Wt)))
+
+
+# ------------------------------------------------------------------------------------------------ loaders
+_UV_NAMES = (("texture_u", "texture_v"), ("u", "v"), ("s", "t"))
+
+
+def corner_uv_from_vertices(vertex_uv, faces):
+    """Per-vertex UVs (V,2) gathered through the faces (F,3) -> per-corner UVs f32 (F,3,2)."""
+    uv = np.asarray(vertex_uv, np.float32).reshape(-1, 2)
+    return np.ascontiguousarray(uv[np.asarray(faces, np.int64).reshape(-1, 3)])
+
+
+def load_textured_ply(path):
+    """-> dict: vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3) | None (all three as render.load_ply returns them),
+    corner_uv f32 (F,3,2), texture_file (the name after `comment TextureFile`, as written) | None.  UVs come from the per-face
+    list `texcoord` (six floats: u, v of the three corners) when the file has one, else from the per-vertex pair texture_u /
+    texture_v (also u / v, s / t) gathered through the faces.  ValueError: no UVs at all, a texcoord list that does not hold six
+    values, a `texnumber` other than 0 (several textures per model are out of scope), and whatever load_ply rejects."""
+    path = os.fspath(path)
+    vertices, faces, colours = render.load_ply(path)
+    with open(path, "rb") as fh:
+        data = fh.read()
+    fmt, elements, pos = render._ply_header(data, path)
+    texture_file = None
+    for ln in data[:pos].decode("ascii", "replace").splitlines():
+        w = ln.split(None, 2)
+        if len(w) == 3 and w[0] == "comment" and w[1] == "TextureFile":
+            texture_file = w[2].strip()
+    tokens = None
+    if fmt == "ascii":
+        tokens, pos = data[pos:].split(), 0
+    got = {}
+    for name, count, props in elements:
+        got[name], pos = render._read_element(fmt, props, count, data, pos, tokens, path, name)
+    face = got.get("face", {})
+    if "texnumber" in face and len(faces) and np.any(np.asarray(face["texnumber"]) != 0):
+        raise ValueError(f"load_textured_ply: {path}: a face has texnumber != 0: several textures per model are out of scope")
+    corner_uv = None
+    if "texcoord" in face:
+        rows = face["texcoord"]
+        if isinstance(rows, list):
+            if any(len(r) != 6 for r in rows):
+                raise ValueError(f"load_textured_ply: {path}: a texcoord list does not hold six values (u, v of three corners)")
+            rows = np.asarray(rows, np.float32).reshape(-1, 6)
+        if rows.ndim != 2 or (len(rows) and rows.shape[1] != 6) or len(rows) != len(faces):
+            raise ValueError(f"load_textured_ply: {path}: a texcoord list does not hold six values (u, v of three corners)")
+        corner_uv = np.ascontiguousarray(np.asarray(rows, np.float32).reshape(-1, 3, 2))
+    else:
+        vert = got["vertex"]
+        pair = next((p for p in _UV_NAMES if p[0] in vert and p[1] in vert), None)
+        if pair is None:
+            raise ValueError(f"load_textured_ply: {path}: the file has no texture coordinates (texture_u / texture_v, u / v or s / t "
+                             "per vertex, or a texcoord list per face)")
+        corner_uv = corner_uv_from_vertices(np.stack([np.asarray(vert[pair[0]], np.float32), np.asarray(vert[pair[1]], np.float32)], axis=1), faces)
+    return dict(vertices=vertices, faces=faces, colours=colours, corner_uv=corner_uv, texture_file=texture_file)
+
+
+def load_texture(path):
+    """Any PIL-readable image -> rgb u8 (Ht,Wt,3): alpha is dropped, grey and palette images are expanded.  ValueError: a 16-bit
+    or float image (mode I;16, I, F), or a side beyond 16384."""
+    from PIL import Image
+
+    with Image.open(os.fspath(path)) as im:
+        if im.mode.startswith("I") or im.mode == "F":
+            raise ValueError(f"load_texture: {path}: mode {im.mode} (16-bit or float samples) is not supported: convert to 8 bits")
+        rgb = np.array(im.convert("RGB"), dtype=np.uint8, order="C")
+    _check_texture_shape(rgb.shape, "load_texture")
+    return rgb
+
+
+def _check_texture_shape(shape, who):
+    if len(shape) != 3 or shape[2] != 3 or not (1 <= shape[0] <= MAX_TEXTURE and 1 <= shape[1] <= MAX_TEXTURE):
+        raise ValueError(f"{who}: expected a texture (Ht, Wt, 3) with 1 <= Ht, Wt <= {MAX_TEXTURE}, got {tuple(shape)}")
+
+
+# ------------------------------------------------------------------------------------------------ the two entry points
+@torch.no_grad()
+def build_mips(rgb):
+    """gpt_build_mips: rgb u8 (Ht,Wt,3) on the device -> the pyramid, int32 (gpt_mip_texels(Ht, Wt),), holding the 32-bit texels
+    R | G << 8 | B << 16 | 0xff << 24 of every level, level 0 first."""
+    rgb = _on_device(rgb, torch.uint8, (None, None, 3), "build_mips", "texture")
+    _check_texture_shape(rgb.shape, "build_mips")
+    Ht, Wt = rgb.shape[:2]
+    pyramid = torch.empty(mip_texels(Ht, Wt), dtype=torch.int32, device=rgb.device)
+    _call("gpt_build_mips", _lib.ptr(rgb), _lib.i(Ht), _lib.i(Wt), _lib.ptr(pyramid), _lib.stream_ptr())
+    return pyramid
+
+
+@torch.no_grad()
+def resolve_textured(vis, xy, vdepth, faces, corner_uv, pyramid, size, out=None):
+    """gpt_resolve: the keys of render.raster + corner_uv f32 (F,3,2) + the pyramid of a size = (Ht, Wt) texture -> rgba u8
+    (N,H,W,4), depth f32 (N,H,W); `out` = (rgba, depth) are buffers to write into."""
+    who = "resolve_textured"
+    vis = _on_device(vis, torch.int64, (None, None, None), who, "vis")
+    N, H, W = vis.shape
+    xy = _on_device(xy, torch.int32, (N, None, 2), who, "xy")
+    V = xy.shape[1]
+    vdepth = _on_device(vdepth, torch.float32, (N, V), who, "vdepth")
+    faces = _on_device(faces, torch.int32, (None, 3), who, "faces")
+    F = faces.shape[0]
+    corner_uv = _on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
+    Ht, Wt = int(size[0]), int(size[1])
+    _check_texture_shape((Ht, Wt, 3), who)
+    pyramid = _on_device(pyramid, torch.int32, (mip_texels(Ht, Wt),), who, "pyramid")
+    rgba, depth = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=vis.device),
+                                               torch.empty(N, H, W, dtype=torch.float32, device=vis.device))
+    if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W):
+        raise ValueError(f"{who}: out must be rgba (N,H,W,4) and depth (N,H,W)")
+    _call("gpt_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(corner_uv),
+          _lib.ptr(pyramid), _lib.i(Ht), _lib.i(Wt), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.stream_ptr())
+    return rgba, depth
+
+
+# ------------------------------------------------------------------------------------------------ the renderer
+class TexturedMeshRenderer:
+    """vertices f32 (V,3), faces int32 (F,3), corner_uv f32 (F,3,2), texture, poses f32 (N,4,4), all on the device -> rgba u8
+    (N,H,W,4), depth f32 (N,H,W), clipped int32 (N,), as render.MeshRenderer returns them (same poses, K, pixel centres, znear).
+    texture: rgb u8 (Ht,Wt,3), of which the pyramid is built once per call, or a pyramid built before, as (pyramid, (Ht, Wt)).
+    The colour is the filtered texel alone: vertex colours are not an input."""
+
+    def __init__(self, H=480, W=640, K=TEMPLATE_K, znear=1e-3):
+        self.H, self.W, self.znear = int(H), int(W), float(znear)
+        self._K = render._k9(K)
+
+    @torch.no_grad()
+    def __call__(self, vertices, faces, corner_uv, texture, poses, views_per_call=None, on_clipped="raise"):
+        """Chunking, the clipped-view error and the one host synchronisation are MeshRenderer's."""
+        who = "TexturedMeshRenderer"
+        if on_clipped not in ("raise", "ignore"):
+            raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
+        vertices = _on_device(vertices, torch.float32, (None, 3), who, "vertices")
+        faces = _on_device(faces, torch.int32, (None, 3), who, "faces")
+        V, F = vertices.shape[0], faces.shape[0]
+        corner_uv = _on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
+        if isinstance(texture, (tuple, list)):
+            pyramid, size = texture
+            size = (int(size[0]), int(size[1]))
+            _check_texture_shape(size + (3,), who)
+            pyramid = _on_device(pyramid, torch.int32, (mip_texels(*size),), who, "pyramid")
+        else:
+            texture = _on_device(texture, torch.uint8, (None, None, 3), who, "texture")
+            _check_texture_shape(texture.shape, who)
+            pyramid, size = None, tuple(texture.shape[:2])
+        poses = _on_device(poses, torch.float32, (None, 4, 4), who, "poses")
+        N, dev = poses.shape[0], vertices.device
+        if pyramid is None:
+            pyramid = build_mips(texture)
+        H, W = self.H, self.W
+        if views_per_call is None:
+            views_per_call = max(1, render.VIS_BYTES_PER_CALL // (H * W * 8))
+        step = max(1, min(int(views_per_call), render.MAX_VIEWS_PER_CALL))
+        rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
+        depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+        clipped = torch.empty(N, dtype=torch.int32, device=dev)
+        n = min(N, step)
+        xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
+        vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
+        vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
+        work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
+        for _, a, b in _lib.chunked(N, step):
+            pxy, pz = render.project(vertices, poses[a:b], self._K, self.znear, out=(xy, vdepth))
+            keys, _ = render.raster(pxy, pz, faces, H, W, out=(vis, clipped[a:b]), workspace=work)
+            resolve_textured(keys, pxy, pz, faces, corner_uv, pyramid, size, out=(rgba[a:b], depth[a:b]))
+        if on_clipped == "raise":
+            bad = torch.nonzero(clipped).flatten().tolist()
+            if bad:
+                raise ValueError(f"{who}: view {bad[0]} drops {int(clipped[bad[0]])} of {F} triangles: a vertex lies behind znear = {self.znear}, "
+                                 f"beyond 16384 px or is not finite (views {bad[:8]}{' ...' if len(bad) > 8 else ''}; there is no "
+                                 "near-plane clipping -- on_clipped='ignore' renders what is left)")
+        return {"rgba": rgba, "depth": depth, "clipped": clipped}
+
+
+def _host(a, dtype):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return torch.from_numpy(np.array(a, dtype=dtype, order="C"))          # a copy: PIL hands out read-only arrays
+
+
+def _host_textured_mesh(mesh, texture, who):
+    """-> vertices, faces, corner_uv, texture as host tensors."""
+    base = None
+    if isinstance(mesh, (str, os.PathLike)):
+        base = os.path.dirname(os.path.abspath(os.fspath(mesh)))
+        mesh = load_textured_ply(mesh)
+    if not isinstance(mesh, dict) or not all(k in mesh for k in ("vertices", "faces", "corner_uv")):
+        raise ValueError(f"{who}: the mesh must be a PLY path or a dict with vertices, faces and corner_uv")
+    v, f, uv = _host(mesh["vertices"], np.float32), _host(mesh["faces"], np.int32), _host(mesh["corner_uv"], np.float32)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or tuple(uv.shape) != (f.shape[0], 3, 2):
+        raise ValueError(f"{who}: expected vertices (V,3), faces (F,3), corner_uv (F,3,2), got {tuple(v.shape)}, {tuple(f.shape)}, {tuple(uv.shape)}")
+    if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
+        raise ValueError(f"{who}: a face index is outside [0, {len(v)})")
+    if texture is None:
+        name = mesh.get("texture_file")
+        if name is None:
+            raise ValueError(f"{who}: no texture given and the mesh names none (`comment TextureFile` in the PLY)")
+        texture = name if base is None or os.path.isabs(name) else os.path.join(base, name)
+    if isinstance(texture, (str, os.PathLike)):
+        texture = load_texture(texture)
+    t = _host(texture, np.uint8)
+    _check_texture_shape(t.shape, who)
+    return v, f, uv, t
+
+
+class TexturedMeshTemplates:
+    """Drop-in for `model.template_datasets[name]`, beside render.MeshTemplates: item i is the same PandasTensorCollection, .rgb
+    (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3) .poses (N,4,4) on the device.
+
+    objects: list of (mesh, texture, poses) -- mesh a PLY path or a dict as load_textured_ply returns it; texture a path, an
+    rgb array (Ht,Wt,3) or None to take the mesh's `texture_file` next to the PLY; poses (N,4,4) as for MeshTemplates.  Meshes
+    and textures stay on the HOST; every __getitem__ uploads them, builds the pyramid, renders the N views on the device and hands
+    the device renders to TemplateOnboarder: no render crosses PCIe.  Vertex colours in the mesh are ignored."""
+
+    def __init__(self, objects, K=None, device="cuda", target_size=224, H=480, W=640, znear=1e-3):
+        self.device = torch.device(device)
+        K = np.asarray(TEMPLATE_K if K is None else K, dtype=np.float32).reshape(3, 3)
+        self.K = torch.as_tensor(K)
+        self.renderer = TexturedMeshRenderer(H, W, K, znear)
+        self.onboard = TemplateOnboarder(target_size)
+        self._meshes, self._poses = [], []
+        for o, obj in enumerate(objects):
+            if len(obj) != 3:
+                raise ValueError(f"TexturedMeshTemplates: object {o}: expected (mesh, texture, poses)")
+            mesh, texture, poses = obj
+            m = _host_textured_mesh(mesh, texture, f"TexturedMeshTemplates: object {o}")
+            if isinstance(poses, torch.Tensor):
+                poses = poses.detach().cpu().numpy()
+            p = torch.as_tensor(np.asarray(poses, dtype=np.float32))
+            if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
+                raise ValueError(f"TexturedMeshTemplates: object {o}: expected poses (N, 4, 4), got {tuple(p.shape)}")
+            self._meshes.append(m)
+            self._poses.append(p)
+
+    def __len__(self):
+        return len(self._meshes)
+
+    @torch.no_grad()
+    def render(self, i):
+        """The device renders of object i: {"rgba", "depth", "clipped"}."""
+        if self.device.type != "cuda":
+            raise _lib.GigaPoseHipError("TexturedMeshTemplates needs a GPU device (no CPU fallback)")
+        v, f, uv, t = (a.to(self.device) for a in self._meshes[i])
+        try:
+            return self.renderer(v, f, uv, t, self._poses[i].to(self.device))
+        except ValueError as e:
+            raise ValueError(f"TexturedMeshTemplates: object {i}: {e}") from None
+
+    @torch.no_grad()
+    def __getitem__(self, i):
+        rgba = self.render(i)["rgba"]
+        try:
+            out = self.onboard(rgba)
+        except ValueError as e:
+            raise ValueError(f"TexturedMeshTemplates: object {i}: {e}") from None
+        return PandasTensorCollection(infos=pd.DataFrame(), K=self.K.to(self.device), rgb=out["rgb"], mask=out["mask"], M=out["M"],
+                                      poses=self._poses[i].to(self.device))

@@ -1,5 +1,6 @@
 """Deterministic test meshes for the renderer (gigapose_amd/render.py, gigapose_testing/raster_ref.py): vertices f32 (V,3), faces
-int32 (F,3), colours u8 (V,3).  Nothing here is random unless a seed is passed."""
+int32 (F,3), colours u8 (V,3); and their UV-mapped variants for the textured renderer (gigapose_amd/texture.py,
+gigapose_testing/texture_ref.py): vertices, faces, corner_uv f32 (F,3,2).  Nothing here is random unless a seed is passed."""
 import numpy as np
 
 
@@ -83,6 +84,59 @@ def convex_polygon(n=7, radius=1.0, z=0.0):
     f = np.asarray([(0, i, i + 1) for i in range(1, n - 1)], np.int32)
     c = np.stack([np.rint(127.5 + 127.5 * np.cos(a)), np.rint(127.5 + 127.5 * np.sin(a)), np.full(n, 128.0)], axis=1).astype(np.uint8)
     return v, f, c
+
+
+# ------------------------------------------------------------------------------------------------ UV-mapped shapes
+def uv_quad(size=(1.0, 1.0), z=0.0, uv_min=(0.0, 0.0), uv_max=(1.0, 1.0)):
+    """A rectangle in the plane z = const, two triangles.  Seen with the identity rotation (x right, y down) the texture stands
+    upright: the vertex at (-w/2, -h/2), the top-left of the image, carries (u_min, v_max).  uv_min / uv_max beyond [0, 1] repeat
+    the texture."""
+    w, h = size[0] / 2.0, size[1] / 2.0
+    (u0, v0), (u1, v1) = uv_min, uv_max
+    v = np.asarray([(-w, -h, z), (w, -h, z), (w, h, z), (-w, h, z)], np.float32)
+    uv = np.asarray([(u0, v1), (u1, v1), (u1, v0), (u0, v0)], np.float32)
+    f = np.asarray([(0, 1, 2), (0, 2, 3)], np.int32)
+    return v, f, uv[f]
+
+
+BOX_ATLAS = {"-z": (0, 0), "+z": (1, 0), "-y": (2, 0), "+y": (3, 0), "-x": (0, 1), "+x": (1, 1)}     # cell (column, row) of 4 x 2, row 0 = v < 1/2
+
+
+def uv_box(size=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), shared=True):
+    """box() with an atlas: face `name` fills cell BOX_ATLAS[name] of a 4 x 2 grid (so -z, +z lie in the texture's bottom-left
+    quadrant, -y, +y in the bottom-right one, -x, +x in the top-left one; the top-right quadrant is unused).  shared=True: the 8
+    corners are the vertices, so every vertex carries three different UVs -- seams that only per-corner UVs can express.
+    shared=False: 24 vertices, one UV each (corner_uv is then vertex_uv[faces]).  Same faces in the same order either way."""
+    s, c = np.asarray(size, np.float64) / 2, np.asarray(centre, np.float64)
+    corners = np.asarray([(-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1), (-1, -1, 1), (1, -1, 1), (1, 1, 1), (-1, 1, 1)], np.float64) * s + c
+    v, f, uv = [], [], []
+    for quad, name in _BOX_FACES:
+        cx, cy = BOX_ATLAS[name]
+        cell = [((cx + a) / 4.0, (cy + b) / 2.0) for a, b in ((0, 0), (1, 0), (1, 1), (0, 1))]
+        if shared:
+            idx = list(quad)
+        else:
+            idx = list(range(len(v), len(v) + 4))
+            v += [corners[i] for i in quad]
+        for tri in ((0, 1, 2), (0, 2, 3)):
+            f.append([idx[k] for k in tri])
+            uv.append([cell[k] for k in tri])
+    v = corners if shared else np.asarray(v)
+    return v.astype(np.float32), np.asarray(f, np.int32), np.asarray(uv, np.float32)
+
+
+def uv_icosphere(level=2, radius=1.0):
+    """icosphere() with a longitude / latitude map: u = longitude / 2 pi + 1/2, v = latitude / pi + 1/2.  A face that straddles
+    the date line gets 1 added to its corners' u on the low side, so its UVs run beyond 1: per-corner, and repeat wrapping."""
+    v, f, _ = icosphere(level, 1.0)
+    d = v.astype(np.float64)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    u = np.arctan2(d[:, 1], d[:, 0]) / (2 * np.pi) + 0.5
+    w = np.arcsin(np.clip(d[:, 2], -1, 1)) / np.pi + 0.5
+    cu, cw = u[f], w[f]
+    wide = (cu.max(axis=1) - cu.min(axis=1)) > 0.5
+    cu = np.where(wide[:, None] & (cu < 0.5), cu + 1.0, cu)
+    return (v * np.float32(radius)).astype(np.float32), f, np.stack([cu, cw], axis=2).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ polygons in screen coordinates
