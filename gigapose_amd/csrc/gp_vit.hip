@@ -66,28 +66,7 @@ __global__ __launch_bounds__(320) void embed_kernel(const float* __restrict__ pe
     X[(size_t)c * Mpad + (size_t)b * T_TOK + t] = v;
 }
 
-// ---- LayerNorm over C of channel-major X [C][Mpad]; thread = token column (coalesced)
-__global__ __launch_bounds__(128) void layernorm_kernel(const float* __restrict__ X, float* __restrict__ Y,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, int C, int Mpad,
-                                                         float eps)
-{
-    const int m = blockIdx.x * 128 + threadIdx.x;
-    const float* x = X + m;
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += x[(size_t)c * Mpad];
-    const float mean = s / (float)C;
-    float v = 0.f;
-    for (int c = 0; c < C; ++c) {
-        const float d = x[(size_t)c * Mpad] - mean;
-        v = __builtin_fmaf(d, d, v);
-    }
-    const float rstd = 1.0f / __builtin_sqrtf(v / (float)C + eps);
-    for (int c = 0; c < C; ++c)
-        Y[(size_t)c * Mpad + m] = (x[(size_t)c * Mpad] - mean) * rstd * gamma[c] + beta[c];
-}
-
-// ---- LayerNorm, wide: block = 64 token columns x 16 channel slices (16 waves, 4128 waves in flight at
+// ---- LayerNorm over C of channel-major X [C][Mpad], wide: block = 64 token columns x 16 channel slices (16 waves, 4128 waves in flight at
 // B=64 instead of 258), three short passes; the block's 64 x C tile is re-read from L2.
 __global__ __launch_bounds__(1024) void layernorm_wide_kernel(const float* __restrict__ X, float* __restrict__ Y,
                                                                const float* __restrict__ gamma,
@@ -129,11 +108,9 @@ __global__ __launch_bounds__(1024) void layernorm_wide_kernel(const float* __res
 int launch_layernorm(const float* X, float* Y, const float* g, const float* b, int C, int Mpad, float eps,
                      hipStream_t st)
 {
+    // C % 16 == 0 (16 channel slices) and Mpad % 64 == 0: gp_vit_forward requires dim % 128 == 0 and Mpad is a multiple of 256
     GpProfScope prof(GP_PROF_LN, 8.0 * C * Mpad, st);
-    if (C % 16 == 0)
-        hipLaunchKernelGGL(layernorm_wide_kernel, dim3(Mpad / 64), dim3(1024), 0, st, X, Y, g, b, C, Mpad, eps);
-    else
-        hipLaunchKernelGGL(layernorm_kernel, dim3(Mpad / 128), dim3(128), 0, st, X, Y, g, b, C, Mpad, eps);
+    hipLaunchKernelGGL(layernorm_wide_kernel, dim3(Mpad / 64), dim3(1024), 0, st, X, Y, g, b, C, Mpad, eps);
     return 0;
 }
 
@@ -457,6 +434,14 @@ __global__ __launch_bounds__(64, 4) void attention_kernel(const float* __restric
     const float* Vp = Vt + (size_t)b * T_TOK * C + h * 64;
     float* Op = O + (size_t)(h * 64) * Mpad + (size_t)b * T_TOK;
     attention_body(Qp, Kp, Vp, Op, qb * 32, C, Mpad, scale);
+}
+
+// QK [2C][Mpad] (Q rows h*64+d, K rows C+h*64+d), Vt [Mpad][C] -> O [C][Mpad]; columns b*257+t.  0.125 = 64^-0.5, exact.
+int launch_attention_f32(const float* QK, const float* Vt, float* O, int B, int heads, int C, int Mpad, hipStream_t st)
+{
+    GpProfScope prof(GP_PROF_ATTN, 4.0 * B * heads * 257.0 * 257.0 * 64.0, st);
+    hipLaunchKernelGGL(attention_kernel, dim3(xcd_chunked_grid(B * heads * NKT)), dim3(64), 0, st, QK, Vt, O, B, heads, C, Mpad, 0.125f);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -862,6 +847,14 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
     for (int c = c0; c < c1; ++c) o[(size_t)c * GP_P] = normalize ? x[(size_t)c * Mpad] / d : x[(size_t)c * Mpad];
 }
 
+// one block per (crop, channel chunk): 32 chunks below 16 crops, 16 below 64, 4 from there on (see features_kernel)
+int launch_features(const float* X, float* out, int B, int C, int Mpad, int normalize, hipStream_t st)
+{
+    hipLaunchKernelGGL(features_kernel, dim3(B, B >= 64 ? 4 : (B >= 16 ? 16 : 32)), dim3(256), 0, st, X, out, C, Mpad, normalize,
+                       gp_status_buffer());
+    return 0;
+}
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 }  // namespace
@@ -918,6 +911,35 @@ int gp_layernorm_planes(const float* X, void* out_hi, void* out_lo, const float*
     GP_CHECK_LAUNCH("gp_layernorm_planes");
     return GP_OK;
 }
+
+#ifdef GP_PROBES
+/* stage entries of the f32 kernels the forward runs off the plane path (include/gigapose_hip_probe.h; tests/test_gpu_vit_f32_stages.py):
+ * each goes through the launcher the forward uses. */
+int gp_vit_attention_f32(const float* qk, const float* vt, float* out, int B, int heads, int dim, int Mpad, void* stream)
+{
+    GP_REQUIRE(qk && vt && out && B > 0 && heads > 0 && dim == heads * 64 && Mpad > 0 && Mpad % 256 == 0 && (long long)Mpad >= (long long)B * T_TOK,
+               "gp_vit_attention_f32: bad arguments");
+    launch_attention_f32(qk, vt, out, B, heads, dim, Mpad, (hipStream_t)stream);
+    GP_CHECK_LAUNCH("gp_vit_attention_f32");
+    return GP_OK;
+}
+
+int gp_vit_layernorm_f32(const float* X, float* Y, const float* gamma, const float* beta, int C, int Mpad, float eps, void* stream)
+{
+    GP_REQUIRE(X && Y && gamma && beta && C > 0 && C % 16 == 0 && Mpad > 0 && Mpad % 64 == 0, "gp_vit_layernorm_f32: bad arguments");
+    launch_layernorm(X, Y, gamma, beta, C, Mpad, eps, (hipStream_t)stream);
+    GP_CHECK_LAUNCH("gp_vit_layernorm_f32");
+    return GP_OK;
+}
+
+int gp_vit_features(const float* X, float* out, int B, int C, int Mpad, int normalize, void* stream)
+{
+    GP_REQUIRE(X && out && B > 0 && C > 0 && Mpad > 0 && (long long)Mpad >= (long long)B * T_TOK, "gp_vit_features: bad arguments");
+    launch_features(X, out, B, C, Mpad, normalize, (hipStream_t)stream);
+    GP_CHECK_LAUNCH("gp_vit_features");
+    return GP_OK;
+}
+#endif
 
 int gp_vit_forward(const float* images, int B, int dim, int depth, int heads, int mlp_dim, float ln_eps,
                    const float* const* weights, int n_weights, float* workspace, size_t workspace_bytes,
@@ -1085,11 +1107,7 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
         if (sp) rc = sgemm(Hn, Mpad, S_V_HI, Vt, C, Mpad, C, C, 0, 4 /*BIAS_J*/, w[L_V_B], nullptr, nullptr, 0);
         else rc = gp_gemm_launch(Hn, Mpad, w[L_V_WT], C, Vt, C, Mpad, C, C, 4 /*BIAS_J*/, w[L_V_B], nullptr, nullptr, 0, SK, st);
         if (rc) return rc;
-        {
-            GpProfScope prof(GP_PROF_ATTN, 4.0 * B * heads * 257.0 * 257.0 * 64.0, st);
-            hipLaunchKernelGGL(attention_kernel, dim3(xcd_chunked_grid(B * heads * NKT)), dim3(64), 0, st, QK, Vt, Hn, B, heads, C,
-                               Mpad, 0.125f);
-        }
+        launch_attention_f32(QK, Vt, Hn, B, heads, C, Mpad, st);
         GP_CHECK_LAUNCH("gp_vit_forward/attention");
         // x = x + ls1 * proj(attn)
         if (sp) rc = sgemm(Hn, Mpad, S_PROJ_HI, X, Mpad, C, Mpad, C, 1, 3, w[L_PROJ_B], w[L_LS1], X, Mpad);
@@ -1106,8 +1124,7 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
         else rc = gp_gemm_launch(w[L_FC2_WT], C, F, Mpad, X, Mpad, C, Mpad, mlp_dim, 3, w[L_FC2_B], w[L_LS2], X, Mpad, SK, st);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(features_kernel, dim3(B, B >= 64 ? 4 : (B >= 16 ? 16 : 32)), dim3(256), 0, st, X, out_features, C, Mpad, normalize,
-                       gp_status_buffer());
+    launch_features(X, out_features, B, C, Mpad, normalize, st);
     GP_CHECK_LAUNCH("gp_vit_forward/features");
     return GP_OK;
 }

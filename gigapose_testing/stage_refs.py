@@ -1,5 +1,6 @@
 """Input builders and float64 references of the stage tests of the split path's non-GEMM kernels (tests/test_gpu_layernorm_planes.py,
-test_gpu_ist_split.py, test_gpu_stem_planes.py, test_gpu_plane_producers.py).  numpy / torch on the CPU only: nothing here touches a GPU or
+test_gpu_ist_split.py, test_gpu_stem_planes.py, test_gpu_plane_producers.py) and of the f32 ViT kernels behind the plane path
+(tests/test_gpu_vit_f32_stages.py).  numpy / torch on the CPU only: nothing here touches a GPU or
 the HIP library, and tests/test_stage_refs.py checks every function of this file against torch's own float64 operators without one.
 
 Conventions restated (include/gigapose_hip.h):
@@ -74,6 +75,7 @@ def layernorm_class_columns(Mpad):
              "offset": [16, 31, 63, 128, 191, 1001, Mpad // 2 + 32, Mpad - 3],
              "constant": [32, 47, 192, 255, 256, 1002, Mpad // 2 + 63, Mpad - 2],
              "pad": [Mpad - 8, Mpad - 7, Mpad - 6, Mpad - 5, Mpad - 1]}
+    fixed = {name: [c for c in cc if c < Mpad] for name, cc in fixed.items()}     # Mpad = 512: the columns near 1000 do not exist
     taken = {c for cc in fixed.values() for c in cc}
     for name, r in (("massive", 5), ("offset", 11), ("constant", 17)):
         fixed[name] = fixed[name] + [c for c in range(r, Mpad - 8, 37) if c not in taken]
@@ -405,7 +407,64 @@ def attention_mutant(kind, vals, B, H):
             pc = torch.exp(s[..., a:b] - s[..., a:b].max(-1, keepdim=True).values)
             num, den = num + pc @ v[:, :, a:b], den + pc.sum(-1, keepdim=True)
         return (num / den).permute(0, 2, 1, 3)
+    # ---- bugs attention_body (the f32 kernel: one wave per 32 queries, a lane half per 16 keys of a 32-key tile) could have
+    if kind == "half_denominator":        # l_part without its cross-half share: the denominator holds the keys of lane half 0 only
+        p = torch.exp(q @ k.transpose(-1, -2) * 0.125 - (q @ k.transpose(-1, -2) * 0.125).max(-1, keepdim=True).values)
+        return ((p @ v) / p[..., attention_half_keys(0)].sum(-1, keepdim=True)).permute(0, 2, 1, 3)
+    if kind == "channel_halves_swapped":  # o0 / o1 stored to each other's rows: channels d and 32 + d of a head exchanged
+        return torch.roll(attention_ref(vals, B, H), 32, dims=-1)
+    if kind == "query_256_from_next_crop":   # a crop stride of 256 on the q side of the last query tile: crop b reads crop b + 1's q
+        q = q.clone()
+        q[:, :, 256] = torch.roll(q[:, :, 256], -1, dims=0)
+        return (torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1) @ v).permute(0, 2, 1, 3)
     raise ValueError(kind)
+
+
+ATTN_MUTANTS = ("drop_key_256", "scale_63", "per_chunk_max", "half_denominator", "channel_halves_swapped", "query_256_from_next_crop")
+
+
+def attention_half_keys(half):
+    """The keys whose P registers lane half `half` of attention_body holds: in every 32-key tile rows frag_row(r, lane) =
+    (r & 3) + 8 (r >> 2) + 4 half, r = 0 .. 15 (gp_common.h) -- the keys with (key % 8) // 4 == half; only keys < 257 exist."""
+    return torch.tensor([t for t in range(T_TOK) if (t % 8) // 4 == half])
+
+
+def attention_cm_layout(vals, B, H, Mpad, fill):
+    """[B * 257][3 * 64 H] values of attention_case -> (qk [2 * 64 H][Mpad], vt [Mpad][64 H]) f32 as gp_vit_attention_f32 reads them: Q in
+    rows h * 64 + d, K in rows 64 H + h * 64 + d, column = token b * 257 + t; V token-major.  Pad columns of qk and pad rows of vt = fill."""
+    C, M = 64 * H, B * T_TOK
+    assert vals.shape == (M, 3 * C) and Mpad >= M
+    qk = torch.full((2 * C, Mpad), float(fill), dtype=torch.float32)
+    vt = torch.full((Mpad, C), float(fill), dtype=torch.float32)
+    qk[:, :M] = vals[:, :2 * C].t().float()
+    vt[:M] = vals[:, 2 * C:].float()
+    return qk, vt
+
+
+def attention_cm_values(qk, vt, B, H):
+    """Inverse of attention_cm_layout on the token columns: -> [B * 257][3 * 64 H]."""
+    M = B * T_TOK
+    return torch.cat([qk[:, :M].t(), vt[:M]], dim=1)
+
+
+def attention_cm_output(out, B, H):
+    """out [64 H][Mpad] channel-major (gp_vit_attention_f32) -> [B][257][H][64], the layout of attention_ref."""
+    return out[:, :B * T_TOK].t().reshape(B, T_TOK, H, 64)
+
+
+def attention_cm_from_output(o, Mpad, fill):
+    """Inverse of attention_cm_output: [B][257][H][64] -> [64 H][Mpad] f32, pad columns = fill."""
+    B, _, H, _ = o.shape
+    out = torch.full((64 * H, Mpad), float(fill), dtype=torch.float32)
+    out[:, :B * T_TOK] = o.reshape(B * T_TOK, 64 * H).t().float()
+    return out
+
+
+def attention_bound_f32(e32):
+    """Bound of the f32 kernel (attention_kernel, f32 in and out: no plane term) on max |err| / max |ref|: twice torch's own f32 evaluation
+    of the formula on the same values (another summation order and nothing else), not below 2e-6 -- the floor its f16-plane twin is
+    held to on x 8 planes; the f32 kernel may not be worse."""
+    return max(2.0 * e32, 2e-6)
 
 
 def attention_bound(e32, scale):

@@ -188,7 +188,10 @@ size_t gp_vit_workspace_bytes(int B, int dim, int mlp_dim);
  *                             bfc1, Wfc2^T (mlp, dim), bfc2, ls2
  * stop_after_layers: < 0 = all layers (otherwise run only that many blocks; test hook).
  * After the call the workspace's first dim*Mpad floats hold x_prenorm^T (dim, Mpad),
- * column b*257 + t, Mpad = round_up(257*B, 256). */
+ * column b*257 + t, Mpad = round_up(257*B, 256); columns from 257*B on are +0.0 in the embedding.
+ * The last guard against non-finite features belongs to the normalisation: with normalize != 0 a patch token whose
+ * residual stream holds a NaN / inf (or sum x^2 > 3e38) raises GP_STATUS_SPLIT_RANGE; with normalize == 0 the values
+ * are copied as they are and that guard raises nothing. */
 int gp_vit_forward(const float* images, int B, int dim, int depth, int heads, int mlp_dim, float ln_eps,
                    const float* const* weights, int n_weights, float* workspace, size_t workspace_bytes,
                    float* out_features, int normalize, int stop_after_layers, void* stream);

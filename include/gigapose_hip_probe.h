@@ -53,6 +53,21 @@ void gp_vit_set_ln_reg(int mode); /* plane path's LayerNorm: 1 (default) 32-toke
                                      them; 2 always 32-token blocks; 0 the first-generation three-pass kernel (results identical) */
 void gp_vit_set_planes(int on);   /* split numerics: 1 (default; any value but 0) = activation planes + attention in split numerics where the
                                      shapes allow, 0 = f32 activations and the lock-step kernels */
+/* Stage entries of the f32 kernels gp_vit_forward runs whenever the plane path is not taken (chain numerics, ViT-S, ViT-L below 8 crops,
+ * the fall-back after a range trip); the feature epilogue runs on every forward.  Each launches through the launcher the forward uses
+ * (tests/test_gpu_vit_f32_stages.py; the product library's kernels are tied to these by a bit-exact composition test).
+ * Token b*257 + t is column (row of vt) b*257 + t; Mpad = round_up(257 B, 256) in the forward.
+ *   gp_vit_attention_f32  softmax(q k^T / 8) v per (crop, head), HF modeling_dinov2.py:207-229.  qk [2 dim][Mpad]: Q in rows h*64 + d, K in
+ *                         rows dim + h*64 + d; vt [Mpad][dim]; out [dim][Mpad].  Requires dim == 64 heads, Mpad % 256 == 0, Mpad >= 257 B.
+ *                         Columns / rows from 257 B on are neither read nor written.
+ *   gp_vit_layernorm_f32  LayerNorm over C of X [C][Mpad] -> Y [C][Mpad] (norm1 / norm2, :342-380).  Requires C % 16 == 0, Mpad % 64 == 0.
+ *   gp_vit_features       X [C][Mpad] -> out (B, C, 256): the patch tokens (t >= 1) of every crop, divided by max(|x|_2, 1e-12) over C if
+ *                         normalize != 0 (ae_net.py:64-69).  The class-token column and the pad columns are not read.  The finiteness guard
+ *                         (GP_STATUS_SPLIT_RANGE on a token with a NaN / inf or sum x^2 > 3e38) belongs to the normalisation: with
+ *                         normalize == 0 the values are copied as they are and no bit is raised. */
+int gp_vit_attention_f32(const float* qk, const float* vt, float* out, int B, int heads, int dim, int Mpad, void* stream);
+int gp_vit_layernorm_f32(const float* X, float* Y, const float* gamma, const float* beta, int C, int Mpad, float eps, void* stream);
+int gp_vit_features(const float* X, float* out, int B, int C, int Mpad, int normalize, void* stream);
 
 /* ---- IST convolutions ---- */
 void gp_conv_set_direct(int on);                                  /* 0 = always the generic gather kernel (results identical) */

@@ -63,7 +63,7 @@ def test_f16_ulp():
 
 
 # ---------------------------------------------------------------------------------------------------------------- LayerNorm
-@pytest.mark.parametrize("C,Mpad", [(384, 1024), (1024, 2304), (1280, 1024)])
+@pytest.mark.parametrize("C,Mpad", [(384, 1024), (1024, 2304), (1280, 1024), (128, 512)])
 def test_layernorm_f64_equals_torch_and_the_classes_are_what_they_say(C, Mpad):
     x, cls, gamma, beta = sr.layernorm_case(C, Mpad, 11)
     y, xhat = sr.layernorm_f64(x, gamma, beta, 1e-6)
@@ -296,6 +296,85 @@ def test_attention_preconditions_reject_another_class():
 def test_attention_bound_is_the_stage_bound_for_plain_inputs():
     assert sr.attention_bound(9.0e-7, 8.0) == 2e-6 + 2.0 ** -21 and sr.attention_bound(9.0e-7, 0.5) == 4e-6 + 2.0 ** -21
     assert sr.attention_bound(7.2e-5, 8.0) == 1.44e-4 + 2.0 ** -21
+
+
+# ---------------------------------------------------------------------------------------------------------------- f32 attention
+# (tests/test_gpu_vit_f32_stages.py: attention_kernel reads f32 values, not planes -- the cases are attention_case's own f32 values)
+def test_attention_bound_f32_has_no_plane_term():
+    assert sr.attention_bound_f32(9.0e-7) == 2e-6 and sr.attention_bound_f32(7.2e-5) == 1.44e-4
+    assert sr.attention_bound_f32(7.2e-5) == sr.attention_bound(7.2e-5, 8.0) - 2.0 ** -21
+
+
+def test_attention_half_keys_are_frag_rows():
+    """frag_row(r, lane) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (gp_common.h), restated: the two halves partition the 257 keys."""
+    for half in (0, 1):
+        rows = sorted(32 * t + (r & 3) + 8 * (r >> 2) + 4 * half for t in range(9) for r in range(16))
+        assert sr.attention_half_keys(half).tolist() == [k for k in rows if k < sr.T_TOK]
+    assert sorted(sr.attention_half_keys(0).tolist() + sr.attention_half_keys(1).tolist()) == list(range(sr.T_TOK))
+    assert 256 in sr.attention_half_keys(0).tolist()
+
+
+@pytest.mark.parametrize("B,H,Mpad", [(1, 6, 512), (3, 16, 1024), (5, 12, 1536)])
+def test_attention_channel_major_layout_round_trip(B, H, Mpad):
+    vals = sr.attention_case("plain", B, H, 5)
+    C, M = 64 * H, B * sr.T_TOK
+    qk, vt = sr.attention_cm_layout(vals, B, H, Mpad, float("nan"))
+    assert qk.shape == (2 * C, Mpad) and vt.shape == (Mpad, C) and qk.dtype == vt.dtype == torch.float32
+    # the layout, element by element: Q rows h * 64 + d, K rows C + h * 64 + d, column b * 257 + t; V token-major
+    q, k, v = sr.attention_qkv(vals, B, H)
+    b, h, t, d = B - 1, H - 2, 256, 37
+    assert qk[h * 64 + d, b * 257 + t] == q[b, h, t, d] and qk[C + h * 64 + d, b * 257 + t] == k[b, h, t, d]
+    assert vt[b * 257 + t, h * 64 + d] == v[b, h, t, d] and qk[5, 1] == q[0, 0, 1, 5]
+    assert torch.isnan(qk[:, M:]).all() and torch.isnan(vt[M:]).all() and not torch.isnan(qk[:, :M]).any() and not torch.isnan(vt[:M]).any()
+    back = sr.attention_cm_values(qk, vt, B, H)
+    assert torch.equal(back, vals)
+    assert torch.equal(sr.attention_ref(back.double(), B, H), sr.attention_ref(vals.double(), B, H))
+    # ... and of the output
+    ref = sr.attention_ref(vals.double(), B, H).float()
+    out = sr.attention_cm_from_output(ref, Mpad, -7.0)
+    assert out.shape == (C, Mpad) and out[h * 64 + d, b * 257 + t] == ref[b, t, h, d] and bool((out[:, M:] == -7.0).all())
+    assert torch.equal(sr.attention_cm_output(out, B, H), ref)
+
+
+@pytest.mark.parametrize("B,H", [(1, 6), (3, 16), (5, 12)])
+@pytest.mark.parametrize("cls", sr.ATTN_CLASSES)
+def test_attention_classes_hold_their_preconditions_on_the_f32_values(cls, B, H):
+    """The geometries of tests/test_gpu_vit_f32_stages.py at its seed, ViT-S with one crop included."""
+    pre = sr.attention_preconditions(cls, sr.attention_logits(sr.attention_case(cls, B, H, 5), B, H))
+    assert pre and all(ok for _, ok in pre.values()), pre
+
+
+# (mutant, class) pairs on which the class cannot see the bug -- every other pair must be separated:
+#   scale_63, per_chunk_max, query_256_from_next_crop on uniform / zero_q: equal logits whatever the scale, the maximum or the query;
+#   drop_key_256 on descending: key 256 carries < 2^-15 of every row's weight.
+# So drop_key_256 bites on 8 classes (all but descending), scale_63 / per_chunk_max / query_256_from_next_crop on the 7 classes with
+# unequal logits, half_denominator and channel_halves_swapped on all 9.
+ATTN_F32_BLIND = {("scale_63", "uniform"), ("scale_63", "zero_q"), ("per_chunk_max", "uniform"), ("per_chunk_max", "zero_q"),
+                  ("query_256_from_next_crop", "uniform"), ("query_256_from_next_crop", "zero_q"), ("drop_key_256", "descending")}
+
+
+@pytest.mark.parametrize("cls", sr.ATTN_CLASSES)
+def test_float64_attention_separates_every_mutant_from_the_f32_kernels_bound(cls):
+    """ViT-L geometry (3 crops: a next crop exists), f32 values: each of the six wrong kernels is at least 10 x attention_bound_f32 away
+    from the float64 reference on every class that can see it; the blind pairs are shown to be blind (< 0.1 x), so nobody counts on them."""
+    B, H = 3, 16
+    vals = sr.attention_case(cls, B, H, 5).double()
+    ref = sr.attention_ref(vals, B, H)
+    rmax = float(ref.abs().max())
+    e32 = float((sr.attention_ref(vals, B, H, torch.float32).double() - ref).abs().max()) / rmax
+    bound = sr.attention_bound_f32(e32)
+    assert 1e-7 < e32 < 2e-4 and bound < 2e-4
+    for kind in sr.ATTN_MUTANTS:
+        d = sr.attention_mutant(kind, vals, B, H) - ref
+        err, err256 = float(d.abs().max()) / rmax, float(d[:, 256].abs().max()) / rmax
+        if (kind, cls) in ATTN_F32_BLIND:
+            assert err < 0.1 * bound, (kind, cls, err, bound)
+            continue
+        assert err >= 10.0 * bound, (kind, cls, err, bound)
+        if kind == "query_256_from_next_crop":
+            assert err256 == err and float(d[:, :256].abs().max()) == 0.0      # that row alone
+        if kind == "channel_halves_swapped":
+            assert torch.equal(sr.attention_mutant(kind, vals, B, H)[..., :32], ref[..., 32:])
 
 
 # ---------------------------------------------------------------------------------------------------------------- the split matcher
