@@ -10,8 +10,8 @@ numpy and tests/test_gpu_eval.py holds the kernels to it bit for bit).
   pose_errors(vertices, syms, est, gt, K)            -> mssd, mspd: torch f64 on the host (any number of pairs)
   vsd_errors(mesh, est, gt, K, depth_test, frame, diameter, ...)   renders both pose sets, -> {"errors", "counts", "clipped"}
   PoseScorer(models, targets, gts, cameras)          .score_csv(path) / .score(estimates) -> recalls, ar_mssd, ar_mspd, ar_vsd, ar
-Out of scope: ADD / ADD-S (a mean's bits depend on the summation order, and BOP-19 does not use it), reading BOP json and depth
-PNG files (PoseScorer is handed their contents), the bop18 visibility mode, near-plane clipping (an estimate that puts a vertex
+ADD, ADD-S and the model diameter are gigapose_amd/distances.py (libgigapose_dist.so: means over integers, so their bits do not
+depend on the summation order).  Out of scope: reading BOP json and depth PNG files (PoseScorer is handed their contents), the bop18 visibility mode, near-plane clipping (an estimate that puts a vertex
 behind the camera drops triangles: it is reported and scores VSD 1).  There is no CPU fallback: a missing library is an error.
 """
 import ctypes
@@ -346,6 +346,22 @@ def _pose(R, t):
     return P
 
 
+def group_estimates(targets, gts, estimates):
+    """The grouping rule of the scorers (PoseScorer, distances.AddScorer): per target the inst_count highest-scored estimates of
+    that object in that image (a tie in score: file order) and every ground truth of it there
+    -> [(target, [estimates kept, descending score], [ground truths])]."""
+    by_key = {}
+    for i, e in enumerate(estimates):
+        by_key.setdefault((int(e["scene_id"]), int(e["im_id"]), int(e["obj_id"])), []).append((-float(e["score"]), i, e))
+    out = []
+    for t in targets:
+        key = (int(t["scene_id"]), int(t["im_id"]), int(t["obj_id"]))
+        kept = [e for _, _, e in sorted(by_key.get(key, []), key=lambda r: r[:2])][:int(t["inst_count"])]
+        g = [g for g in gts.get(key[:2], []) if int(g["obj_id"]) == key[2]]
+        out.append((t, kept, g))
+    return out
+
+
 class PoseScorer:
     """BOP-19 recall of a set of estimates.
       models   {obj_id: {"vertices" (V,3), "faces" (F,3), "diameter", ["symmetries_discrete"], ["symmetries_continuous"]}}
@@ -383,16 +399,7 @@ class PoseScorer:
 
     def pairs(self, estimates):
         """-> per target [(target, [estimates kept, descending score], [ground truths])]."""
-        by_key = {}
-        for i, e in enumerate(estimates):
-            by_key.setdefault((int(e["scene_id"]), int(e["im_id"]), int(e["obj_id"])), []).append((-float(e["score"]), i, e))
-        out = []
-        for t in self.targets:
-            key = (int(t["scene_id"]), int(t["im_id"]), int(t["obj_id"]))
-            kept = [e for _, _, e in sorted(by_key.get(key, []), key=lambda r: r[:2])][:int(t["inst_count"])]
-            g = [g for g in self.gts.get(key[:2], []) if int(g["obj_id"]) == key[2]]
-            out.append((t, kept, g))
-        return out
+        return group_estimates(self.targets, self.gts, estimates)
 
     def errors(self, estimates):
         """-> [(target, {"mssd" (E,G), "mspd" (E,G), "vsd" (E,G,T), "clipped" (E,G)})] as numpy, E estimates kept x G ground truths."""
