@@ -54,3 +54,13 @@ class AENet(nn.Module):
 
     def forward(self, images):
         return self.forward_by_chunk(images)
+
+    @torch.no_grad()
+    def forward_planes(self, processed_rgbs):
+        """forward() for the split matcher alone: its query planes (2, B, 256, C) f16 = (hi, lo) of the same features, written by
+        the ViT's last kernel (Dinov2ViT.patch_features: matcher_planes) instead of the f32 tensor the matcher would re-read."""
+        outs = [self.dinov2_model.patch_features(processed_rgbs[s:s + self.max_batch_size], matcher_planes=True)
+                for s in range(0, processed_rgbs.shape[0], self.max_batch_size)]
+        if not outs:
+            return torch.empty(2, 0, 256, self.descriptor_size, dtype=torch.float16, device=processed_rgbs.device)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)

@@ -723,8 +723,15 @@ __global__ __launch_bounds__(256) void l2norm_split_kernel(const float* __restri
     }
 }
 
+// the patch-mask part of l2norm_split_kernel on its own (gp_l2norm_split_mask with x == NULL)
+__global__ __launch_bounds__(256) void patch_mask_kernel(const float* __restrict__ mask_img, int mh, int mw, float* __restrict__ patch_mask)
+{
+    const int row = blockIdx.x, p = threadIdx.x;
+    patch_mask[(size_t)row * GP_P + p] = mask_img[(size_t)row * mh * mw + (size_t)((p >> 4) * (mh / GP_G)) * mw + (p & 15) * (mw / GP_G)];
+}
+
 // ------------------------------------------------------------------ top-k per detection
-// One wave per detection.  Order: higher score, then lower template index (torch.topk leaves
+// One wave per detection. Order: higher score, then lower template index (torch.topk leaves
 // ties unspecified; the oracle uses the same rule).
 __global__ __launch_bounds__(64) void topk_kernel(const float* __restrict__ sim_avg, int N, int k,
                                                    int* __restrict__ ids, float* __restrict__ scores)
@@ -882,10 +889,15 @@ int gp_l2norm_split_mask(const float* x, void* hi, void* lo, int rows, int C, co
 {
     GP_REQUIRE(rows >= 0 && C > 0, "gp_l2norm_split: bad arguments (rows=%d C=%d)", rows, C);
     if (rows == 0) return GP_OK;
-    GP_REQUIRE(x && hi && lo, "gp_l2norm_split: null pointer");
+    GP_REQUIRE((x && hi && lo) || (!x && patch_mask), "gp_l2norm_split: null pointer");
     GP_REQUIRE(!patch_mask || (mask_img && mask_h > 0 && mask_w > 0 && mask_h % GP_G == 0 && mask_w % GP_G == 0),
                "gp_l2norm_split_mask: the mask image must be (rows, H, W) f32 with H, W multiples of 16 (got %d x %d)", mask_h, mask_w);
     const int ngrp = (C + 31) / 32;
+    if (!x) {  // the patch masks alone (the planes came from gp_vit_forward_split2, normalize == 2)
+        hipLaunchKernelGGL(patch_mask_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, mask_img, mask_h, mask_w, patch_mask);
+        GP_CHECK_LAUNCH("gp_l2norm_split");
+        return GP_OK;
+    }
     hipLaunchKernelGGL(l2norm_split_kernel, dim3(rows, ngrp < 4 ? ngrp : 4), dim3(256), 0, (hipStream_t)stream, x, (_Float16*)hi,
                        (_Float16*)lo, C, ngrp * 32, mask_img, mask_h, mask_w, patch_mask);
     GP_CHECK_LAUNCH("gp_l2norm_split");

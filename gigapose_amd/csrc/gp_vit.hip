@@ -22,7 +22,7 @@ int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const
                             int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
                             float* scratch, hipStream_t st);
 size_t gp_gemm_streamk_bytes();
-int gp_gemm_streamk_reset_launch(float* sk_ws, hipStream_t st);
+size_t gp_gemm_streamk_header_bytes();
 bool gp_gemm_split256_usable(int I, int J, int K);
 bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K);
 int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
@@ -36,9 +36,14 @@ constexpr int PATCH = 14, IMG = 224, KPE = 588, KPE_PAD = 592, T_TOK = 257;
 
 // ---- patch-embed operand: col[k][b*256+p] = img[b][ci][14py+dy][14px+dx], k = ci*196+dy*14+dx
 // (flatten order of Conv2d weight (C,3,14,14); HF modeling_dinov2.py:139).  Rows 588..591 = 0.
-__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, float* __restrict__ col, int B)
+// The forward's first launch also zeroes the header of the stream-K scratch (hand-over flags + error word, `sk_words` ints): the
+// runtime's fill kernel did that in a launch of its own in front of every forward.
+__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, float* __restrict__ col, int B,
+                                                      int* __restrict__ sk_header, int sk_words)
 {
     const int k = blockIdx.x, b = blockIdx.y, p = threadIdx.x;
+    if (k == 0 && b == 0)
+        for (int w = p; w < sk_words; w += 256) sk_header[w] = 0;
     float v = 0.f;
     if (k < KPE) {
         const int ci = k / 196, dy = (k % 196) / PATCH, dx = k % PATCH;
@@ -48,23 +53,8 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
     col[(size_t)k * (B * GP_P) + (size_t)b * GP_P + p] = v;
 }
 
-// ---- tokens = cat(cls, patches) + pos  (HF modeling_dinov2.py:108-112); zero the pad columns
-__global__ __launch_bounds__(320) void embed_kernel(const float* __restrict__ pe /*[C][B*256]*/,
-                                                     const float* __restrict__ cls_pos /*[C]*/,
-                                                     const float* __restrict__ pos_t /*[C][256]*/,
-                                                     float* __restrict__ X, int B, int Mpad)
-{
-    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    if (b == B) {  // extra block row: clear padding columns [B*T, Mpad)
-        for (int m = B * T_TOK + t; m < Mpad; m += 320) X[(size_t)c * Mpad + m] = 0.f;
-        return;
-    }
-    if (t >= T_TOK) return;
-    float v;
-    if (t == 0) v = cls_pos[c];
-    else v = pe[(size_t)c * (B * GP_P) + (size_t)b * GP_P + (t - 1)] + pos_t[(size_t)c * GP_P + (t - 1)];
-    X[(size_t)c * Mpad + (size_t)b * T_TOK + t] = v;
-}
+// tokens = cat(cls, patches) + pos (HF modeling_dinov2.py:108-112) and the zeros of the pad columns are the patch-embed GEMM's
+// epilogue (gp_gemm.hip: EPI_EMBED)
 
 // ---- LayerNorm over C of channel-major X [C][Mpad], wide: block = 64 token columns x 16 channel slices (16 waves, 4128 waves in flight at
 // B=64 instead of 258), three short passes; the block's 64 x C tile is re-read from L2.
@@ -210,15 +200,41 @@ __global__ __launch_bounds__(1024) void layernorm_planes_kernel(const float* __r
 // (the 8-crop step 8.93 -> 8.82 ms); at 16 / 24 crops (129 / 193 blocks) the 16-token form is SLOWER (13.0 -> 15.6, 15.1 -> 17.3 us: twice
 // the blocks with 64-byte token segments) -- hence the threshold at 128 blocks.  The per-thread summation order of the statistics differs
 // between the two forms: they agree to f32 round-off, not bit for bit -- like two batch shapes.
-template <int NK, int TOK = 32>
+// Tail of a launch (launch_layernorm_planes): the blocks cover rows [0, gridDim.x * TOK); `n_extra` further tokens, rows extra_tok0 + i,
+// ride on blocks i < n_extra (FOLD), and rows [zero_row0, zero_row0 + zero_rows) -- row padding no block computes -- are zeroed.
+struct LnTail { int n_extra, extra_tok0, zero_row0, zero_rows; };
+
+// FOLD (32-token blocks only): when the blocks exceed a whole number of resident rounds by a few, the remainder's blocks would start
+// late and run alone, latency-bound (4.3 of 25.5 us at ViT-L x 64 crops: 514 blocks on 512 slots; profiles/r06_ln_rounds_and_cold_gemm.txt).
+// Their tokens are instead EXTRA tokens of first-round blocks, one each: the block's 512 threads load the token's C values (c = tid,
+// tid + 512) with the main loads and park them in LDS; 16 lanes sum the 16 slices in a regular token's order -- slice j: channels
+// CH k + 8 j + e, k then e ascending, then the 16 partials in slice order -- between the barriers the block has anyway; every thread
+// converts the values it loaded.  Same operations on the same values in the same order: an extra token's planes are bit-identical to
+// what a block of its own writes.
+template <int NK, int TOK = 32, bool FOLD = false>
 __global__ __launch_bounds__(512) void layernorm_planes_reg_kernel(const float* __restrict__ X, _Float16* __restrict__ Yhi,
                                                                     _Float16* __restrict__ Ylo, const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, int Mpad, float eps,
-                                                                    int* __restrict__ status, float plane_scale, float* __restrict__ amax)
+                                                                    int* __restrict__ status, float plane_scale, float* __restrict__ amax,
+                                                                    const LnTail tail)
 {
     constexpr int C = 128 * NK, SL = 512 / TOK, CH = 8 * SL, NC = C / CH;  // slices, channels per chunk, chunks
     constexpr int TP = CH + 4;  // LDS row pitch in words: 16-byte aligned pieces, consecutive tokens one 16-byte slot off the bank period
     static_assert(C % CH == 0 && (TOK == 32 || TOK == 16), "layernorm_planes_reg_kernel: C must be a multiple of the chunk width");
+    static_assert(!FOLD || TOK == 32, "layernorm_planes_reg_kernel: extra tokens are summed as 16 slices");
+    constexpr int EV = (C + 511) / 512;  // FOLD: values of the extra token per thread
+    __shared__ __attribute__((aligned(16))) float xe[FOLD ? C : 4];
+    __shared__ float rede[2][16];
+    const bool fold = FOLD && (int)blockIdx.x < tail.n_extra;  // block-uniform
+    const size_t etok = FOLD ? (size_t)(tail.extra_tok0 + (int)blockIdx.x) : 0;
+    float ev[EV] = {};
+    if (fold) {
+#pragma unroll
+        for (int u = 0; u < EV; ++u) {
+            const int c = threadIdx.x + 512 * u;
+            ev[u] = c < C ? X[(size_t)c * Mpad + etok] : 0.f;
+        }
+    }
     __shared__ float red[SL][TOK];
     __shared__ __attribute__((aligned(16))) unsigned int tile[2][TOK * TP];
     // gamma | beta once per block through LDS (requested with the activations, visible after the first barrier): read from global
@@ -240,12 +256,27 @@ __global__ __launch_bounds__(512) void layernorm_planes_reg_kernel(const float* 
         gb[0][c] = gamma[c];
         gb[1][c] = beta[c];
     }
+    if (fold) {
+#pragma unroll
+        for (int u = 0; u < EV; ++u)
+            if (threadIdx.x + 512 * u < C) xe[threadIdx.x + 512 * u] = ev[u];
+    }
     red[sl][tok] = s;
     __syncthreads();
     float tot = 0.f;
 #pragma unroll
     for (int j = 0; j < SL; ++j) tot += red[j][tok];
     const float mean = tot / (float)C;
+    if (fold && threadIdx.x < 16) {  // slice threadIdx.x of the extra token, summed as thread (tok, sl = threadIdx.x) sums its registers
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(xe + CH * k + 8 * threadIdx.x), a1 = *reinterpret_cast<const f32x4*>(xe + CH * k + 8 * threadIdx.x + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) se += e < 4 ? a0[e] : a1[e - 4];
+        }
+        rede[0][threadIdx.x] = se;
+    }
     __syncthreads();
     float q = 0.f;
 #pragma unroll
@@ -256,15 +287,53 @@ __global__ __launch_bounds__(512) void layernorm_planes_reg_kernel(const float* 
             q = __builtin_fmaf(d, d, q);
         }
     red[sl][tok] = q;
+    if (fold && threadIdx.x < 16) {
+        float te = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) te += rede[0][j];
+        const float me = te / (float)C;
+        float qe = 0.f;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(xe + CH * k + 8 * threadIdx.x), a1 = *reinterpret_cast<const f32x4*>(xe + CH * k + 8 * threadIdx.x + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = (e < 4 ? a0[e] : a1[e - 4]) - me;
+                qe = __builtin_fmaf(d, d, qe);
+            }
+        }
+        rede[1][threadIdx.x] = qe;
+    }
     __syncthreads();
     tot = 0.f;
 #pragma unroll
     for (int j = 0; j < SL; ++j) tot += red[j][tok];
     const float rstd = 1.0f / __builtin_sqrtf(tot / (float)C + eps);
-    const int g2 = threadIdx.x & (SL - 1), t2 = threadIdx.x / SL;  // store phase: SL lanes = the SL eight-channel pieces of token t2
-    const size_t row = (tok0 + t2) * C + 8 * g2;
     int bad = 0;
     float vmax = 0.f;
+    if (fold) {  // the extra token's statistics from its 16 + 16 partials (every thread, in slice order), then its values, element-wise
+        float te = 0.f, tq = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) te += rede[0][j];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tq += rede[1][j];
+        const float me = te / (float)C, re = 1.0f / __builtin_sqrtf(tq / (float)C + eps);
+#pragma unroll
+        for (int u = 0; u < EV; ++u) {
+            const int c = threadIdx.x + 512 * u;
+            if (c < C) {
+                const float y = (ev[u] - me) * re * gb[0][c] + gb[1][c];
+                const float v = y * plane_scale;
+                const _Float16 hh = (_Float16)v;
+                bad |= !(fabsf(v) <= kSplitPlaneLimit);
+                if (amax) vmax = __builtin_elementwise_maximum(vmax, __builtin_fabsf(v));
+                Yhi[etok * C + c] = hh;
+                Ylo[etok * C + c] = (_Float16)(v - (float)hh);
+            }
+        }
+    }
+    const int g2 = threadIdx.x & (SL - 1), t2 = threadIdx.x / SL;  // store phase: SL lanes = the SL eight-channel pieces of token t2
+    const size_t row = (tok0 + t2) * C + 8 * g2;
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
         unsigned int* T = tile[k & 1];
@@ -301,6 +370,12 @@ __global__ __launch_bounds__(512) void layernorm_planes_reg_kernel(const float* 
     }
     if (bad) gp_raise(status, GP_ST_SPLIT_RANGE);
     if (amax) gp_record_amax(amax, vmax, 1.0f / plane_scale);
+    // rows of padding no block computes: zero, 16 bytes per thread and plane, spread over the grid
+    const v16x8 z = {};
+    for (int w = blockIdx.x * 512 + threadIdx.x; w < tail.zero_rows * (C / 8); w += gridDim.x * 512) {
+        *reinterpret_cast<v16x8*>(Yhi + (size_t)tail.zero_row0 * C + (size_t)w * 8) = z;
+        *reinterpret_cast<v16x8*>(Ylo + (size_t)tail.zero_row0 * C + (size_t)w * 8) = z;
+    }
 }
 
 
@@ -308,17 +383,65 @@ static int g_ln_planes_reg = 1;  // A/B hook (gp_vit_set_ln_reg): 0 = the three-
 #ifdef GP_PROBES
 extern "C" void gp_vit_set_ln_reg(int on) { g_ln_planes_reg = (on >= 0 && on <= 2) ? on : 1; }
 #endif
+static int g_ln_live = -1;  // stage entry gp_layernorm_planes: rows that carry tokens (< 0: all of them)
+#ifdef GP_PROBES
+extern "C" void gp_vit_set_ln_live(int tokens) { g_ln_live = tokens > 0 ? tokens : -1; }
+#endif
 
+// resident blocks of the folding kernel on the current device (its occupancy x the CU count), asked once per device; 0 = unknown
+template <int NK>
+int ln_fold_slots()
+{
+    static int cache[64] = {};
+    int dev = 0, per_cu = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cache[dev] == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, layernorm_planes_reg_kernel<NK, 32, true>, 512, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return 0;
+        cache[dev] = per_cu * cus > 0 ? per_cu * cus : -1;
+    }
+    return cache[dev] > 0 ? cache[dev] : 0;
+}
+
+constexpr int kLnFoldMaxBlocks = 4;  // fold a remainder of at most this many 32-token blocks (each first-round block takes one extra token)
+
+// 32-token blocks over the `live` token rows only: blocks of pure row padding do not run (their plane rows are zeroed by the blocks that
+// do), and a small remainder past a whole number of resident rounds is folded into first-round blocks (FOLD above)
+template <int NK>
+void launch_ln_reg32(const float* X, _Float16* hi, _Float16* lo, const float* g, const float* b, int Mpad, int live, float eps, hipStream_t st,
+                     float plane_scale, float* amax)
+{
+    const int nblk = (live + 31) / 32;
+    const int slots = ln_fold_slots<NK>();
+    const int rem = slots > 0 ? nblk % slots : 0;
+    const int n_extra = live - (nblk - rem) * 32;  // the remainder's live tokens
+    if (rem >= 1 && rem <= kLnFoldMaxBlocks && nblk > rem && n_extra <= nblk - rem) {
+        const LnTail tail{n_extra, (nblk - rem) * 32, live, Mpad - live};
+        hipLaunchKernelGGL((layernorm_planes_reg_kernel<NK, 32, true>), dim3(nblk - rem), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(),
+                           plane_scale, amax, tail);
+    } else {
+        const LnTail tail{0, 0, nblk * 32, Mpad - nblk * 32};
+        hipLaunchKernelGGL((layernorm_planes_reg_kernel<NK, 32, false>), dim3(nblk), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(),
+                           plane_scale, amax, tail);
+    }
+}
+
+// Mtok: the rows that carry tokens (the forward passes B * 257; < 0 = all Mpad).  Which kernel runs depends on C and Mpad alone, as before
+// (the forms differ in summation order); Mtok only keeps blocks of pure padding from running.
 int launch_layernorm_planes(const float* X, _Float16* hi, _Float16* lo, const float* g, const float* b, int C, int Mpad, float eps,
-                            hipStream_t st, float plane_scale = kPlaneScale, float* amax = nullptr)
+                            hipStream_t st, float plane_scale = kPlaneScale, float* amax = nullptr, int Mtok = -1)
 {
     GpProfScope prof(GP_PROF_LN, 8.0 * C * Mpad, st);
-    if (g_ln_planes_reg && C == 1024 && Mpad % 32 == 0 && Mpad / 32 <= 128 && g_ln_planes_reg != 2)   // at most half a block per CU: 16-token blocks
-        hipLaunchKernelGGL((layernorm_planes_reg_kernel<8, 16>), dim3(Mpad / 16), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(), plane_scale, amax);
-    else if (g_ln_planes_reg && C == 1024 && Mpad % 32 == 0)
-        hipLaunchKernelGGL(layernorm_planes_reg_kernel<8>, dim3(Mpad / 32), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(), plane_scale, amax);
+    const int live = (Mtok > 0 && Mtok < Mpad) ? Mtok : Mpad;
+    if (g_ln_planes_reg && C == 1024 && Mpad % 32 == 0 && Mpad / 32 <= 128 && g_ln_planes_reg != 2) {   // at most half a block per CU: 16-token blocks
+        const int nblk = (live + 15) / 16;
+        const LnTail tail{0, 0, nblk * 16, Mpad - nblk * 16};
+        hipLaunchKernelGGL((layernorm_planes_reg_kernel<8, 16>), dim3(nblk), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(), plane_scale, amax, tail);
+    } else if (g_ln_planes_reg && C == 1024 && Mpad % 32 == 0)
+        launch_ln_reg32<8>(X, hi, lo, g, b, Mpad, live, eps, st, plane_scale, amax);
     else if (g_ln_planes_reg && C == 768 && Mpad % 32 == 0)
-        hipLaunchKernelGGL(layernorm_planes_reg_kernel<6>, dim3(Mpad / 32), dim3(512), 0, st, X, hi, lo, g, b, Mpad, eps, gp_status_buffer(), plane_scale, amax);
+        launch_ln_reg32<6>(X, hi, lo, g, b, Mpad, live, eps, st, plane_scale, amax);
     else
         hipLaunchKernelGGL(layernorm_planes_kernel, dim3(Mpad / 64), dim3(1024), 0, st, X, hi, lo, g, b, C, Mpad, eps, gp_status_buffer(), plane_scale, amax);
     return 0;
@@ -855,6 +978,94 @@ int launch_features(const float* X, float* out, int B, int C, int Mpad, int norm
     return 0;
 }
 
+// ---- x_prenorm[:, 1:] straight to the split matcher's query planes: features_kernel(normalize) followed by gp_match.hip's
+// l2norm_split_kernel in one pass over X, without the f32 tensor (B, C, 256) between them.  Per patch, exactly their arithmetic:
+//   chain 1 over x (c ascending), d1 = max(sqrt(ss), 1e-12), v = x / d1;  chain 2 over v, d2 likewise;  w = (v / d2) * 32,
+//   hi = f16(w), lo = f16(w - hi)                                                        -> planes [b][patch][C], bit-identical.
+// Block = 16 patches of one crop x all C channels, held in LDS patch-major (pitch C + 4 words: the 16 patch rows start 4 banks
+// apart, so the channel-major loads' writes, the chains' b128 reads and the store phase's b128 reads are all conflict-free or
+// two-way).  All 256 threads load (8 independent loads per thread and round), divide and convert; the two sequential chains run
+// ONCE per patch, on 16 lanes, out of LDS -- the two kernels this replaces ran each chain in 4 blocks per crop, one 64 KB row
+// round trip to L2 / HBM per 16 fmas.  16 C + 64 floats of LDS: two blocks per CU at C = 1024.
+constexpr float kMatchFeatScale = 32.0f;  // == kFeatScale of gp_match.hip
+constexpr int FP_PT = 16;                 // patches per block
+
+__global__ __launch_bounds__(256) void features_planes_kernel(const float* __restrict__ X, _Float16* __restrict__ hi,
+                                                               _Float16* __restrict__ lo, int C, int Mpad, int* __restrict__ status)
+{
+    extern __shared__ __attribute__((aligned(16))) float fp_lds[];
+    const int pitch = C + 4;
+    float* xs = fp_lds;                    // [FP_PT][pitch]
+    float* dn = fp_lds + FP_PT * pitch;    // [FP_PT]
+    const int b = blockIdx.x / (GP_P / FP_PT), p0 = (blockIdx.x % (GP_P / FP_PT)) * FP_PT, t = threadIdx.x;
+    const int pl = t & (FP_PT - 1), cs = t / FP_PT;  // load / divide phases: patch pl, channels cs + 16 i
+    const float* x = X + (size_t)cs * Mpad + (size_t)b * T_TOK + 1 + p0 + pl;
+    float* xl = xs + pl * pitch + cs;
+    for (int i = 0; i < C / 16; i += 8) {  // C % 128 == 0 (gp_vit_forward)
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = x[(size_t)(16 * (i + u)) * Mpad];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xl[16 * (i + u)] = v[u];
+    }
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+        if (t < FP_PT) {  // the sequential chain of patch t: channels in ascending order, as features_kernel / l2norm_split_kernel
+            const f32x4* r = reinterpret_cast<const f32x4*>(xs + t * pitch);
+            float ss = 0.f;
+#pragma unroll 8
+            for (int c4 = 0; c4 < C / 4; ++c4) {
+                const f32x4 v = r[c4];
+                ss = __builtin_fmaf(v[0], v[0], ss);
+                ss = __builtin_fmaf(v[1], v[1], ss);
+                ss = __builtin_fmaf(v[2], v[2], ss);
+                ss = __builtin_fmaf(v[3], v[3], ss);
+            }
+            // features_kernel's guard: a NaN / inf anywhere in the token's residual stream ends up in its first norm
+            if (pass == 0 && !(ss <= 3.0e38f)) gp_raise(status, GP_ST_SPLIT_RANGE);
+            dn[t] = fmaxf(__builtin_sqrtf(ss), 1e-12f);
+        }
+        __syncthreads();
+        if (pass == 0) {  // v = x / d1 in place, element-wise
+            const float d = dn[pl];
+#pragma unroll 8
+            for (int i = 0; i < C / 16; ++i) xl[16 * i] = xl[16 * i] / d;
+            __syncthreads();
+        }
+    }
+    // store phase: thread -> (patch pp, 8-channel group g), g fastest: C / 8 lanes write one patch row's 2 C contiguous bytes per plane
+    const int G = C >> 3;
+    for (int item = t; item < FP_PT * G; item += 256) {
+        const int pp = item / G, g = item - pp * G;
+        const float d = dn[pp];
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(xs + pp * pitch + 8 * g), a1 = *reinterpret_cast<const f32x4*>(xs + pp * pitch + 8 * g + 4);
+        v16x8 h, l;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float v = ((e < 4 ? a0[e] : a1[e - 4]) / d) * kMatchFeatScale;
+            const _Float16 hh = (_Float16)v;
+            h[e] = hh;
+            l[e] = (_Float16)(v - (float)hh);
+        }
+        const size_t o = ((size_t)b * GP_P + p0 + pp) * C + 8 * g;
+        *reinterpret_cast<v16x8*>(hi + o) = h;
+        *reinterpret_cast<v16x8*>(lo + o) = l;
+    }
+}
+
+// planes hi | lo, each (B, 256, C) f16, back to back in `out` (C % 128 == 0: no pad channels, Cp == C)
+int launch_features_planes(const float* X, float* out, int B, int C, int Mpad, hipStream_t st)
+{
+    const size_t lds = sizeof(float) * ((size_t)FP_PT * (C + 4) + FP_PT);
+    GP_REQUIRE(lds <= 160 * 1024, "gp_vit_forward: dim=%d is too wide for the features-to-planes kernel", C);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&features_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    _Float16* hi = reinterpret_cast<_Float16*>(out);
+    hipLaunchKernelGGL(features_planes_kernel, dim3(B * (GP_P / FP_PT)), dim3(256), lds, st, X, hi, hi + (size_t)B * GP_P * C, C, Mpad,
+                       gp_status_buffer());
+    return GP_OK;
+}
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 }  // namespace
@@ -870,7 +1081,7 @@ size_t gp_vit_workspace_bytes(int B, int dim, int mlp_dim)
 {
     if (B <= 0 || dim <= 0 || mlp_dim <= 0) return 0;
     const size_t Mpad = (size_t)round_up(B * T_TOK, 256);
-    // X, H (C each), QK (2C), Vt (C), F (mlp_dim; also hosts im2col + patch-embed output)
+    // X, H (C each), QK (2C), Vt (C), F (mlp_dim; also hosts im2col; sized as when the patch-embed output lay behind it)
     size_t f = (size_t)mlp_dim * Mpad;
     const size_t pe_need = (size_t)KPE_PAD * B * GP_P + (size_t)dim * B * GP_P;
     if (pe_need > f) f = pe_need;
@@ -907,7 +1118,8 @@ int gp_layernorm_planes(const float* X, void* out_hi, void* out_lo, const float*
                         void* stream)
 {
     GP_REQUIRE(X && out_hi && out_lo && gamma && beta && C > 0 && C % 128 == 0 && Mpad > 0 && Mpad % 64 == 0, "gp_layernorm_planes: bad arguments");
-    launch_layernorm_planes(X, (_Float16*)out_hi, (_Float16*)out_lo, gamma, beta, C, Mpad, eps, (hipStream_t)stream);
+    // every row carries a token (the forward passes its live-token count; the probe library's gp_vit_set_ln_live does it for this entry)
+    launch_layernorm_planes(X, (_Float16*)out_hi, (_Float16*)out_lo, gamma, beta, C, Mpad, eps, (hipStream_t)stream, kPlaneScale, nullptr, g_ln_live);
     GP_CHECK_LAUNCH("gp_layernorm_planes");
     return GP_OK;
 }
@@ -999,21 +1211,18 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
     float* F = Vt + (size_t)C * Mpad;
     size_t f_floats = (size_t)mlp_dim * Mpad;
     if ((size_t)KPE_PAD * B * GP_P + (size_t)dim * B * GP_P > f_floats) f_floats = (size_t)KPE_PAD * B * GP_P + (size_t)dim * B * GP_P;
-    float* SK = F + f_floats;                  // stream-K scratch (flags zeroed once per forward)
+    float* SK = F + f_floats;                  // stream-K scratch (flags zeroed once per forward, by im2col_kernel)
     float* col = F;                            // [592][B*256]
-    float* pe = F + (size_t)KPE_PAD * BP;      // [C][B*256]
     int rc;
 
-    if ((rc = gp_gemm_streamk_reset_launch(SK, st))) return rc;
-    hipLaunchKernelGGL(im2col_kernel, dim3(KPE_PAD, B), dim3(256), 0, st, images, col, B);
+    hipLaunchKernelGGL(im2col_kernel, dim3(KPE_PAD, B), dim3(256), 0, st, images, col, B, reinterpret_cast<int*>(SK),
+                       (int)(gp_gemm_streamk_header_bytes() / sizeof(int)));
     GP_CHECK_LAUNCH("gp_vit_forward/im2col");
-    // BP = B*256 is a multiple of 128 only for even B... (256 is) -> always a multiple of 128
-    if ((rc = gp_gemm_launch(weights[W_PATCH_WT], C, col, BP, pe, BP, C, BP, KPE_PAD, 1 /*BIAS_I*/,
-                             weights[W_PATCH_B], nullptr, nullptr, 0, SK, st)))
+    // BP = B*256 is always a multiple of 128.  Epilogue 8: + bias, + position table, re-indexed b*256+p -> b*257+1+p straight into X,
+    // with the class-token columns and the zeroed pad columns
+    if ((rc = gp_gemm_launch(weights[W_PATCH_WT], C, col, BP, X, Mpad, C, BP, KPE_PAD, 8 /*EMBED*/,
+                             weights[W_PATCH_B], weights[W_POS_T], weights[W_CLS_POS], Mpad, SK, st)))
         return rc;
-    hipLaunchKernelGGL(embed_kernel, dim3(C, B + 1), dim3(320), 0, st, pe, weights[W_CLS_POS], weights[W_POS_T],
-                       X, B, Mpad);
-    GP_CHECK_LAUNCH("gp_vit_forward/embed");
 
     const int nl = (stop_after_layers >= 0 && stop_after_layers < depth) ? stop_after_layers : depth;
     // Split numerics, third generation: when all five GEMMs of a layer fill the chip with 256 x 256 tiles, the
@@ -1041,7 +1250,7 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
             const float os_ln1 = 1.0f / (ps[PS_LN1] * 64.0f), os_qkv = 1.0f / (ps[PS_QKV] * 64.0f), os_ln2 = 1.0f / (ps[PS_LN2] * 64.0f),
                         os_gelu = 1.0f / (ps[PS_GELU] * 64.0f);   // a consumer undoes its B operand's scale and the weights' x 64, exactly
             const GpPlaneOut po_qkv{ps[PS_QKV], am ? am + PS_QKV : nullptr}, po_gelu{ps[PS_GELU], am ? am + PS_GELU : nullptr};
-            launch_layernorm_planes(X, Hhi, Hlo, w[L_LN1_G], w[L_LN1_B], C, Mpad, ln_eps, st, ps[PS_LN1], am ? am + PS_LN1 : nullptr);
+            launch_layernorm_planes(X, Hhi, Hlo, w[L_LN1_G], w[L_LN1_B], C, Mpad, ln_eps, st, ps[PS_LN1], am ? am + PS_LN1 : nullptr, Mtok);
             GP_CHECK_LAUNCH("gp_vit_forward/layernorm_planes");
             // Q | K | V as planes [Mpad][3C] (aliasing the f32 QK + Vt buffers): W_qk / W_v (A) x tokens (B), plane epilogue
             _Float16* Ahi = reinterpret_cast<_Float16*>(QK);
@@ -1073,7 +1282,7 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
             if ((rc = gp_gemm_planes256_launch(sq[S_PROJ_HI], sq[S_PROJ_LO], Hhi, Hlo, X, Mpad, nullptr, nullptr, 0, C, Mpad, Mtok, C,
                                                3 /*BIAS_I_SCALE_RES*/, w[L_PROJ_B], w[L_LS1], X, Mpad, os_qkv, SK, st)))
                 return rc;
-            launch_layernorm_planes(X, Hhi, Hlo, w[L_LN2_G], w[L_LN2_B], C, Mpad, ln_eps, st, ps[PS_LN2], am ? am + PS_LN2 : nullptr);
+            launch_layernorm_planes(X, Hhi, Hlo, w[L_LN2_G], w[L_LN2_B], C, Mpad, ln_eps, st, ps[PS_LN2], am ? am + PS_LN2 : nullptr, Mtok);
             GP_CHECK_LAUNCH("gp_vit_forward/layernorm_planes");
             // gelu(fc1(.)) straight to planes [Mpad][mlp_dim]
             if ((rc = gp_gemm_planes256_launch(sq[S_FC1_HI], sq[S_FC1_LO], Hhi, Hlo, nullptr, 0, Fhi, Flo, mlp_dim, mlp_dim, Mpad, Mtok, C,
@@ -1124,7 +1333,11 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
         else rc = gp_gemm_launch(w[L_FC2_WT], C, F, Mpad, X, Mpad, C, Mpad, mlp_dim, 3, w[L_FC2_B], w[L_LS2], X, Mpad, SK, st);
         if (rc) return rc;
     }
-    launch_features(X, out_features, B, C, Mpad, normalize, st);
+    if (normalize == 2) {  // the split matcher's query planes instead of the f32 features (include/gigapose_hip.h)
+        if ((rc = launch_features_planes(X, out_features, B, C, Mpad, st))) return rc;
+    } else {
+        launch_features(X, out_features, B, C, Mpad, normalize, st);
+    }
     GP_CHECK_LAUNCH("gp_vit_forward/features");
     return GP_OK;
 }

@@ -342,7 +342,12 @@ class GigaPose(_Base):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 tar_ist = self._backbone_rows("ist", self.ist_net.forward_by_chunk, tar_img, live_rows)   # stage 4a: IST backbone (once)
-        tar_ae = self._backbone_rows("ae", self.ae_net, tar_img, live_rows)            # stage 1: ViT features
+        if self.template_shard is None and self.testing_metric.numerics == "split" and hasattr(self.ae_net, "forward_planes"):
+            # stage 1: ViT features, handed to the matcher as its query planes (2, B, 256, C) by the ViT's last kernel -- nothing but
+            # the matcher reads them here (the sharded path exchanges the f32 tensor and keeps it)
+            tar_ae = self._backbone_rows("ae_planes", self.ae_net.forward_planes, tar_img, live_rows, row_dim=1)
+        else:
+            tar_ae = self._backbone_rows("ae", self.ae_net, tar_img, live_rows)            # stage 1: ViT features
         if self.template_shard is None:
             pred = self.testing_metric.test_bank(bank, tar_ae, tar_mask, labels0)  # stage 3: matching
             if side is None:
@@ -367,22 +372,26 @@ class GigaPose(_Base):
         pred.register_tensor("pred_poses", poses)
         return pred
 
-    def _backbone_rows(self, key, net, tar_img, live_rows):
+    def _backbone_rows(self, key, net, tar_img, live_rows, row_dim=0):
         """net(tar_img) computed on the first `live_rows` rows only, zero features for the padding rows behind them (an all-padding
-        batch does not run the network at all once its output shape is known)."""
+        batch does not run the network at all once its output shape is known).  row_dim: the output's dimension that counts crops."""
         B = tar_img.shape[0]
+
+        def shape_for(rows, other):
+            return other[:row_dim] + (rows,) + other[row_dim:]
+
         if live_rows is None or live_rows >= B:
             out = net(tar_img)
-            self._feat_shapes[key] = (tuple(out.shape[1:]), out.dtype)
+            self._feat_shapes[key] = (tuple(out.shape[:row_dim]) + tuple(out.shape[row_dim + 1:]), out.dtype)
             return out
         if live_rows == 0 and key in self._feat_shapes:
             shape, dtype = self._feat_shapes[key]
-            return torch.zeros((B,) + shape, dtype=dtype, device=tar_img.device)
+            return torch.zeros(shape_for(B, shape), dtype=dtype, device=tar_img.device)
         feat = net(tar_img[:max(live_rows, 1)])
-        self._feat_shapes[key] = (tuple(feat.shape[1:]), feat.dtype)
-        out = feat.new_zeros((B,) + tuple(feat.shape[1:]))
+        self._feat_shapes[key] = (tuple(feat.shape[:row_dim]) + tuple(feat.shape[row_dim + 1:]), feat.dtype)
+        out = feat.new_zeros(shape_for(B, self._feat_shapes[key][0]))
         if live_rows > 0:
-            out[:live_rows] = feat[:live_rows]
+            out.narrow(row_dim, 0, live_rows).copy_(feat.narrow(row_dim, 0, live_rows))
         return out
 
     def eval_retrieval(self, batch, idx_batch, dataset_name, sort_pred_by_inliers=True):

@@ -61,6 +61,20 @@ def normalize_split(feats, mask224=None):
     return hi, lo, qmask
 
 
+def patch_masks(mask224):
+    """(rows, H, W) -> the rows' patch masks (rows, 256) f32 = patch_grid_mask(mask224): the mask part of normalize_split's launch
+    on its own (gp_l2norm_split_mask with no features), for query planes that the ViT already wrote."""
+    rows = mask224.shape[0]
+    fused = (mask224.is_cuda and mask224.dtype == torch.float32 and mask224.is_contiguous() and mask224.dim() == 3 and rows > 0
+             and mask224.shape[1] % 16 == 0 and mask224.shape[2] % 16 == 0)
+    if not fused:   # another dtype / layout: the strided copy
+        return patch_grid_mask(mask224)
+    qmask = torch.empty(rows, P, dtype=torch.float32, device=mask224.device)
+    _lib.call("gp_l2norm_split_mask", _lib.ptr(None), _lib.ptr(None), _lib.ptr(None), _lib.i(rows), _lib.i(32), _lib.ptr(mask224),
+              _lib.i(mask224.shape[1]), _lib.i(mask224.shape[2]), _lib.ptr(qmask), _lib.stream_ptr())
+    return qmask
+
+
 class MatchBank:
     """Matcher-ready template bank: twice-normalised features (AENet's F.normalize, then the
     matcher's own, matching.py:229) and patch masks (O,N,256).  numerics "chain": features (O,N,C,256) f32;
@@ -205,8 +219,14 @@ class LocalSimilarity(torch.nn.Module):
 
     # ---- resident-bank entry point (what GigaPose.eval_retrieval uses) --------------------
     def test_bank(self, bank, tar_feat, tar_mask, labels0):
-        """tar_feat (B,C,16,16) AENet features, tar_mask (B,224,224), labels0 (B,) 0-based."""
-        if self.numerics == "split":   # normalise + split + the patch masks in ONE launch
+        """tar_feat (B,C,16,16) AENet features, tar_mask (B,224,224), labels0 (B,) 0-based.  Split numerics also take tar_feat as
+        the query planes (2, B, 256, Cp) f16 the ViT wrote itself (AENet.forward_planes): only the patch masks are left to make."""
+        if self.numerics == "split" and tar_feat.dtype == torch.float16:
+            if tar_feat.dim() != 4 or tar_feat.shape[0] != 2 or tar_feat.shape[2] != P or not tar_feat.is_contiguous():
+                raise ValueError(f"query planes must be a contiguous (2, B, 256, Cp) f16 tensor, got {tuple(tar_feat.shape)}")
+            query = (tar_feat[0], tar_feat[1])
+            qmask = patch_masks(tar_mask)
+        elif self.numerics == "split":   # normalise + split + the patch masks in ONE launch
             hi, lo, qmask = normalize_split(tar_feat.reshape(tar_feat.shape[0], tar_feat.shape[1], P), tar_mask)
             query = (hi, lo)
         else:

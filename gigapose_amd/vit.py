@@ -334,9 +334,12 @@ class Dinov2ViT(nn.Module):
 
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
-    def patch_features(self, images, normalize=True, stop_after_layers=-1, plane_amax=None):
+    def patch_features(self, images, normalize=True, stop_after_layers=-1, plane_amax=None, matcher_planes=False):
         """images (B,3,224,224) f32 -> (B, C, 16, 16): x_prenorm[:, 1:] rearranged 'b (h w) c ->
-        b c h w' and (optionally) L2-normalised over C -- i.e. AENet.forward_by_chunk's result."""
+        b c h w' and (optionally) L2-normalised over C -- i.e. AENet.forward_by_chunk's result.
+        matcher_planes: instead, the split matcher's query planes of those normalised features, one f16 tensor (2, B, 256, C) =
+        (hi, lo) -- bit for bit what matching.normalize_split makes of the normalize=True result, written by the forward's last
+        kernel without the f32 tensor in between (gp_vit_forward_split2: normalize == 2)."""
         if images.shape[1:] != (3, 224, 224):
             raise ValueError(f"expected (B,3,224,224) crops, got {tuple(images.shape)}")
         device = images.device
@@ -346,7 +349,10 @@ class Dinov2ViT(nn.Module):
             self._pack(device)
         B = images.shape[0]
         x = images.contiguous().float()
-        out = torch.empty(B, self.dim, 16, 16, dtype=torch.float32, device=device)
+        if matcher_planes:
+            out = torch.empty(2, B, 256, self.dim, dtype=torch.float16, device=device)
+        else:
+            out = torch.empty(B, self.dim, 16, 16, dtype=torch.float32, device=device)
         if B == 0:
             return out
         ws, need = self._workspace(B, device)
@@ -357,7 +363,8 @@ class Dinov2ViT(nn.Module):
         _lib.call("gp_vit_forward_split2", _lib.ptr(x), _lib.i(B), _lib.i(self.dim), _lib.i(self.depth),
                   _lib.i(self.heads), _lib.i(self.mlp_dim), _lib.f(1e-6), table, _lib.i(len(tensors)),
                   split_table, _lib.i(len(split)), _lib.ptr(ws), ctypes.c_size_t(need), _lib.ptr(out),
-                  _lib.i(1 if normalize else 0), _lib.i(stop_after_layers), scales, _lib.ptr(plane_amax), _lib.stream_ptr())
+                  _lib.i(2 if matcher_planes else (1 if normalize else 0)), _lib.i(stop_after_layers), scales, _lib.ptr(plane_amax),
+                  _lib.stream_ptr())
         return out
 
     @torch.no_grad()

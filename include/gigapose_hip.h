@@ -103,7 +103,7 @@ int gp_match_tiles_dir(const float* query, const float* bank, const float* qmask
  * gp_match_tiles. */
 /* gp_l2norm_split_mask: the split normalisation and, in the same launch, the rows' 16 x 16 patch masks: patch_mask (rows, 256) f32 =
  * mask_img (rows, mask_h, mask_w) f32 sampled at pixel (i mask_h / 16, j mask_w / 16) = F.interpolate(mask, (16, 16)) nearest
- * (matching.py:222, 227); mask_img = patch_mask = NULL: the normalisation alone. */
+ * (matching.py:222, 227); mask_img = patch_mask = NULL: the normalisation alone; x = NULL (hi, lo unused): the patch masks alone. */
 int gp_l2norm_split_mask(const float* x, void* hi, void* lo, int rows, int C, const float* mask_img, int mask_h, int mask_w,
                          float* patch_mask, void* stream);
 int gp_match_tiles_split_dir(const void* q_hi, const void* q_lo, const void* b_hi, const void* b_lo, const float* qmask,
@@ -252,7 +252,12 @@ int gp_attention_split_scaled(const void* qkv_hi, const void* qkv_lo, void* out_
  *   plane_scales  HOST array [depth][4] or NULL (= all 8); each in [2^-10, 64];
  *   plane_amax    DEVICE array [depth][4] f32 or NULL; non-NULL = calibration pass: every plane producer records max |x| of what it
  *                 wrote (atomic max on the f32 bits; the caller zeroes it) -- gigapose_amd/vit.py picks s from it with headroom.
- * Consumers undo the scale exactly (out_scale = 1 / (64 s)); the range guard (GP_STATUS_SPLIT_RANGE) stays |s x| <= 65504. */
+ * Consumers undo the scale exactly (out_scale = 1 / (64 s)); the range guard (GP_STATUS_SPLIT_RANGE) stays |s x| <= 65504.
+ * normalize == 2 (either mode of the linear layers): `out_features` receives the split matcher's query planes instead of the f32
+ * features -- what gp_l2norm_split_mask makes of the normalize == 1 output, bit for bit (F.normalize over dim, the matcher's own
+ * F.normalize again, x 32, hi = f16(.), lo = f16(. - hi)): the hi plane (B, 256, dim) f16 followed by the lo plane (B, 256, dim) f16,
+ * the same B * dim * 256 * 4 bytes.  The non-finite guard of normalize != 0 holds.  The rows' patch masks are
+ * gp_l2norm_split_mask's with x == NULL. */
 int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int heads, int mlp_dim, float ln_eps,
                           const float* const* weights, int n_weights, const void* const* split, int n_split,
                           float* workspace, size_t workspace_bytes, float* out_features, int normalize,

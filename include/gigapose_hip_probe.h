@@ -51,6 +51,9 @@ int gp_gemm_planes256_timing(const void* a_hi, const void* a_lo, const void* b_h
 /* ---- ViT ---- */
 void gp_vit_set_ln_reg(int mode); /* plane path's LayerNorm: 1 (default) 32-token blocks, 16-token blocks when the launch has at most 128 of
                                      them; 2 always 32-token blocks; 0 the first-generation three-pass kernel (results identical) */
+void gp_vit_set_ln_live(int tokens); /* gp_layernorm_planes: only rows < tokens carry tokens, as in the forward (B * 257 of Mpad): blocks of
+                                        pure row padding do not run (those plane rows are zeroed), and 32-token blocks past a whole number of
+                                        resident rounds are folded into first-round blocks; <= 0 (default): all Mpad rows */
 void gp_vit_set_planes(int on);   /* split numerics: 1 (default; any value but 0) = activation planes + attention in split numerics where the
                                      shapes allow, 0 = f32 activations and the lock-step kernels */
 /* Stage entries of the f32 kernels gp_vit_forward runs whenever the plane path is not taken (chain numerics, ViT-S, ViT-L below 8 crops,
