@@ -54,6 +54,27 @@ __device__ __forceinline__ void gp_record_amax(float* amax, float mx_scaled, flo
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(amax), __float_as_uint(m * inv_scale));
 }
 
+// The `epilogue` argument of every GEMM entry point (include/gigapose_hip.h documents the numbers: they are C ABI).  Which codes a
+// kernel family builds is its launch function's business: gp_gemm.hip 0-5 and 8, gp_split.hip 0-5, gp_split256.hip 0-5 (f32
+// activations) and 0-7 (planes).
+enum GpEpilogue {
+    GP_EPI_NONE = 0,
+    GP_EPI_BIAS_I = 1,            // + bias[i]
+    GP_EPI_BIAS_I_GELU = 2,       // gelu_erf(acc + bias[i])                      (DINOv2 fc1)
+    GP_EPI_BIAS_I_SCALE_RES = 3,  // res[i][j] + scale[i] * (acc + bias[i])       (LayerScale + residual; D may alias res)
+    GP_EPI_BIAS_J = 4,            // + bias[j]                                    (token-major V)
+    GP_EPI_BIAS_I_RELU = 5,       // relu(acc + bias[i])                          (IST MLP)
+    GP_EPI_GELU_PLANES = 6,       // gelu(acc + bias[i]) as activation planes O[j][i] (x the plane scale, hi + lo): gp_split256.hip
+    GP_EPI_BIAS_I_PLANES = 7,     // acc + bias[i] as activation planes O[j][i]: gp_split256.hip
+    GP_EPI_EMBED = 8,             // ViT patch embedding, j = b * 256 + p: D[i][b * 257 + 1 + p] = (acc + bias[i]) + scale[i * 256 + p]
+                                  // (scale = pos_embed[1:]^T), D[i][b * 257] = res[i] (cls + pos[0]), D[i][J / 256 * 257 .. ldr) = 0: gp_gemm.hip
+};
+
+// Header of the stream-K scratch a forward shares between gp_gemm.hip (flags of kGpSkMaxSlots slots, then its error word) and the
+// 256-tile kernels (gp_tile256.h: their error word lies behind)
+constexpr int kGpSkMaxSlots = 1024;
+constexpr size_t kGpSkHeaderBytes = 8192;
+
 // set by every entry point on failure; read through gp_last_error()
 void gp_set_error(const char* fmt, ...);
 

@@ -11,19 +11,18 @@
 //     zeros through the buffer descriptor's range check);
 //   * tile 256 pixels (i) x 64 NI output channels (j), NI = 2, 3, 4 for Cout = 128, 192, >= 256: 8 waves as 4 x 2, wave
 //     tile 64 x 32 NI, ONE accumulator, k-step 32, two LDS buffers, the two wave groups half a k-step apart with one
-//     barrier per step (the loop of gemm_planes256_kernel);
+//     barrier per step (gp_tile256.h's gp_two_group_loop);
 //     (a 512 x 128 tile with the waves as 8 x 1 -- the plane GEMM's 48 matrix instructions per wave and k-step for
 //     Cout = 128, all 160 KiB of LDS -- was built and measured: bit-identical, no faster: 2.76 us per k-step against 2 x
 //     1.33, the loop is bound by the global -> LDS staging rate per CU, not by LDS reads; DESIGN.md, negative results)
-//   * work distribution of gemm_planes256_kernel: data-parallel rounds of whole tiles per XCD chunk, a stream-K remainder
+//   * work distribution of gp_tile256.h's GpSlotPlan: data-parallel rounds of whole tiles per XCD chunk, a stream-K remainder
 //     with deterministic accumulator hand-overs when the tile count does not fill the slots evenly (layer4 at B = 64:
 //     128 tiles on 256 slots -> every tile is cut in two k halves);
 //   * epilogue through LDS (per wave, 32 pixel rows at a time): eval-BatchNorm alpha / beta, residual (planes), ReLU,
 //     output planes (npix, Cout) with 8 contiguous bytes per lane and 256-byte row segments per 32 lanes -- or f32 NCHW for
 //     the last layer.
-#include "gp_common.h"
+#include "gp_tile256.h"
 
-typedef _Float16 c16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 c16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int cu32x2 __attribute__((ext_vector_type(2)));
@@ -32,47 +31,10 @@ namespace {
 
 constexpr float kActScale = 8.0f, kOutScale = 1.0f / (8.0f * 64.0f);
 
-// Thin plane arithmetic of the tile epilogues (round 4, as gp_split256.hip's): the same bits with fewer vector instructions.
-//   cv_sum_planes: (float)h + (float)l of a residual's two planes -- exact in f32 -- as ONE v_fma_mix_f32 reading both f16 halves in place;
-//   cv_hi_pair / cv_lo_pair: a pair's hi plane by v_cvt_pk_f16_f32, its lo plane f16(v - hi) by v_fma_mixlo / mixhi_f16 (v - hi is exact);
-//   cv_absmax: v_maximum3_f32 over |v| (propagates NaN) as the range guard.
-template <int HALF>
-__device__ __forceinline__ float cv_sum_planes(unsigned h, unsigned l)
-{
-    float r;
-    if (HALF == 0) asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "v"(l));
-    else asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "v"(l));
-    return r;
-}
-__device__ __forceinline__ unsigned cv_hi_pair(float v0, float v1)
-{
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 h;
-    h[0] = (_Float16)v0;
-    h[1] = (_Float16)v1;
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ unsigned cv_lo_pair(float v0, float v1, unsigned hi)
-{
-    unsigned lo;
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(lo)
-        : "v"(v0), "v"(v1), "v"(hi));
-    return lo;
-}
-__device__ __forceinline__ float cv_absmax(float m, float v0, float v1)
-{
-    return __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(__builtin_fabsf(v0), __builtin_fabsf(v1)));
-}
-constexpr int CT = 256, CBK = 32, CNT = 512;
-constexpr int CROW = 32, CPLANE = CT * CROW;  // halfs
-constexpr int CBUF = 4 * CPLANE;              // A hi, A lo, B hi, B lo (B uses 64 NI of its 256 rows)
-constexpr int kSlots = 256, kErrWord = 1025;
-constexpr size_t kHeaderBytes = 8192;
-constexpr size_t kFragFloats = (size_t)CT * CT;
-constexpr int kSpin = 400000;
-constexpr unsigned kOob = 0x80000000u;        // buffer offset beyond every plane: the load returns zeros
+// thin plane arithmetic of the tile epilogue (gp_sum_planes, gp_hi_pair, gp_lo_pair, gp_absmax3): gp_tile256.h
+constexpr int CT = 256, CBK = 32, CNT = kTileThreads;
+constexpr int CROW = kRowHalfs;  // halfs per LDS row
+static_assert(kFragFloats == (size_t)CT * CT, "a slot's scratch fragment holds a tile's accumulators");
 
 struct ConvPArgs {
     const _Float16* xhi; const _Float16* xlo;   // (B, H, W, Cin) x 8
@@ -88,7 +50,108 @@ struct ConvPArgs {
     unsigned long long* trace;  // probe (gp_conv2d_planes_set_trace): per slot 8 words -- segments, k-steps, 100 MHz ticks in prologue / k loop / tail
 };
 
-__device__ __forceinline__ int toff(int row, int kc) { return row * CROW + ((kc ^ ((row >> 2) & 3)) << 3); }
+// ---- The tile epilogue of both convolution kernels, through LDS: per wave 32 pixel rows x 32 NI channels of f32 at a time (round mi of
+// the wave tile in the wave-private region wl), then per lane 4 NI items of four channels: eval-BatchNorm alpha | beta, residual (planes),
+// ReLU, output planes (npix, Cout) with 8 contiguous bytes per lane -- or f32 NCHW for the last layer.  j_base: first channel of the wave
+// tile; pix_of(r): the output pixel of row r (< 256) of the tile; AB_STASH: 2 x 8 NI quads of the wave's LDS behind wl (NI = 3 only).
+template <int NIW, class PixOf>
+__device__ __forceinline__ void conv_epilogue(const ConvPArgs& a, f32x16 (&acc)[2][NIW], float* wl, float* const AB_STASH, int j_base, int wr, int ln,
+                                              __amdgpu_buffer_rsrc_t r_rhi, __amdgpu_buffer_rsrc_t r_rlo, int OHW, PixOf pix_of)
+{
+    const int l31 = ln & 31;
+    constexpr int WC = 32 * NIW, QPR = 8 * NIW;  // f32 columns / 4-column quads per row of the wave tile
+    float mx = 0.f;  // range guard: largest |8 x| written (v_maximum3_f32 propagates NaN)
+    // eval-BatchNorm alpha | beta of the channels a lane finishes: item `it` of a lane is quad (ln + 64 it) % QPR of its row -- ONE quad
+    // for 16 / 32 quads per row (NI = 2 / 4) -- so they are loaded once per tile.  (Round 6: read inside the item loop they were two
+    // 16-byte global loads + s_waitcnt vmcnt(0) PER ITEM -- the stores to the output planes may alias them as far as hipcc knows -- i.e.
+    // 16 dependent round trips per tile, each also waiting for the previous item's stores.)
+    // (24 quads per row, NI = 3: three quads per lane = 24 registers, which the 192-channel builds do not have -- 7 spilled when tried;
+    // there the wave parks its 24 + 24 quads in LDS behind its epilogue region -- AB_STASH -- and an item reads its two from there.)
+    constexpr bool kHoist = 64 % QPR == 0;
+    f32x4 al_ = {1.f, 1.f, 1.f, 1.f}, be_ = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (kHoist) {
+        const int co_l = j_base + 4 * (ln % QPR);
+        if (a.alpha && co_l < a.Cout) {
+            al_ = *reinterpret_cast<const f32x4*>(a.alpha + co_l);
+            be_ = *reinterpret_cast<const f32x4*>(a.beta + co_l);
+        }
+    } else if (a.alpha && ln < 2 * QPR) {   // lanes 0 .. 23: alpha quads, 24 .. 47: beta quads
+        const int qd_l = ln < QPR ? ln : ln - QPR, co_l = j_base + 4 * qd_l;
+        f32x4 t = {0.f, 0.f, 0.f, 0.f};
+        if (co_l < a.Cout) t = *reinterpret_cast<const f32x4*>((ln < QPR ? a.alpha : a.beta) + co_l);
+        *reinterpret_cast<f32x4*>(AB_STASH + 4 * ln) = t;
+    }
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+        for (int ni = 0; ni < NIW; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) wl[frag_row(r, ln) * WC + 32 * ni + l31] = acc[mi][ni][r];
+        // one unconditional use in straight-line code: hipcc then waits for alpha | beta HERE (under the LDS writes above), once -- behind the
+        // items' `co < Cout` branches its wait-count pass assumes them pending at every join and emits vmcnt(0) per item, i.e. a wait for
+        // the previous item's stores
+        if (kHoist && mi == 0) asm volatile("" : "+v"(al_), "+v"(be_));
+        // residual planes: the loads of a round of RG items up front (RG x 2 x 8 bytes per lane in flight).  Loaded inside
+        // the item loop, one dependent 8-byte load per item, they cost 16 us of a 25 us tile tail (tools/probe_conv_timeline.py).
+        constexpr int RG = NIW == 2 ? 8 : (NIW == 3 ? 6 : 4);  // items per round (divides 4 NIW); fewer where the accumulators leave fewer registers
+#pragma unroll
+        for (int it0 = 0; it0 < 4 * NIW; it0 += RG) {
+            cu32x2 rh[RG], rl[RG];
+            if (a.rhi) {
+#pragma unroll
+                for (int u = 0; u < RG; ++u) {
+                    const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
+                    const int pix = pix_of(64 * wr + 32 * mi + row), co = j_base + 4 * qd;
+                    const unsigned ob = co < a.Cout ? ((unsigned)pix * (unsigned)a.Cout + (unsigned)co) * 2u : kOob;  // one offset, both planes
+                    rh[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rhi, ob, 0, 0);
+                    rl[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rlo, ob, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RG; ++u) {
+                const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(wl + row * WC + 4 * qd);
+                const int pix = pix_of(64 * wr + 32 * mi + row), co = j_base + 4 * qd;
+                if (co < a.Cout) {
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = tv[e] * kOutScale;
+                    if (a.alpha) {
+                        const f32x4 al4 = kHoist ? al_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * qd), be4 = kHoist ? be_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * (QPR + qd));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = v[e] * al4[e] + be4[e];
+                    }
+                    const size_t o = (size_t)pix * a.Cout + co;
+                    if (a.rhi) {  // + residual: (h + l) / 8, exact, then ONE rounding -- the bits of ((float)h + (float)l) * (1 / 8) + v
+                        v[0] = __builtin_fmaf(gp_sum_planes<0>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[0]);
+                        v[1] = __builtin_fmaf(gp_sum_planes<1>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[1]);
+                        v[2] = __builtin_fmaf(gp_sum_planes<0>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[2]);
+                        v[3] = __builtin_fmaf(gp_sum_planes<1>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[3]);
+                    }
+                    if (a.relu)  // NaN-propagating maximum (v_maximum3_f32): fmaxf would hand the range guard below a 0 for a NaN
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
+                    if (a.of32) {  // (B, Cout, OH, OW): the last layer only
+                        const int b = pix / OHW, rem = pix - b * OHW;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a.of32[((size_t)b * a.Cout + co + e) * OHW + rem] = v[e];
+                    } else {
+                        const float s0 = v[0] * kActScale, s1 = v[1] * kActScale, s2 = v[2] * kActScale, s3 = v[3] * kActScale;
+                        cu32x2 oh, ol;
+                        oh[0] = gp_hi_pair(s0, s1);
+                        oh[1] = gp_hi_pair(s2, s3);
+                        ol[0] = gp_lo_pair(s0, s1, oh[0]);
+                        ol[1] = gp_lo_pair(s2, s3, oh[1]);
+                        mx = gp_absmax3(gp_absmax3(mx, s0, s1), s2, s3);
+                        *reinterpret_cast<cu32x2*>(a.ohi + o) = oh;
+                        *reinterpret_cast<cu32x2*>(a.olo + o) = ol;
+                    }
+                }
+            }
+        }
+    }
+    if (!(mx <= kSplitPlaneLimit)) gp_raise(a.status, GP_ST_SPLIT_RANGE_CONV);  // !(<=): NaN counts
+}
 
 template <int NI>
 __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
@@ -106,20 +169,9 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
     constexpr int JT = 64 * NI;  // output channels per tile
 
-    // ---- this slot's range of (tile, k-step) units inside its XCD's tile chunk (gemm_planes256_kernel's scheme)
-    const int p = blockIdx.x, x = p & 7, n = p >> 3, slots_x = gridDim.x >> 3;
-    const int T = a.tiles_i * a.tiles_j;
-    const int t_lo = (int)((long long)T * x / 8), n_t = (int)((long long)T * (x + 1) / 8) - t_lo;
-    const int nstep = a.K / CBK;
-    const int rounds_dp = (n_t / slots_x > 1) ? n_t / slots_x - 1 : 0;
-    const int n_dp = rounds_dp * slots_x;
-    const long long U = (long long)(n_t - n_dp) * nstep;
-    const long long u0 = U * n / slots_x, u1 = U * (n + 1) / slots_x;
-    const int ta = (int)(u0 / nstep), sa = (int)(u0 % nstep);
-    const int tb = (int)(u1 / nstep), sb = (int)(u1 % nstep);
-    const int n_head = sb > 0 ? 1 : 0, n_rest = sa > 0 ? 1 : 0;
-    const int first_whole = ta + n_rest;
-    const int n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest;
+    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h)
+    const GpSlotPlan plan(a.tiles_i * a.tiles_j, a.K / CBK, true, 0);
+    const int p = plan.p, n_seg = plan.n_seg;
 
     const unsigned x_bytes = (unsigned)a.B * a.H * a.W * a.Cin * 2u, w_bytes = (unsigned)a.Cout * a.K * 2u;
     const __amdgpu_buffer_rsrc_t r_xhi = __builtin_amdgcn_make_buffer_rsrc((void*)a.xhi, 0, x_bytes, 0x00020000);
@@ -130,7 +182,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
     const __amdgpu_buffer_rsrc_t r_rhi = __builtin_amdgcn_make_buffer_rsrc((void*)a.rhi, 0, r_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_rlo = __builtin_amdgcn_make_buffer_rsrc((void*)a.rlo, 0, r_bytes, 0x00020000);
     const int srow = tid >> 2, schunk = tid & 3;
-    const int wofs = toff(srow, schunk);
+    const int wofs = gp_swz(srow, schunk);
     const int OHW = a.OH * a.OW, cps = a.stem ? 1 : a.Cin / CBK;  // k-steps per tap
     cu32x4 ra_h[AH], ra_l[AH], rb_h[BH], rb_l[BH];
     // fragment addressing
@@ -142,12 +194,10 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
     unsigned long long tr_pro = 0, tr_loop = 0, tr_tail = 0, tr_steps = 0, tr_t0 = a.trace ? wall_clock64() : 0;
     const unsigned long long tr_begin = tr_t0;
     for (int seg = 0; seg < n_seg; ++seg) {
-        const bool is_dp = seg < rounds_dp;
-        const bool is_head = !is_dp && seg - rounds_dp < n_head;
-        const bool is_rest = !is_dp && n_rest && seg == n_seg - 1;
-        const int t = is_dp ? seg * slots_x + n : n_dp + (is_head ? tb : (is_rest ? ta : first_whole + seg - rounds_dp - n_head));
-        const int s0 = is_rest ? sa : 0, s1 = is_head ? sb : nstep;
-        const int q = t_lo + t;
+        const GpSlotPlan::Segment sg = plan.segment(seg);
+        const bool is_head = sg.is_head, is_rest = sg.is_rest;
+        const int s0 = sg.u0, s1 = sg.u1;
+        const int q = sg.tile;
         const int i0 = (q / a.tiles_j) * MT, j0 = (q % a.tiles_j) * JT;  // j fastest: the co tiles of one pixel tile are neighbours
 
         // ---- gather state of this thread's pixel rows (srow + 128 h): byte offset of (b, oy*stride-pad, ox*stride-pad, 0)
@@ -181,30 +231,8 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
 
         f32x16 acc[2][NIW];
         if (is_rest) {
-            if (tid == 0) {
-                int spins = 0;
-                while (__hip_atomic_load(a.flags + (p - 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                    __builtin_amdgcn_s_sleep(16);
-                    if (++spins > kSpin) {
-                        __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            __syncthreads();
-            const f32x4* w = reinterpret_cast<const f32x4*>(a.partial + (size_t)(p - 8) * kFragFloats) + tid * 32;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const f32x4 v = w[(mi * 4 + ni) * 4 + r4];
-                        acc[mi][ni][r4 * 4 + 0] = v[0]; acc[mi][ni][r4 * 4 + 1] = v[1];
-                        acc[mi][ni][r4 * 4 + 2] = v[2]; acc[mi][ni][r4 * 4 + 3] = v[3];
-                    }
+            gp_handoff_wait(a.flags, p - 8, p - 8, 8, a.epoch, a.status);
+            gp_frag_load<NIW>(acc, a.partial, p - 8);
         } else {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -260,178 +288,30 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
         __syncthreads();
         if (a.trace) { const unsigned long long t = wall_clock64(); tr_pro += t - tr_t0; tr_t0 = t; tr_steps += ns; }
 
-#define C_MFMA(A_, B_, mi, ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[mi], B_[ni], acc[mi][ni], 0, 0, 0)
         auto c_phase = [&](int s) __attribute__((always_inline)) {
             const _Float16* L = lds + (s & 1) * TBUF;
-            __builtin_amdgcn_s_setprio(1);
-            c16x8 ah[2], al[2], bh[NIW], bl[NIW], ch[2], cl[2], dh[NIW], dl[NIW];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ah[mi] = *reinterpret_cast<const c16x8*>(L + P_AHI + arow + mi * 32 * CROW + ak0);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) bh[ni] = *reinterpret_cast<const c16x8*>(L + P_BHI + brow + ni * 32 * CROW + bk0);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) bl[ni] = *reinterpret_cast<const c16x8*>(L + P_BLO + brow + ni * 32 * CROW + bk0);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) al[mi] = *reinterpret_cast<const c16x8*>(L + P_ALO + arow + mi * 32 * CROW + ak0);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ah, bh, 0, ni); C_MFMA(ah, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ah, bl, 0, ni); C_MFMA(ah, bl, 1, ni); }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ch[mi] = *reinterpret_cast<const c16x8*>(L + P_AHI + arow + mi * 32 * CROW + ak1);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) dh[ni] = *reinterpret_cast<const c16x8*>(L + P_BHI + brow + ni * 32 * CROW + bk1);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(al, bh, 0, ni); C_MFMA(al, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) dl[ni] = *reinterpret_cast<const c16x8*>(L + P_BLO + brow + ni * 32 * CROW + bk1);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) cl[mi] = *reinterpret_cast<const c16x8*>(L + P_ALO + arow + mi * 32 * CROW + ak1);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ch, dh, 0, ni); C_MFMA(ch, dh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ch, dl, 0, ni); C_MFMA(ch, dl, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(cl, dh, 0, ni); C_MFMA(cl, dh, 1, ni); }
-            __builtin_amdgcn_s_setprio(0);
+            const int a0[2] = {ak0, 32 * CROW + ak0}, a1[2] = {ak1, 32 * CROW + ak1};
+            gp_mfma3_step<NIW>(acc, L + P_AHI, L + P_ALO, arow, a0, a1, L + P_BHI, L + P_BLO, brow, bk0, bk1);
         };
         auto m_phase = [&](int slab) __attribute__((always_inline)) {  // stages `slab`, loads slab + 1
             if (slab < ns) stage(slab & 1);
             __builtin_amdgcn_sched_barrier(0);
             gload(min(slab + 1, ns - 1));
         };
-        //     waves 0-3:  C0 M1 | C1 M2 | ...          waves 4-7:  M1 C0 | M2 C1 | ...        (| = the one barrier per k-step)
-        if (grp) m_phase(1);
-        for (int s = 0; s < ns; ++s) {
-            c_phase(s);
-            if (grp && s + 1 < ns) __syncthreads();
-            m_phase(s + 1 + grp);
-            if (!grp && s + 1 < ns) __syncthreads();
-        }
-#undef C_MFMA
+        gp_two_group_loop(ns, grp, c_phase, m_phase);
         if (a.trace) { const unsigned long long t = wall_clock64(); tr_loop += t - tr_t0; tr_t0 = t; }
 
-        if (is_head) {  // publish the fragment for slot n + 1 (agent-scope release by one lane)
-            f32x4* w = reinterpret_cast<f32x4*>(a.partial + (size_t)p * kFragFloats) + tid * 32;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        f32x4 v;
-                        v[0] = acc[mi][ni][r4 * 4 + 0]; v[1] = acc[mi][ni][r4 * 4 + 1];
-                        v[2] = acc[mi][ni][r4 * 4 + 2]; v[3] = acc[mi][ni][r4 * 4 + 3];
-                        w[(mi * 4 + ni) * 4 + r4] = v;
-                    }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(a.flags + p, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        if (is_head) {  // publish the fragment for slot n + 1
+            gp_frag_publish<NIW>(acc, a.partial, p, a.flags, a.epoch, true);
         } else {
             // ---- epilogue through LDS: per wave 32 pixel rows x 32 NI channels of f32 at a time (16 KiB regions, wave-private)
             int tid_ = threadIdx.x;
             asm volatile("" : "+v"(tid_));
             __syncthreads();  // every wave has read its last operand fragments
-            const int ln = tid_ & 63, l31 = ln & 31;
             float* wl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + (tid_ >> 6) * 16384);
-            constexpr int WC = 32 * NIW, QPR = 8 * NIW;  // f32 columns / 4-column quads per row of the wave tile
-            float* const AB_STASH = wl + 32 * WC;        // NI = 3: 768 bytes behind the 12 KiB of the wave's 16 KiB region that a round uses
-            static_assert(NIW != 3 || 32 * WC * 4 + 8 * QPR * 4 <= 16384, "alpha | beta stash must fit the wave's region");
-            float mx = 0.f;  // range guard: largest |8 x| written (v_maximum3_f32 propagates NaN)
-            // eval-BatchNorm alpha | beta of the channels a lane finishes: item `it` of a lane is quad (ln + 64 it) % QPR of its row -- ONE quad
-            // for 16 / 32 quads per row (NI = 2 / 4) -- so they are loaded once per tile.  (Round 6: read inside the item loop they were two
-            // 16-byte global loads + s_waitcnt vmcnt(0) PER ITEM -- the stores to the output planes may alias them as far as hipcc knows -- i.e.
-            // 16 dependent round trips per tile, each also waiting for the previous item's stores.)
-            // (24 quads per row, NI = 3: three quads per lane = 24 registers, which the 192-channel builds do not have -- 7 spilled when tried;
-            // there the wave parks its 24 + 24 quads in LDS behind its epilogue region -- AB_STASH -- and an item reads its two from there.)
-            constexpr bool kHoist = 64 % QPR == 0;
-            f32x4 al_ = {1.f, 1.f, 1.f, 1.f}, be_ = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (kHoist) {
-                const int co_l = j0 + WC * wc + 4 * (ln % QPR);
-                if (a.alpha && co_l < a.Cout) {
-                    al_ = *reinterpret_cast<const f32x4*>(a.alpha + co_l);
-                    be_ = *reinterpret_cast<const f32x4*>(a.beta + co_l);
-                }
-            } else if (a.alpha && ln < 2 * QPR) {   // lanes 0 .. 23: alpha quads, 24 .. 47: beta quads
-                const int qd_l = ln < QPR ? ln : ln - QPR, co_l = j0 + WC * wc + 4 * qd_l;
-                f32x4 t = {0.f, 0.f, 0.f, 0.f};
-                if (co_l < a.Cout) t = *reinterpret_cast<const f32x4*>((ln < QPR ? a.alpha : a.beta) + co_l);
-                *reinterpret_cast<f32x4*>(AB_STASH + 4 * ln) = t;
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) wl[frag_row(r, ln) * WC + 32 * ni + l31] = acc[mi][ni][r];
-                // one unconditional use in straight-line code: hipcc then waits for alpha | beta HERE (under the LDS writes above), once -- behind the
-                // items' `co < Cout` branches its wait-count pass assumes them pending at every join and emits vmcnt(0) per item, i.e. a wait for
-                // the previous item's stores
-                if (kHoist && mi == 0) asm volatile("" : "+v"(al_), "+v"(be_));
-                // residual planes: the loads of a round of RG items up front (RG x 2 x 8 bytes per lane in flight).  Loaded inside
-                // the item loop, one dependent 8-byte load per item, they cost 16 us of a 25 us tile tail (tools/probe_conv_timeline.py).
-                constexpr int RG = NIW == 2 ? 8 : (NIW == 3 ? 6 : 4);  // items per round (divides 4 NIW); fewer where the accumulators leave fewer registers
-#pragma unroll
-                for (int it0 = 0; it0 < 4 * NIW; it0 += RG) {
-                    cu32x2 rh[RG], rl[RG];
-                    if (a.rhi) {
-#pragma unroll
-                        for (int u = 0; u < RG; ++u) {
-                            const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
-                            const int pix = i0 + 64 * wr + 32 * mi + row, co = j0 + WC * wc + 4 * qd;
-                            const unsigned ob = co < a.Cout ? ((unsigned)pix * (unsigned)a.Cout + (unsigned)co) * 2u : kOob;  // one offset, both planes
-                            rh[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rhi, ob, 0, 0);
-                            rl[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rlo, ob, 0, 0);
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < RG; ++u) {
-                        const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
-                        const f32x4 tv = *reinterpret_cast<const f32x4*>(wl + row * WC + 4 * qd);
-                        const int pix = i0 + 64 * wr + 32 * mi + row, co = j0 + WC * wc + 4 * qd;
-                        if (co < a.Cout) {
-                            float v[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = tv[e] * kOutScale;
-                            if (a.alpha) {
-                                const f32x4 al4 = kHoist ? al_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * qd), be4 = kHoist ? be_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * (QPR + qd));
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = v[e] * al4[e] + be4[e];
-                            }
-                            const size_t o = (size_t)pix * a.Cout + co;
-                            if (a.rhi) {  // + residual: (h + l) / 8, exact, then ONE rounding -- the bits of ((float)h + (float)l) * (1 / 8) + v
-                                v[0] = __builtin_fmaf(cv_sum_planes<0>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[0]);
-                                v[1] = __builtin_fmaf(cv_sum_planes<1>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[1]);
-                                v[2] = __builtin_fmaf(cv_sum_planes<0>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[2]);
-                                v[3] = __builtin_fmaf(cv_sum_planes<1>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[3]);
-                            }
-                            if (a.relu)  // NaN-propagating maximum (v_maximum3_f32): fmaxf would hand the range guard below a 0 for a NaN
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
-                            if (a.of32) {  // (B, Cout, OH, OW): the last layer only
-                                const int b = pix / OHW, rem = pix - b * OHW;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) a.of32[((size_t)b * a.Cout + co + e) * OHW + rem] = v[e];
-                            } else {
-                                const float s0 = v[0] * kActScale, s1 = v[1] * kActScale, s2 = v[2] * kActScale, s3 = v[3] * kActScale;
-                                cu32x2 oh, ol;
-                                oh[0] = cv_hi_pair(s0, s1);
-                                oh[1] = cv_hi_pair(s2, s3);
-                                ol[0] = cv_lo_pair(s0, s1, oh[0]);
-                                ol[1] = cv_lo_pair(s2, s3, oh[1]);
-                                mx = cv_absmax(cv_absmax(mx, s0, s1), s2, s3);
-                                *reinterpret_cast<cu32x2*>(a.ohi + o) = oh;
-                                *reinterpret_cast<cu32x2*>(a.olo + o) = ol;
-                            }
-                        }
-                    }
-                }
-            }
-            if (!(mx <= kSplitPlaneLimit)) gp_raise(a.status, GP_ST_SPLIT_RANGE_CONV);  // !(<=): NaN counts
+            static_assert(NIW != 3 || 32 * 32 * NIW * 4 + 8 * 8 * NIW * 4 <= 16384, "alpha | beta stash must fit the wave's region");
+            // (NI = 3: the stash is the 768 bytes behind the 12 KiB of the wave's 16 KiB region that a round uses)
+            conv_epilogue<NIW>(a, acc, wl, wl + 32 * 32 * NIW, j0 + 32 * NIW * wc, wr, tid_ & 63, r_rhi, r_rlo, OHW, [&](int row) { return i0 + row; });
             __syncthreads();  // LDS buffer 0 is re-staged by the next segment's prologue
         }
         if (a.trace) { const unsigned long long t = wall_clock64(); tr_tail += t - tr_t0; tr_t0 = t; }
@@ -454,20 +334,15 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
 // per step, L2-resident) are staged per step.  The halo of the next channel block arrives during the first taps of the
 // current one (two halo buffers).  Global -> LDS bytes per k-step at Cout = 128: 48 KB -> 20.6 KB.
 // Same wave layout (4 x 2 waves, wave tile 64 pixels x 32 NI channels), same two-group half-step offset with one barrier per
-// step, same epilogue and hand-over scheme as conv_planes_kernel; stream-K units are channel blocks (9 steps each).
+// step, same epilogue and hand-over scheme as conv_planes_kernel (gp_tile256.h); stream-K units are channel blocks (9 steps each).
 // Per output the products are those of conv_planes_kernel summed in the order (channel block, tap) instead of (tap, channel
 // block): results agree to f32 round-off, not bit for bit (tests: both against float64).
 constexpr int HPX = 18 * 18;                 // halo pixels of a 16 x 16 output block
 constexpr int HPLANE = HPX * CROW;           // halfs per halo plane (64-byte rows)
 constexpr int HBUF = 2 * HPLANE;             // hi + lo
 
-__device__ __forceinline__ int hoff(int hp, int kc) { return hp * CROW + ((kc ^ ((hp >> 2) & 3)) << 3); }
-
-// PAR (fewer tiles than slots: layer3 / layer4 below 64 crops, layer4 always): S = floor(slots / tiles) slots per tile, each an equal
-// share of the tile's channel blocks from a zero accumulator, all at once; all but the last publish their partial accumulator, the
-// slot holding the last range adds them in slot order (deterministic) and runs the epilogue -- gemm_planes256_kernel's scheme.  The
-// serial hand-over (PAR = false) keeps a split tile's summation order but serialises its slots: layer4's 128 tiles on 256 slots
-// took as long as whole tiles.
+// PAR (fewer tiles than slots: layer3 / layer4 below 64 crops, layer4 always): the slots of a tile split its channel blocks in
+// parallel (GpSlotPlan); PAR = false: the serial hand-over -- layer4's 128 tiles on 256 slots took as long as whole tiles.
 template <int NI, bool PAR>
 __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
 {
@@ -485,29 +360,12 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
 
-    // ---- this slot's range of (tile, channel-block) units inside its XCD's tile chunk (conv_planes_kernel's scheme)
-    const int p = blockIdx.x, x = p & 7, n = p >> 3, slots_x = gridDim.x >> 3;
-    const int T = a.tiles_i * a.tiles_j;
-    const int t_lo = (int)((long long)T * x / 8), n_t = (int)((long long)T * (x + 1) / 8) - t_lo;
-    const int ncb = a.Cin / CBK;
-    const int rounds_dp = (!PAR && n_t / slots_x > 1) ? n_t / slots_x - 1 : 0;
-    const int n_dp = rounds_dp * slots_x;
-    const long long U = (long long)(n_t - n_dp) * ncb;
-    long long u0 = U * n / slots_x, u1 = U * (n + 1) / slots_x;
-    const int par_S = PAR ? min(min(max(1, slots_x / max(n_t, 1)), ncb), max(1, a.par_cap)) : 1;
-    if (PAR) {
-        const int tile = n / par_S, part = n - tile * par_S;
-        u0 = u1 = 0;
-        if (tile < n_t) {
-            u0 = (long long)tile * ncb + ncb * part / par_S;
-            u1 = (long long)tile * ncb + ncb * (part + 1) / par_S;
-        }
-    }
-    const int ta = (int)(u0 / ncb), sa = (int)(u0 % ncb);
-    const int tb = (int)(u1 / ncb), sb = (int)(u1 % ncb);
-    const int n_head = sb > 0 ? 1 : 0, n_rest = sa > 0 ? 1 : 0;
-    const int first_whole = ta + n_rest;
-    const int n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest;
+    // ---- this slot's segments: (tile, channel-block) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h); PAR: at most
+    // par_cap slots per tile (the host's cap: channel blocks per slot) and no more than the tile has channel blocks
+    const int T = a.tiles_i * a.tiles_j, ncb = a.Cin / CBK;
+    const int par_S = PAR ? min(min(max(1, (int)(gridDim.x >> 3) / max(GpSlotPlan::chunk_tiles(T), 1)), ncb), max(1, a.par_cap)) : 0;
+    const GpSlotPlan plan(T, ncb, !PAR, par_S);
+    const int p = plan.p, x = plan.x, n = plan.n, n_seg = plan.n_seg;
 
     const unsigned x_bytes = (unsigned)a.B * a.H * a.W * a.Cin * 2u, w_bytes = (unsigned)a.Cout * a.K * 2u;
     const __amdgpu_buffer_rsrc_t r_xhi = __builtin_amdgcn_make_buffer_rsrc((void*)a.xhi, 0, x_bytes, 0x00020000);
@@ -518,7 +376,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
     const __amdgpu_buffer_rsrc_t r_rhi = __builtin_amdgcn_make_buffer_rsrc((void*)a.rhi, 0, r_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_rlo = __builtin_amdgcn_make_buffer_rsrc((void*)a.rlo, 0, r_bytes, 0x00020000);
     const int srow = tid >> 2, schunk = tid & 3;
-    const int wofs = toff(srow, schunk);
+    const int wofs = gp_swz(srow, schunk);
     const int nbx = a.OW >> 4, nby = a.OH >> 4, OHW = a.OH * a.OW;
     cu32x4 rb_h[BH], rb_l[BH], rh_h, rh_l;
     // fragment addressing: A rows = halo pixels of this lane's two output pixels, B rows as conv_planes_kernel
@@ -534,13 +392,11 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
 
     unsigned long long tr_pro = 0, tr_loop = 0, tr_tail = 0, tr_steps = 0, tr_t0 = a.trace ? wall_clock64() : 0;
     const unsigned long long tr_begin = tr_t0;
-    for (int seg = 0; seg < n_seg; ++seg) {
-        const bool is_dp = seg < rounds_dp;
-        const bool is_head = !is_dp && seg - rounds_dp < n_head;
-        const bool is_rest = !is_dp && n_rest && seg == n_seg - 1;
-        const int t = is_dp ? seg * slots_x + n : n_dp + (is_head ? tb : (is_rest ? ta : first_whole + seg - rounds_dp - n_head));
-        const int c0 = is_rest ? sa : 0, c1 = is_head ? sb : ncb;  // channel blocks [c0, c1)
-        const int q = t_lo + t;
+    for (int seg = 0; seg < plan.n_seg; ++seg) {
+        const GpSlotPlan::Segment sg = plan.segment(seg);
+        const bool is_head = sg.is_head, is_rest = sg.is_rest;
+        const int c0 = sg.u0, c1 = sg.u1;  // channel blocks [c0, c1)
+        const int q = sg.tile;
         const int ti = q / a.tiles_j, j0 = (q % a.tiles_j) * JT;    // j fastest: the co tiles of one pixel block are neighbours
         const int b = ti / (nby * nbx), rb_ = ti - b * (nby * nbx);
         const int by = rb_ / nbx, bx = rb_ - by * nbx;
@@ -555,7 +411,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
             const int iy = by * 16 - 1 + hp / 18, ix = bx * 16 - 1 + hp % 18;
             const bool ok = i < 4 * HPX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             hvoff[u] = ok ? (unsigned)(((b * a.H + iy) * a.W + ix) * a.Cin) * 2u + (unsigned)ck * 16u : kOob;
-            hlds[u] = i < 4 * HPX ? hoff(hp, ck) : -1;
+            hlds[u] = i < 4 * HPX ? gp_swz(hp, ck) : -1;
         }
         // weights: rows j0 + srow (+128) of (Cout, K); rows past Cout read as zeros
         unsigned wvoff[BH];
@@ -567,33 +423,8 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
 
         f32x16 acc[2][NIW];
         if (!PAR && is_rest) {
-            if (tid == 0) {
-                int spins = 0;
-                while (__hip_atomic_load(a.flags + (p - 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                    __builtin_amdgcn_s_sleep(16);
-                    if (++spins > kSpin) {
-                        __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            __syncthreads();
-            // piece u of thread tid at [u][tid]; buffer loads: one lane offset + a scalar offset per piece (no address pair per piece)
-            const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)(p - 8) * kFragFloats), 0,
-                                                                                 (int)(kFragFloats * sizeof(float)), 0x00020000);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const cu32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rf, (unsigned)tid * 16u, (unsigned)(((mi * 4 + ni) * 4 + r4) * CNT) * 16u, 0);
-                        const f32x4 vf = __builtin_bit_cast(f32x4, v);  // whole-vector cast (element-wise __builtin_bit_cast of vector lanes miscompiles: every r4 got lane group 0)
-                        acc[mi][ni][r4 * 4 + 0] = vf[0]; acc[mi][ni][r4 * 4 + 1] = vf[1];
-                        acc[mi][ni][r4 * 4 + 2] = vf[2]; acc[mi][ni][r4 * 4 + 3] = vf[3];
-                    }
+            gp_handoff_wait(a.flags, p - 8, p - 8, 8, a.epoch, a.status);
+            gp_frag_load<NIW>(acc, a.partial, p - 8);
         } else {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -649,50 +480,19 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
         __syncthreads();
         if (a.trace) { const unsigned long long t_ = wall_clock64(); tr_pro += t_ - tr_t0; tr_t0 = t_; tr_steps += ns; }
 
-#define C_MFMA(A_, B_, mi, ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[mi], B_[ni], acc[mi][ni], 0, 0, 0)
         auto c_phase = [&](int s) __attribute__((always_inline)) {
             const int cbr = s / 9, tap = s - cbr * 9;                  // wave-uniform
             const int dy = tap / 3, tofs = dy * 18 + (tap - dy * 3);
             const _Float16* LH = Hb + ((c0 + cbr) & 1) * HBUF;
             const _Float16* LW = Wb + (s & 1) * WBUF;
-            __builtin_amdgcn_s_setprio(1);
-            int a0[2], a1[2];
+            int a0[2], a1[2];  // the A fragments: the halo rows of this lane's two output pixels, shifted by the tap
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
                 const int hp = hbase[mi] + tofs;
-                a0[mi] = hoff(hp, kh_);
-                a1[mi] = hoff(hp, kh_ + 2);
+                a0[mi] = gp_swz(hp, kh_);
+                a1[mi] = gp_swz(hp, kh_ + 2);
             }
-            c16x8 ah[2], al[2], bh[NIW], bl[NIW], ch[2], cl[2], dh[NIW], dl[NIW];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ah[mi] = *reinterpret_cast<const c16x8*>(LH + a0[mi]);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) bh[ni] = *reinterpret_cast<const c16x8*>(LW + brow + ni * 32 * CROW + bk0);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) bl[ni] = *reinterpret_cast<const c16x8*>(LW + WPLANE + brow + ni * 32 * CROW + bk0);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) al[mi] = *reinterpret_cast<const c16x8*>(LH + HPLANE + a0[mi]);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ah, bh, 0, ni); C_MFMA(ah, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ah, bl, 0, ni); C_MFMA(ah, bl, 1, ni); }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ch[mi] = *reinterpret_cast<const c16x8*>(LH + a1[mi]);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) dh[ni] = *reinterpret_cast<const c16x8*>(LW + brow + ni * 32 * CROW + bk1);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(al, bh, 0, ni); C_MFMA(al, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) dl[ni] = *reinterpret_cast<const c16x8*>(LW + WPLANE + brow + ni * 32 * CROW + bk1);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) cl[mi] = *reinterpret_cast<const c16x8*>(LH + HPLANE + a1[mi]);
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ch, dh, 0, ni); C_MFMA(ch, dh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(ch, dl, 0, ni); C_MFMA(ch, dl, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NIW; ++ni) { C_MFMA(cl, dh, 0, ni); C_MFMA(cl, dh, 1, ni); }
-            __builtin_amdgcn_s_setprio(0);
+            gp_mfma3_step<NIW>(acc, LH, LH + HPLANE, 0, a0, a1, LW, LW + WPLANE, brow, bk0, bk1);
         };
         // m_phase(slab): stages the weights of `slab` (loaded one phase earlier) and requests those of slab + 1; the halo of the NEXT
         // channel block rides on the phases of taps 1..3 of the current one: item u requested in the phase of tap u + 1 (after the
@@ -709,177 +509,27 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
             wload(min(slab + 1, ns - 1));
             if (slab < ns && more && tap >= 1 && tap <= 3) hload(c0 + cbr + 1, tap - 1);
         };
-        //     waves 0-3:  C0 M1 | C1 M2 | ...          waves 4-7:  M1 C0 | M2 C1 | ...        (| = the one barrier per k-step)
-        if (grp) m_phase(1);
-        for (int s = 0; s < ns; ++s) {
-            c_phase(s);
-            if (grp && s + 1 < ns) __syncthreads();
-            m_phase(s + 1 + grp);
-            if (!grp && s + 1 < ns) __syncthreads();
-        }
-#undef C_MFMA
+        gp_two_group_loop(ns, grp, c_phase, m_phase);
         if (a.trace) { const unsigned long long t_ = wall_clock64(); tr_loop += t_ - tr_t0; tr_t0 = t_; }
 
-        if (is_head) {  // publish the fragment for slot n + 1 (write-through stores, then the flag)
-            const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)p * kFragFloats), 0,
-                                                                                 (int)(kFragFloats * sizeof(float)), 0x00020000);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        f32x4 vf;
-                        vf[0] = acc[mi][ni][r4 * 4 + 0]; vf[1] = acc[mi][ni][r4 * 4 + 1];
-                        vf[2] = acc[mi][ni][r4 * 4 + 2]; vf[3] = acc[mi][ni][r4 * 4 + 3];
-                        const cu32x4 v = __builtin_bit_cast(cu32x4, vf);
-                        __builtin_amdgcn_raw_buffer_store_b128(v, rf, (unsigned)tid * 16u, (unsigned)(((mi * 4 + ni) * 4 + r4) * CNT) * 16u, 0);
-                    }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(a.flags + p, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        if (is_head) {  // publish the fragment for the slot that continues (or owns) the tile
+            gp_frag_publish<NIW>(acc, a.partial, p, a.flags, a.epoch, true);
             __syncthreads();  // the next segment's prologue rewrites the operand buffers
         } else {
             if (PAR && is_rest) {  // the owner of the tile: add the partial accumulators of the par_S - 1 slots before it, nearest first
                 const int m_lo = n - (par_S - 1);
-                if (tid == 0) {
-                    for (int m = n - 1; m >= m_lo; --m) {
-                        int spins = 0;
-                        while (__hip_atomic_load(a.flags + (x + 8 * m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                            __builtin_amdgcn_s_sleep(16);
-                            if (++spins > kSpin) {
-                                __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                                break;
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                }
-                __syncthreads();
-                for (int m = n - 1; m >= m_lo; --m) {
-                    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)(x + 8 * m) * kFragFloats), 0,
-                                                                                         (int)(kFragFloats * sizeof(float)), 0x00020000);
-#pragma unroll
-                    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                        for (int ni = 0; ni < NIW; ++ni) {
-                            cu32x4 v[4];
-#pragma unroll
-                            for (int r4 = 0; r4 < 4; ++r4)
-                                v[r4] = __builtin_amdgcn_raw_buffer_load_b128(rf, (unsigned)tid * 16u, (unsigned)(((mi * 4 + ni) * 4 + r4) * CNT) * 16u, 0);
-#pragma unroll
-                            for (int r4 = 0; r4 < 4; ++r4) {
-                                const f32x4 vf = __builtin_bit_cast(f32x4, v[r4]);
-                                acc[mi][ni][r4 * 4 + 0] += vf[0]; acc[mi][ni][r4 * 4 + 1] += vf[1];
-                                acc[mi][ni][r4 * 4 + 2] += vf[2]; acc[mi][ni][r4 * 4 + 3] += vf[3];
-                            }
-                        }
-                }
+                gp_handoff_wait(a.flags, x + 8 * (n - 1), x + 8 * m_lo, 8, a.epoch, a.status);
+                for (int m = n - 1; m >= m_lo; --m) gp_frag_add<NIW, 4>(acc, a.partial, x + 8 * m);
             }
-            // ---- epilogue through LDS (conv_planes_kernel's, with the block's pixel order)
+            // ---- epilogue through LDS (conv_epilogue, with the block's pixel order)
             int tid_ = threadIdx.x;
             asm volatile("" : "+v"(tid_));
             __syncthreads();  // every wave has read its last operand fragments
-            const int ln = tid_ & 63, l31 = ln & 31;
             constexpr int EPI_PITCH = EPI_STRIDE + (NIW == 3 ? 1024 : 0);   // NI = 3: + the wave's alpha | beta stash (a constant offset from wl: no register)
             static_assert(LDS_HALFS * 2 >= 8 * EPI_PITCH, "the epilogue regions (+ stashes) must fit the operand buffers");
             float* wl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + (tid_ >> 6) * EPI_PITCH);
-            constexpr int WC = 32 * NIW, QPR = 8 * NIW;
-            float* const AB_STASH = wl + EPI_STRIDE / 4;
-            float mx = 0.f;  // range guard: largest |8 x| written (v_maximum3_f32 propagates NaN)
-            // eval-BatchNorm alpha | beta of the channels a lane finishes: item `it` of a lane is quad (ln + 64 it) % QPR of its row -- ONE quad
-            // for 16 / 32 quads per row (NI = 2 / 4) -- so they are loaded once per tile.  (Round 6: read inside the item loop they were two
-            // 16-byte global loads + s_waitcnt vmcnt(0) PER ITEM -- the stores to the output planes may alias them as far as hipcc knows -- i.e.
-            // 16 dependent round trips per tile, each also waiting for the previous item's stores.)
-            // (24 quads per row, NI = 3: three quads per lane = 24 registers, which the 192-channel builds do not have -- 7 spilled when tried;
-            // there the wave parks its 24 + 24 quads in LDS behind its epilogue region -- AB_STASH -- and an item reads its two from there.)
-            constexpr bool kHoist = 64 % QPR == 0;
-            f32x4 al_ = {1.f, 1.f, 1.f, 1.f}, be_ = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (kHoist) {
-                const int co_l = j0 + WC * wc + 4 * (ln % QPR);
-                if (a.alpha && co_l < a.Cout) {
-                    al_ = *reinterpret_cast<const f32x4*>(a.alpha + co_l);
-                    be_ = *reinterpret_cast<const f32x4*>(a.beta + co_l);
-                }
-            } else if (a.alpha && ln < 2 * QPR) {   // lanes 0 .. 23: alpha quads, 24 .. 47: beta quads
-                const int qd_l = ln < QPR ? ln : ln - QPR, co_l = j0 + WC * wc + 4 * qd_l;
-                f32x4 t = {0.f, 0.f, 0.f, 0.f};
-                if (co_l < a.Cout) t = *reinterpret_cast<const f32x4*>((ln < QPR ? a.alpha : a.beta) + co_l);
-                *reinterpret_cast<f32x4*>(AB_STASH + 4 * ln) = t;
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-                for (int ni = 0; ni < NIW; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) wl[frag_row(r, ln) * WC + 32 * ni + l31] = acc[mi][ni][r];
-                // one unconditional use in straight-line code: hipcc then waits for alpha | beta HERE (under the LDS writes above), once -- behind the
-                // items' `co < Cout` branches its wait-count pass assumes them pending at every join and emits vmcnt(0) per item, i.e. a wait for
-                // the previous item's stores
-                if (kHoist && mi == 0) asm volatile("" : "+v"(al_), "+v"(be_));
-                constexpr int RG = NIW == 2 ? 8 : (NIW == 3 ? 6 : 4);
-#pragma unroll
-                for (int it0 = 0; it0 < 4 * NIW; it0 += RG) {
-                    cu32x2 rh[RG], rl[RG];
-                    if (a.rhi) {
-#pragma unroll
-                        for (int u = 0; u < RG; ++u) {
-                            const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
-                            const int pl = 64 * wr + 32 * mi + row, pix = pix00 + (pl >> 4) * a.OW + (pl & 15), co = j0 + WC * wc + 4 * qd;
-                            const unsigned ob = co < a.Cout ? ((unsigned)pix * (unsigned)a.Cout + (unsigned)co) * 2u : kOob;
-                            rh[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rhi, ob, 0, 0);
-                            rl[u] = __builtin_amdgcn_raw_buffer_load_b64(r_rlo, ob, 0, 0);
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < RG; ++u) {
-                        const int f = (it0 + u) * 64 + ln, row = f / QPR, qd = f - row * QPR;
-                        const f32x4 tv = *reinterpret_cast<const f32x4*>(wl + row * WC + 4 * qd);
-                        const int pl = 64 * wr + 32 * mi + row, pix = pix00 + (pl >> 4) * a.OW + (pl & 15), co = j0 + WC * wc + 4 * qd;
-                        if (co < a.Cout) {
-                            float v[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = tv[e] * kOutScale;
-                            if (a.alpha) {
-                                const f32x4 al4 = kHoist ? al_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * qd), be4 = kHoist ? be_ : *reinterpret_cast<const f32x4*>(AB_STASH + 4 * (QPR + qd));
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = v[e] * al4[e] + be4[e];
-                            }
-                            const size_t o = (size_t)pix * a.Cout + co;
-                            if (a.rhi) {  // + residual: (h + l) / 8, exact, then ONE rounding -- the bits of ((float)h + (float)l) * (1 / 8) + v
-                                v[0] = __builtin_fmaf(cv_sum_planes<0>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[0]);
-                                v[1] = __builtin_fmaf(cv_sum_planes<1>(rh[u][0], rl[u][0]), 1.0f / kActScale, v[1]);
-                                v[2] = __builtin_fmaf(cv_sum_planes<0>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[2]);
-                                v[3] = __builtin_fmaf(cv_sum_planes<1>(rh[u][1], rl[u][1]), 1.0f / kActScale, v[3]);
-                            }
-                            if (a.relu)  // NaN-propagating maximum (v_maximum3_f32): fmaxf would hand the range guard below a 0 for a NaN
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
-                            if (a.of32) {  // (B, Cout, OH, OW)
-                                const int bb = pix / OHW, rem = pix - bb * OHW;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) a.of32[((size_t)bb * a.Cout + co + e) * OHW + rem] = v[e];
-                            } else {
-                                const float s0 = v[0] * kActScale, s1 = v[1] * kActScale, s2 = v[2] * kActScale, s3 = v[3] * kActScale;
-                                cu32x2 oh, ol;
-                                oh[0] = cv_hi_pair(s0, s1);
-                                oh[1] = cv_hi_pair(s2, s3);
-                                ol[0] = cv_lo_pair(s0, s1, oh[0]);
-                                ol[1] = cv_lo_pair(s2, s3, oh[1]);
-                                mx = cv_absmax(cv_absmax(mx, s0, s1), s2, s3);
-                                *reinterpret_cast<cu32x2*>(a.ohi + o) = oh;
-                                *reinterpret_cast<cu32x2*>(a.olo + o) = ol;
-                            }
-                        }
-                    }
-                }
-            }
-            if (!(mx <= kSplitPlaneLimit)) gp_raise(a.status, GP_ST_SPLIT_RANGE_CONV);  // !(<=): NaN counts
+            conv_epilogue<NIW>(a, acc, wl, wl + EPI_STRIDE / 4, j0 + 32 * NIW * wc, wr, tid_ & 63, r_rhi, r_rlo, OHW,
+                               [&](int pl) { return pix00 + (pl >> 4) * a.OW + (pl & 15); });
             __syncthreads();  // the operand buffers are re-staged by the next segment's prologue
         }
         if (a.trace) { const unsigned long long t_ = wall_clock64(); tr_tail += t_ - tr_t0; tr_t0 = t_; }

@@ -14,17 +14,7 @@
 
 namespace {
 
-enum {
-    EPI_NONE = 0,
-    EPI_BIAS_I = 1,            // + bias[i]
-    EPI_BIAS_I_GELU = 2,       // gelu_erf(acc + bias[i])                      (DINOv2 fc1)
-    EPI_BIAS_I_SCALE_RES = 3,  // res[i][j] + scale[i] * (acc + bias[i])       (LayerScale + residual)
-    EPI_BIAS_J = 4,            // + bias[j]                                    (token-major V)
-    EPI_BIAS_I_RELU = 5,       // relu(acc + bias[i])                          (IST MLP)
-    // (6, 7: plane outputs of gp_split256.hip)
-    EPI_EMBED = 8,             // ViT patch embedding, j = b * 256 + p: D[i][b * 257 + 1 + p] = (acc + bias[i]) + scale[i * 256 + p]
-                               // (scale = pos_embed[1:]^T), D[i][b * 257] = res[i] (cls + pos[0]), D[i][J / 256 * 257 .. ldr) = 0
-};
+// epilogue codes: GpEpilogue (gp_common.h); built here: 0-5 and 8
 
 using GM = KMajor<2, 4, 2, 1, 16>;  // tile: 128 x 128, 8 waves (2 x 4), 32 accumulators/lane
 
@@ -34,10 +24,10 @@ __device__ __forceinline__ float gelu_erf(float x)
 }
 
 // stream-K scratch (device): [flags: kMaxSlots ints][error word ... padded to 8 KiB][kMaxSlots partial tiles]
-constexpr int kMaxSlots = 1024;  // resident workgroups: 4 per CU (<= 64 VGPR, 32 KiB LDS) x 256 CUs
-constexpr size_t kSkHeaderBytes = 8192;
+constexpr int kMaxSlots = kGpSkMaxSlots;  // 1024 resident workgroups: 4 per CU (<= 64 VGPR, 32 KiB LDS) x 256 CUs
+constexpr size_t kSkHeaderBytes = kGpSkHeaderBytes;
 constexpr size_t kSkPartialFloats = (size_t)GM::BM * GM::BN;
-constexpr int T_EMB = GP_P + 1;    // tokens per crop (EPI_EMBED)
+constexpr int T_EMB = GP_P + 1;    // tokens per crop (GP_EPI_EMBED)
 constexpr int kSpinLimit = 400000;  // x ~0.4 us: a lost hand-off ends in an error word, never in a hang
 
 struct GemmArgs {
@@ -87,25 +77,25 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, int i0, int j0,
         for (int r = 0; r < 16; ++r) {
             const int i = i0 + wm * 64 + mi * 32 + frag_row(r, lane);
             float v = acc[mi][0][r];
-            if (EPI == EPI_BIAS_I || EPI == EPI_BIAS_I_GELU || EPI == EPI_BIAS_I_SCALE_RES || EPI == EPI_BIAS_I_RELU || EPI == EPI_EMBED)
+            if (EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU || EPI == GP_EPI_EMBED)
                 v = v + bias[i];
-            if (EPI == EPI_BIAS_J) v = v + bias[j];
-            if (EPI == EPI_BIAS_I_GELU) v = gelu_erf(v);
-            if (EPI == EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+            if (EPI == GP_EPI_BIAS_J) v = v + bias[j];
+            if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_erf(v);
+            if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
             // 32-bit element offsets (I * ld < 2^31 is checked by the launcher): half the address VGPRs
-            if (EPI == EPI_BIAS_I_SCALE_RES) v = res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + scale[i] * v;
+            if (EPI == GP_EPI_BIAS_I_SCALE_RES) v = res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + scale[i] * v;
             // tokens = cat(cls, patches) + pos (HF modeling_dinov2.py:108-112) in the order of GEMM-then-add: (acc + bias) + pos;
             // column j = b * 256 + p lands on token b * 257 + 1 + p = j + b + 1
-            if (EPI == EPI_EMBED) v = v + scale[(unsigned)i * GP_P + (unsigned)(j & (GP_P - 1))];
-            D[(unsigned)i * (unsigned)a.ldd + (unsigned)(EPI == EPI_EMBED ? j + (j >> 8) + 1 : j)] = v;
+            if (EPI == GP_EPI_EMBED) v = v + scale[(unsigned)i * GP_P + (unsigned)(j & (GP_P - 1))];
+            D[(unsigned)i * (unsigned)a.ldd + (unsigned)(EPI == GP_EPI_EMBED ? j + (j >> 8) + 1 : j)] = v;
         }
         // keep the next tile's residual loads below this tile's stores (register pressure)
-        if (EPI == EPI_BIAS_I_SCALE_RES) __builtin_amdgcn_sched_barrier(0);
+        if (EPI == GP_EPI_BIAS_I_SCALE_RES) __builtin_amdgcn_sched_barrier(0);
     }
-    if (EPI == EPI_EMBED) {
+    if (EPI == GP_EPI_EMBED) {
         // a tile in which a crop starts (j0 % 256 == 0; BN = 128) also writes that crop's class-token column, one row per thread, and
         // the last j tile the zeros of the < 256 pad columns [257 B, ldr): no pass of their own (block-uniform branches)
-        static_assert(GM::BN == 128 && GM::BM <= GM::NT, "EPI_EMBED: one crop start per two j tiles, one class-token row per thread");
+        static_assert(GM::BN == 128 && GM::BM <= GM::NT, "GP_EPI_EMBED: one crop start per two j tiles, one class-token row per thread");
         int t2 = threadIdx.x;
         asm volatile("" : "+v"(t2));  // recomputed from scratch: nothing of this part lives through the stores above
         if ((j0 & (GP_P - 1)) == 0 && t2 < GM::BM) D[(unsigned)(i0 + t2) * (unsigned)a.ldd + (unsigned)(j0 + (j0 >> 8))] = res[i0 + t2];
@@ -282,31 +272,31 @@ int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, i
     GP_REQUIRE(((uintptr_t)sk_ws % 16 == 0), "gp_gemm_kmajor: stream-K scratch must be 16-byte aligned");
     GpProfScope prof(GP_PROF_GEMM, 2.0 * I * J * K, st);
     switch (epilogue) {
-        case EPI_NONE: launch<EPI_NONE>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st); break;
-        case EPI_BIAS_I:
+        case GP_EPI_NONE: launch<GP_EPI_NONE>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st); break;
+        case GP_EPI_BIAS_I:
             GP_REQUIRE(bias, "gp_gemm_kmajor: bias required");
-            launch<EPI_BIAS_I>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_BIAS_I>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
-        case EPI_BIAS_I_GELU:
+        case GP_EPI_BIAS_I_GELU:
             GP_REQUIRE(bias, "gp_gemm_kmajor: bias required");
-            launch<EPI_BIAS_I_GELU>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_BIAS_I_GELU>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
-        case EPI_BIAS_I_SCALE_RES:
+        case GP_EPI_BIAS_I_SCALE_RES:
             GP_REQUIRE(bias && scale && res && ldr >= J, "gp_gemm_kmajor: bias/scale/residual required");
-            launch<EPI_BIAS_I_SCALE_RES>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_BIAS_I_SCALE_RES>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
-        case EPI_BIAS_J:
+        case GP_EPI_BIAS_J:
             GP_REQUIRE(bias, "gp_gemm_kmajor: bias required");
-            launch<EPI_BIAS_J>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_BIAS_J>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
-        case EPI_BIAS_I_RELU:
+        case GP_EPI_BIAS_I_RELU:
             GP_REQUIRE(bias, "gp_gemm_kmajor: bias required");
-            launch<EPI_BIAS_I_RELU>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_BIAS_I_RELU>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
-        case EPI_EMBED:  // D has ldr = ldd >= 257 * (J / 256) columns, fewer than 256 of them padding
+        case GP_EPI_EMBED:  // D has ldr = ldd >= 257 * (J / 256) columns, fewer than 256 of them padding
             GP_REQUIRE(bias && scale && res && J % GP_P == 0 && ldr == ldd && ldd >= J / GP_P * T_EMB && ldd - J / GP_P * T_EMB < GP_P,
                        "gp_gemm_kmajor: bias / position table / class token and a (257 B + padding)-column output required");
-            launch<EPI_EMBED>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
+            launch<GP_EPI_EMBED>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
         default: GP_REQUIRE(false, "gp_gemm_kmajor: unknown epilogue %d", epilogue);
     }
@@ -346,7 +336,7 @@ extern "C" void gp_gemm_set_group(int g) { g_group = g > 0 ? g : 1; }
 extern "C" int gp_gemm_streamk_error(const float* scratch, void* stream)
 {
     int e = -1;
-    if (hipMemcpyAsync(&e, reinterpret_cast<const int*>(scratch) + 1024, sizeof(int), hipMemcpyDeviceToHost,
+    if (hipMemcpyAsync(&e, reinterpret_cast<const int*>(scratch) + kMaxSlots, sizeof(int), hipMemcpyDeviceToHost,
                        (hipStream_t)stream) != hipSuccess ||
         hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
         return -1;

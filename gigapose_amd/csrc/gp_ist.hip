@@ -162,15 +162,15 @@ int gp_ist_regress(const float* tar_feat, const float* src_bank, const int* labe
         const float* const* w = weights + head * 6;  // W1^T [2D][2H], b1, W2^T [2H][H], b2, W3 [nout][H], b3
         if (split) {  // split numerics (3 x f16 MFMA, gp_split.hip): the two hidden layers = 99 % of the head's flops
             const float* const* sp = weights + 12 + head * 4;
-            if ((rc = gp_gemm_split_launch_limited(X, (int)R, sp[0], sp[1], H1, (int)R, 2 * H, (int)R, 2 * D, 1, 5, w[1], nullptr, nullptr, 0, count, st)))
+            if ((rc = gp_gemm_split_launch_limited(X, (int)R, sp[0], sp[1], H1, (int)R, 2 * H, (int)R, 2 * D, 1, GP_EPI_BIAS_I_RELU, w[1], nullptr, nullptr, 0, count, st)))
                 return rc;
-            if ((rc = gp_gemm_split_launch_limited(H1, (int)R, sp[2], sp[3], H2, (int)R, H, (int)R, 2 * H, 1, 5, w[3], nullptr, nullptr, 0, count, st)))
+            if ((rc = gp_gemm_split_launch_limited(H1, (int)R, sp[2], sp[3], H2, (int)R, H, (int)R, 2 * H, 1, GP_EPI_BIAS_I_RELU, w[3], nullptr, nullptr, 0, count, st)))
                 return rc;
         } else {
-            if ((rc = gp_gemm_launch(w[0], 2 * H, X, (int)R, H1, (int)R, 2 * H, (int)R, 2 * D, 5, w[1], nullptr, nullptr,
+            if ((rc = gp_gemm_launch(w[0], 2 * H, X, (int)R, H1, (int)R, 2 * H, (int)R, 2 * D, GP_EPI_BIAS_I_RELU, w[1], nullptr, nullptr,
                                      0, nullptr, st)))
                 return rc;
-            if ((rc = gp_gemm_launch(w[2], H, H1, (int)R, H2, (int)R, H, (int)R, 2 * H, 5, w[3], nullptr, nullptr, 0,
+            if ((rc = gp_gemm_launch(w[2], H, H1, (int)R, H2, (int)R, H, (int)R, 2 * H, GP_EPI_BIAS_I_RELU, w[3], nullptr, nullptr, 0,
                                      nullptr, st)))
                 return rc;
         }

@@ -13,7 +13,7 @@
 // Layouts: same as gp_gemm.hip on the outside -- activations f32 k-major X[K][n] (converted while staging),
 // result f32 D[I][ldd] -- plus PRE-SPLIT weights: gp_split_weights() turns W^T [K][n] f32 into two f16 planes
 // [n][K] (k contiguous: the MFMA operand is 8 consecutive k per lane).
-#include "gp_common.h"
+#include "gp_tile256.h"  // the row swizzle gp_swz (+ gp_common.h)
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -52,8 +52,6 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     if (bad) gp_raise(status, GP_ST_SPLIT_RANGE_CONV);
 }
 
-enum { SEPI_NONE = 0, SEPI_BIAS_I = 1, SEPI_BIAS_I_GELU = 2, SEPI_BIAS_I_SCALE_RES = 3, SEPI_BIAS_J = 4, SEPI_BIAS_I_RELU = 5 };
-
 constexpr int SBM = 128, SBN = 128, SBK = 32, SNT = 256;
 constexpr int SROW = 32;                       // halfs per LDS row (64 B, no padding): the 16-byte chunk kc of row r sits at chunk
                                                // position kc ^ ((r >> 2) & 3), so a ds_read_b128 lane group covers all 64 banks once
@@ -61,7 +59,7 @@ constexpr int SPLANE = 128 * SROW;             // halfs per (operand, hi|lo) pla
 // 2 buffers x 4 planes x 8 KiB = 64 KiB per workgroup: TWO workgroups per CU.  (With 80-byte padded rows the kernel needed
 // 80 KiB; 2 x 80 KiB = the whole 160 KiB LDS did not co-reside, occupancy was one 4-wave workgroup per CU -- found with the
 // per-phase cycle probe: block time x tile count only matched the kernel time for ONE resident workgroup.)
-__device__ __forceinline__ int lds_off(int row, int kc) { return row * SROW + ((kc ^ ((row >> 2) & 3)) << 3); }
+static_assert(SROW == kRowHalfs, "gp_swz (gp_tile256.h) places the chunks of these rows");
 constexpr int SBUF = 4 * SPLANE;               // A hi, A lo, B hi, B lo
 constexpr int SLDS_BYTES = 2 * SBUF * 2;       // double buffered: 81920 B
 
@@ -130,7 +128,7 @@ __global__ __launch_bounds__(SNT, 2) void gemm_split_kernel(const SplitArgs a)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int c = tid + 256 * u;
-            *reinterpret_cast<f16x8*>(L + ((c >> 9) ? w_lo : w_hi) + lds_off((c & 511) >> 2, c & 3)) = rw[u];
+            *reinterpret_cast<f16x8*>(L + ((c >> 9) ? w_lo : w_hi) + gp_swz((c & 511) >> 2, c & 3)) = rw[u];
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {  // column n = ng*2 + c: 8 consecutive k
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(SNT, 2) void gemm_split_kernel(const SplitArgs a)
                 h[r] = hh_;
                 l[r] = ll_;
             }
-            const int off = lds_off(ng * 2 + c, kg);
+            const int off = gp_swz(ng * 2 + c, kg);
             *reinterpret_cast<f16x8*>(L + act_hi + off) = h;
             *reinterpret_cast<f16x8*>(L + act_lo + off) = l;
         }
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(SNT, 2) void gemm_split_kernel(const SplitArgs a)
     // The 32 bias rows of a lane, loaded ONCE (round 6): inside the element loop each was a 4-byte load + s_waitcnt vmcnt(0) between two stores
     // (D may alias bias as far as hipcc knows) -- 64 dependent round trips per tile, each also waiting for the previous element's store; the
     // tile epilogue cost more than the k loop of the IST heads' K = 256 / 512 GEMMs.
-    constexpr bool kBiasI = EPI == SEPI_BIAS_I || EPI == SEPI_BIAS_I_GELU || EPI == SEPI_BIAS_I_SCALE_RES || EPI == SEPI_BIAS_I_RELU;
+    constexpr bool kBiasI = EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU;
     f32x4 bias_q[2][4];
     if (kBiasI) {
 #pragma unroll
@@ -302,10 +300,10 @@ __global__ __launch_bounds__(SNT, 2) void gemm_split_kernel(const SplitArgs a)
                 const int i = i0 + wm * 64 + mi * 32 + frag_row(r, lane);
                 float v = hh[mi][ni][r] + xx[mi][ni][r] * kLoInv;
                 if (kBiasI) v = v + bias_q[mi][r >> 2][r & 3];
-                if (EPI == SEPI_BIAS_J) v = v + a.bias[j];
-                if (EPI == SEPI_BIAS_I_GELU) v = gelu_erf_s(v);
-                if (EPI == SEPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
-                if (EPI == SEPI_BIAS_I_SCALE_RES) v = a.res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + a.scale[i] * v;
+                if (EPI == GP_EPI_BIAS_J) v = v + a.bias[j];
+                if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_erf_s(v);
+                if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+                if (EPI == GP_EPI_BIAS_I_SCALE_RES) v = a.res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + a.scale[i] * v;
                 a.D[(unsigned)i * (unsigned)a.ldd + (unsigned)j] = v;
             }
         }
@@ -391,7 +389,7 @@ __global__ __launch_bounds__(512, 4) void conv_split_kernel(const ConvSplitArgs 
     };
     auto stage = [&](int buf) {
         _Float16* L = lds + buf * SBUF;
-        const int off = lds_off(r0, kc);
+        const int off = gp_swz(r0, kc);
         *reinterpret_cast<f16x8*>(L + P_AHI + off) = rw[0];
         *reinterpret_cast<f16x8*>(L + P_ALO + off) = rw[1];
         *reinterpret_cast<f16x8*>(L + P_BHI + off) = rx[0];
@@ -518,12 +516,12 @@ int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, 
     // that the TFLOP/s of the gemm_split family -- the roofline's kernel -- is not overstated by work that was skipped.
     GpProfScope prof(j_limit ? GP_PROF_OTHER : GP_PROF_GEMM_SPLIT, j_limit ? 0.0 : 2.0 * I * J * K, st);
     switch (epilogue) {
-        case SEPI_NONE: launch_split<SEPI_NONE>(a, act_is_b != 0, st); break;
-        case SEPI_BIAS_I: launch_split<SEPI_BIAS_I>(a, act_is_b != 0, st); break;
-        case SEPI_BIAS_I_GELU: launch_split<SEPI_BIAS_I_GELU>(a, act_is_b != 0, st); break;
-        case SEPI_BIAS_I_SCALE_RES: launch_split<SEPI_BIAS_I_SCALE_RES>(a, act_is_b != 0, st); break;
-        case SEPI_BIAS_J: launch_split<SEPI_BIAS_J>(a, act_is_b != 0, st); break;
-        case SEPI_BIAS_I_RELU: launch_split<SEPI_BIAS_I_RELU>(a, act_is_b != 0, st); break;
+        case GP_EPI_NONE: launch_split<GP_EPI_NONE>(a, act_is_b != 0, st); break;
+        case GP_EPI_BIAS_I: launch_split<GP_EPI_BIAS_I>(a, act_is_b != 0, st); break;
+        case GP_EPI_BIAS_I_GELU: launch_split<GP_EPI_BIAS_I_GELU>(a, act_is_b != 0, st); break;
+        case GP_EPI_BIAS_I_SCALE_RES: launch_split<GP_EPI_BIAS_I_SCALE_RES>(a, act_is_b != 0, st); break;
+        case GP_EPI_BIAS_J: launch_split<GP_EPI_BIAS_J>(a, act_is_b != 0, st); break;
+        case GP_EPI_BIAS_I_RELU: launch_split<GP_EPI_BIAS_I_RELU>(a, act_is_b != 0, st); break;
         default: GP_REQUIRE(false, "gp_gemm_split: unknown epilogue %d", epilogue);
     }
     GP_CHECK_LAUNCH("gp_gemm_split");
@@ -588,15 +586,15 @@ int gp_gemm_split_timing(const float* act, int ld_act, const void* whi, const vo
 {
     GP_REQUIRE(I % SBM == 0 && J % SBN == 0 && K % SBK == 0 && out20, "gp_gemm_split_timing: bad arguments");
     SplitArgs a{act, ld_act, (const _Float16*)whi, (const _Float16*)wlo, D, ldd, K, nullptr, nullptr, nullptr, 0, I / SBM, J / SBN, 8};
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_kernel<SEPI_NONE, true, true>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_kernel<GP_EPI_NONE, true, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, SLDS_BYTES);
-    hipLaunchKernelGGL((gemm_split_kernel<SEPI_NONE, true, true>), dim3(xcd_chunked_grid(a.tiles_i * a.tiles_j)), dim3(SNT),
+    hipLaunchKernelGGL((gemm_split_kernel<GP_EPI_NONE, true, true>), dim3(xcd_chunked_grid(a.tiles_i * a.tiles_j)), dim3(SNT),
                        SLDS_BYTES, (hipStream_t)stream, a);
     GP_CHECK_LAUNCH("gp_gemm_split_timing");
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     if (hipMemcpyFromSymbol(out20, HIP_SYMBOL(g_split_clk), 20 * sizeof(unsigned long long)) != hipSuccess) return GP_ELAUNCH;
     int occ = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gemm_split_kernel<SEPI_NONE, true, true>, SNT, SLDS_BYTES);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gemm_split_kernel<GP_EPI_NONE, true, true>, SNT, SLDS_BYTES);
     unsigned long long w[4] = {0, 0, 0, 0};
     if (hipMemcpyFromSymbol(w, HIP_SYMBOL(g_split_wall), sizeof(w)) != hipSuccess) return GP_ELAUNCH;
     out20[20] = w[0]; out20[21] = w[1]; out20[22] = (unsigned long long)occ;

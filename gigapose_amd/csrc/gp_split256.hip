@@ -18,7 +18,7 @@
 //     behind each of the first 12 MFMAs -> barrier.
 // Activations arrive as f32 k-major [K][n] (converted while staging, balanced over all 512 threads); weights as f16
 // planes [n][K] made by gp_split256_weights().
-#include "gp_common.h"
+#include "gp_tile256.h"
 
 typedef _Float16 g16x8 __attribute__((ext_vector_type(8)));
 typedef float g32x2 __attribute__((ext_vector_type(2)));
@@ -28,16 +28,10 @@ typedef _Float16 g16x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr float kActScale = 8.0f, kWScale = 64.0f, kOutScale = 1.0f / (8.0f * 64.0f);
-constexpr int TB = 256, TBK = 32, TNT = 512;
-constexpr int TROW = 32, TPLANE = TB * TROW;  // halfs
+constexpr int TB = 256, TBK = 32, TNT = kTileThreads;
+constexpr int TROW = kRowHalfs, TPLANE = TB * TROW;  // halfs
 constexpr int TBUF = 4 * TPLANE;              // A hi, A lo, B hi, B lo
-constexpr int kSlots = 256;
-constexpr int kErrWord = 1025;  // scratch header word: beyond gp_gemm.hip's 1024 slot flags + its own error word (shared scratch)
-constexpr size_t kHeaderBytes = 8192;
-constexpr size_t kFragFloats = (size_t)TB * TB;
-constexpr int kSpin = 400000;
-
-enum { XEPI_NONE = 0, XEPI_BIAS_I = 1, XEPI_BIAS_I_GELU = 2, XEPI_BIAS_I_SCALE_RES = 3, XEPI_BIAS_J = 4, XEPI_BIAS_I_RELU = 5 };
+static_assert(kFragFloats == (size_t)TB * TB, "a slot's scratch fragment holds a tile's accumulators");
 
 struct Args256 {
     const float* act; int ld_act;
@@ -49,7 +43,6 @@ struct Args256 {
     int* status;
 };
 
-__device__ __forceinline__ int toff(int row, int kc) { return row * TROW + ((kc ^ ((row >> 2) & 3)) << 3); }
 // GELU: gp_common.h (gp_gelu_scaled), shared with gp_split.hip
 __device__ __forceinline__ float gelu_x(float x) { return gp_gelu_scaled(x, 0.5f); }
 
@@ -77,18 +70,9 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
     const int act_hi = ACT_IS_B ? P_BHI : P_AHI, act_lo = ACT_IS_B ? P_BLO : P_ALO;
     const int w_hi = ACT_IS_B ? P_AHI : P_BHI, w_lo = ACT_IS_B ? P_ALO : P_BLO;
 
-    // ---- this slot's range of (tile, k-step) units inside its XCD's tile chunk
-    const int p = blockIdx.x, x = p & 7, n = p >> 3, slots_x = gridDim.x >> 3;
-    const int T = a.tiles_i * a.tiles_j;
-    const int t_lo = (int)((long long)T * x / 8), n_t = (int)((long long)T * (x + 1) / 8) - t_lo;
-    const int nstep = a.K / TBK;
-    const long long U = (long long)n_t * nstep;
-    const long long u0 = U * n / slots_x, u1 = U * (n + 1) / slots_x;
-    const int ta = (int)(u0 / nstep), sa = (int)(u0 % nstep);
-    const int tb = (int)(u1 / nstep), sb = (int)(u1 % nstep);
-    const int n_head = sb > 0 ? 1 : 0, n_rest = sa > 0 ? 1 : 0;
-    const int first_whole = ta + n_rest;
-    const int n_seg = n_head + (tb - first_whole) + n_rest;
+    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan; no data-parallel rounds here)
+    const GpSlotPlan plan(a.tiles_i * a.tiles_j, a.K / TBK, false, 0);
+    const int p = plan.p;
 
     // staging roles (all 512 threads): 2 n x 8 k activation micro-block + four 16-byte weight chunks
     const int ng = tid & 127, kg = tid >> 7;
@@ -101,13 +85,12 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
     const int ak0 = ((kh_ ^ ((ar_ >> 2) & 3)) << 3), ak1 = (((kh_ + 2) ^ ((ar_ >> 2) & 3)) << 3);
     const int bk0 = ((kh_ ^ ((br_ >> 2) & 3)) << 3), bk1 = (((kh_ + 2) ^ ((br_ >> 2) & 3)) << 3);
 
-    for (int seg = 0; seg < n_seg; ++seg) {
-        const bool is_head = seg < n_head;
-        const bool is_rest = n_rest && seg == n_seg - 1;
-        const int t = is_head ? tb : (is_rest ? ta : first_whole + seg - n_head);
-        const int s0 = is_rest ? sa : 0, s1 = is_head ? sb : nstep;
+    for (int seg = 0; seg < plan.n_seg; ++seg) {
+        const GpSlotPlan::Segment sg = plan.segment(seg);
+        const bool is_head = sg.is_head, is_rest = sg.is_rest;
+        const int s0 = sg.u0, s1 = sg.u1;
         // tile order inside the chunk: bands of `group` i-tiles, i fastest
-        const int q = t_lo + t;
+        const int q = sg.tile;
         const int per_band = a.group * a.tiles_j;
         const int band = q / per_band, rr = q - band * per_band;
         const int first_i = band * a.group;
@@ -117,30 +100,8 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 
         f32x16 acc[2][4];
         if (is_rest) {
-            if (tid == 0) {
-                int spins = 0;
-                while (__hip_atomic_load(a.flags + (p - 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                    __builtin_amdgcn_s_sleep(16);
-                    if (++spins > kSpin) {
-                        __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            __syncthreads();
-            const f32x4* w = reinterpret_cast<const f32x4*>(a.partial + (size_t)(p - 8) * kFragFloats) + tid * 32;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const f32x4 v = w[(mi * 4 + ni) * 4 + r4];
-                        acc[mi][ni][r4 * 4 + 0] = v[0]; acc[mi][ni][r4 * 4 + 1] = v[1];
-                        acc[mi][ni][r4 * 4 + 2] = v[2]; acc[mi][ni][r4 * 4 + 3] = v[3];
-                    }
+            gp_handoff_wait(a.flags, p - 8, p - 8, 8, a.epoch, a.status);
+            gp_frag_load<4>(acc, a.partial, p - 8);
         } else {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -176,7 +137,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int c = tid + TNT * u;
-                *reinterpret_cast<g16x8*>(L + ((c >> 10) ? w_lo : w_hi) + toff((c & 1023) >> 2, c & 3)) = rw[u];
+                *reinterpret_cast<g16x8*>(L + ((c >> 10) ? w_lo : w_hi) + gp_swz((c & 1023) >> 2, c & 3)) = rw[u];
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -189,7 +150,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
                     l[r] = (_Float16)(v - (float)hh);
                     bad |= !(fabsf(v) <= kSplitPlaneLimit);  // !(<=): NaN counts
                 }
-                const int off = toff(ng * 2 + c, kg);
+                const int off = gp_swz(ng * 2 + c, kg);
                 *reinterpret_cast<g16x8*>(L + act_hi + off) = h;
                 *reinterpret_cast<g16x8*>(L + act_lo + off) = l;
             }
@@ -255,25 +216,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
 #undef X_LD
 
         if (is_head) {  // publish the fragment for slot n+1 (agent-scope release by one lane; guide, Guideline 16)
-            f32x4* w = reinterpret_cast<f32x4*>(a.partial + (size_t)p * kFragFloats) + tid * 32;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        f32x4 v;
-                        v[0] = acc[mi][ni][r4 * 4 + 0]; v[1] = acc[mi][ni][r4 * 4 + 1];
-                        v[2] = acc[mi][ni][r4 * 4 + 2]; v[3] = acc[mi][ni][r4 * 4 + 3];
-                        w[(mi * 4 + ni) * 4 + r4] = v;
-                    }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(a.flags + p, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            gp_frag_publish<4>(acc, a.partial, p, a.flags, a.epoch, true);
         } else {
             int tid_ = threadIdx.x;
             asm volatile("" : "+v"(tid_));  // keep the epilogue's address arithmetic inside the segment loop
@@ -287,12 +230,12 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
                     for (int r = 0; r < 16; ++r) {
                         const int i = i0 + 64 * wr + 32 * mi + frag_row(r, ln);
                         float v = acc[mi][ni][r] * kOutScale;
-                        if (EPI == XEPI_BIAS_I || EPI == XEPI_BIAS_I_GELU || EPI == XEPI_BIAS_I_SCALE_RES || EPI == XEPI_BIAS_I_RELU)
+                        if (EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU)
                             v = v + a.bias[i];
-                        if (EPI == XEPI_BIAS_J) v = v + a.bias[j];
-                        if (EPI == XEPI_BIAS_I_GELU) v = gelu_x(v);
-                        if (EPI == XEPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
-                        if (EPI == XEPI_BIAS_I_SCALE_RES) v = a.res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + a.scale[i] * v;
+                        if (EPI == GP_EPI_BIAS_J) v = v + a.bias[j];
+                        if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_x(v);
+                        if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+                        if (EPI == GP_EPI_BIAS_I_SCALE_RES) v = a.res[(unsigned)i * (unsigned)a.ldr + (unsigned)j] + a.scale[i] * v;
                         a.D[(unsigned)i * (unsigned)a.ldd + (unsigned)j] = v;
                     }
                 }
@@ -313,17 +256,17 @@ unsigned g_epoch256 = 0;
 // wave of each per SIMD) run half a step apart: while one group issues the 48 MFMAs of slab s (matrix phase C(s)) the
 // other writes its share of slab s+1 to LDS and issues its loads of slab s+2 (memory phase M(s+1)), see the loop below.
 // The lock-step kernel above idles the matrix pipe during every staging phase (60 % busy in-loop,
-// profiles/r01_probe_split256.txt).  Tile, LDS layout, single accumulator, stream-K hand-off and epilogues are those
-// of gemm_split256_kernel; the arithmetic (operand values, k order) is identical, so results are bit-identical to it.
+// profiles/r01_probe_split256.txt).  Tile, LDS layout, single accumulator, slot plan, hand-over and matrix step are those of
+// gemm_split256_kernel (both from gp_tile256.h); the arithmetic (operand values, k order) is identical, so results are bit-identical to it.
 // Work distribution: data-parallel rounds of whole tiles first (L2 reuse), stream-K only for the last round + remainder.
-enum { PEPI_GELU_PLANES = 6, PEPI_BIAS_I_PLANES = 7 };  // bias along i (6: + GELU), output as activation planes O[j][i] (x 8)
-template <int EPI> constexpr bool kEpiPlanesOut = EPI == PEPI_GELU_PLANES || EPI == PEPI_BIAS_I_PLANES;
+// plane epilogues 6 / 7 (GP_EPI_GELU_PLANES, GP_EPI_BIAS_I_PLANES): bias along i (6: + GELU), output as activation planes O[j][i] (x 8)
+template <int EPI> constexpr bool kEpiPlanesOut = EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES;
 
 struct ArgsP {
     const _Float16* ahi; const _Float16* alo;  // A planes [I][K]
     const _Float16* bhi; const _Float16* blo;  // B planes [J][K]
     float* D; int ldd;                         // f32 output D[i][j]
-    _Float16* ohi; _Float16* olo; int ldo;     // PEPI_*_PLANES: O[j][i]
+    _Float16* ohi; _Float16* olo; int ldo;     // GP_EPI_*_PLANES: O[j][i]
     int K;
     const float* bias; const float* scale; const float* res; int ldr;
     int tiles_i, tiles_j, group;
@@ -355,7 +298,7 @@ template <int EPI, int NJ = 4, bool PIPE = true>
 __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2][NJ], float* __restrict__ wl, int i_base, int j_base, int ln)
 {
     const int l31 = ln & 31, half = ln >> 5;
-    constexpr bool kBiasI = EPI == XEPI_BIAS_I || EPI == XEPI_BIAS_I_GELU || EPI == XEPI_BIAS_I_SCALE_RES || EPI == XEPI_BIAS_I_RELU;
+    constexpr bool kBiasI = EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU;
     if constexpr (NJ == 2) {
         // 256 x 128 tiles (launches far below one tile per slot): the wave tile is 64 x 64, a round is wl[32][64], 16 lanes cover a row
         // and a wave four rows per item, eight items per round.  The per-row constants are 4-byte loads of the row a lane finishes
@@ -363,7 +306,7 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
         const int l15 = ln & 15, q4 = ln >> 4;
         const unsigned j = (unsigned)(j_base + 4 * l15);
         f32x4 bias_j = {0.f, 0.f, 0.f, 0.f};
-        if (EPI == XEPI_BIAS_J) bias_j = *reinterpret_cast<const f32x4*>(a.bias + j);
+        if (EPI == GP_EPI_BIAS_J) bias_j = *reinterpret_cast<const f32x4*>(a.bias + j);
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -376,10 +319,10 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
             for (int u = 0; u < 8; ++u) {  // every load of the round first: D may be the residual buffer itself (see below)
                 const unsigned i = (unsigned)(i_base + 32 * mi + 4 * u + q4);
                 bs[u] = kBiasI ? a.bias[i] : 0.f;
-                ss[u] = EPI == XEPI_BIAS_I_SCALE_RES ? a.scale[i] : 0.f;
-                if (EPI == XEPI_BIAS_I_SCALE_RES) rs[u] = *reinterpret_cast<const f32x4*>(a.res + i * (unsigned)a.ldr + j);
+                ss[u] = EPI == GP_EPI_BIAS_I_SCALE_RES ? a.scale[i] : 0.f;
+                if (EPI == GP_EPI_BIAS_I_SCALE_RES) rs[u] = *reinterpret_cast<const f32x4*>(a.res + i * (unsigned)a.ldr + j);
             }
-            if (EPI == XEPI_BIAS_I_SCALE_RES)
+            if (EPI == GP_EPI_BIAS_I_SCALE_RES)
                 asm volatile("" : "+v"(rs[0]), "+v"(rs[1]), "+v"(rs[2]), "+v"(rs[3]), "+v"(rs[4]), "+v"(rs[5]), "+v"(rs[6]), "+v"(rs[7]));
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -391,10 +334,10 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
                 for (int e = 0; e < 4; ++e) {
                     float v = t[e] * a.out_scale;
                     if (kBiasI) v = v + bs[u];
-                    if (EPI == XEPI_BIAS_J) v = v + bias_j[e];
-                    if (EPI == XEPI_BIAS_I_GELU) v = gelu_x(v);
-                    if (EPI == XEPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
-                    if (EPI == XEPI_BIAS_I_SCALE_RES) v = rs[u][e] + ss[u] * v;
+                    if (EPI == GP_EPI_BIAS_J) v = v + bias_j[e];
+                    if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_x(v);
+                    if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+                    if (EPI == GP_EPI_BIAS_I_SCALE_RES) v = rs[u][e] + ss[u] * v;
                     o[e] = v;
                 }
                 *reinterpret_cast<f32x4*>(a.D + i * (unsigned)a.ldd + j) = o;
@@ -403,12 +346,12 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
     } else {
         float bias_l = 0.f, scale_l = 0.f;  // lane l holds the value of row i_base + l
         if (kBiasI) bias_l = a.bias[i_base + ln];
-        if (EPI == XEPI_BIAS_I_SCALE_RES) scale_l = a.scale[i_base + ln];
+        if (EPI == GP_EPI_BIAS_I_SCALE_RES) scale_l = a.scale[i_base + ln];
         f32x4 bias_j = {0.f, 0.f, 0.f, 0.f};
-        if (EPI == XEPI_BIAS_J) bias_j = *reinterpret_cast<const f32x4*>(a.bias + j_base + 4 * l31);
+        if (EPI == GP_EPI_BIAS_J) bias_j = *reinterpret_cast<const f32x4*>(a.bias + j_base + 4 * l31);
         // Rows as buffer accesses: one lane offset (column piece + the lane half's row) and a scalar row offset per item -- 64-bit flat
         // addresses cost an address pair per item in flight.
-        constexpr bool kRes = EPI == XEPI_BIAS_I_SCALE_RES;
+        constexpr bool kRes = EPI == GP_EPI_BIAS_I_SCALE_RES;
         const __amdgpu_buffer_rsrc_t r_d = __builtin_amdgcn_make_buffer_rsrc((void*)a.D, 0, 0x7ffffff0, 0x00020000);
         const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(kRes ? a.res : a.D), 0, 0x7ffffff0, 0x00020000);
         const unsigned v_d = ((unsigned)half * (unsigned)a.ldd + (unsigned)(j_base + 4 * l31)) * 4u;
@@ -466,9 +409,9 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
                 for (int e = 0; e < 4; ++e) {
                     float v = t[e] * a.out_scale;
                     if (kBiasI) v = v + bb;
-                    if (EPI == XEPI_BIAS_J) v = v + bias_j[e];
-                    if (EPI == XEPI_BIAS_I_GELU) v = gelu_x(v);
-                    if (EPI == XEPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+                    if (EPI == GP_EPI_BIAS_J) v = v + bias_j[e];
+                    if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_x(v);
+                    if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
                     if (kRes) v = rs[b & 1][u][e] + sc * v;
                     o[e] = v;
                 }
@@ -478,36 +421,8 @@ __device__ __forceinline__ void epilogue_f32_lds(const ArgsP& a, f32x16 (&acc)[2
     }
 }
 
-// ---- Thin plane arithmetic (round 4).  The round-3 segment probes put the arithmetic half of a plane epilogue at 8.5 vector
-// instructions per element (readlane + select for the bias, multiply, add, x 8, two conversions, a subtraction, a third
-// conversion, a compare) and showed that it adds to the matrix work instead of hiding behind it.  Here: the per-row constants come
-// from 16-byte loads of exactly the rows a lane holds (no readlane / select), every affine step is ONE fma, a pair of values
-// becomes its two f16 planes in three instructions (v_cvt_pk_f16_f32; v_fma_mixlo / mixhi_f16 computing v - hi with the f16
-// operand read straight from the packed hi pair), and the range guard is a NaN-propagating v_maximum3_f32 over |v| per pair.
-typedef _Float16 g16x2 __attribute__((ext_vector_type(2)));
+// thin plane arithmetic (gp_hi_pair, gp_lo_pair, gp_absmax3): gp_tile256.h
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_hi_pair(float v0, float v1)
-{
-    g16x2 h;
-    h[0] = (_Float16)v0;
-    h[1] = (_Float16)v1;
-    return __builtin_bit_cast(unsigned, h);
-}
-// (f16(v0 - hi.lo), f16(v1 - hi.hi)) in one register.  v - hi is exact in f32 (hi = v rounded to 11 bits), so the single rounding
-// of the mixed-precision fma equals the f32 subtraction + conversion the other plane producers use.
-__device__ __forceinline__ unsigned lo_pair(float v0, float v1, unsigned hi)
-{
-    unsigned lo;
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(lo)
-        : "v"(v0), "v"(v1), "v"(hi));
-    return lo;
-}
-__device__ __forceinline__ float absmax3(float m, float v0, float v1)  // v_maximum3_f32: a NaN operand makes the result NaN
-{
-    return __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(__builtin_fabsf(v0), __builtin_fabsf(v1)));
-}
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v)
 {
@@ -539,7 +454,7 @@ __device__ __forceinline__ void epilogue_planes_thin(const ArgsP& a, f32x16 (&ac
                                                      const float* __restrict__ bias_w)
 {
     const int l31 = ln & 31, half = ln >> 5;
-    constexpr bool kGelu = EPI == PEPI_GELU_PLANES;
+    constexpr bool kGelu = EPI == GP_EPI_GELU_PLANES;
     const float k8 = kGelu ? 1.0f : a.plane_scale, hs = 0.5f * a.plane_scale;  // the output tensor's power-of-two scale (8 by default)
     const __amdgpu_buffer_rsrc_t r_hi = __builtin_amdgcn_make_buffer_rsrc((void*)a.ohi, 0, 0x7ffffff0, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_lo = __builtin_amdgcn_make_buffer_rsrc((void*)a.olo, 0, 0x7ffffff0, 0x00020000);
@@ -570,11 +485,11 @@ __device__ __forceinline__ void epilogue_planes_thin(const ArgsP& a, f32x16 (&ac
                         v[e + 1] = x[1];
                     }
                     u32x2 oh, ol;
-                    oh[0] = pack_hi_pair(v[0], v[1]);
-                    oh[1] = pack_hi_pair(v[2], v[3]);
-                    ol[0] = lo_pair(v[0], v[1], oh[0]);
-                    ol[1] = lo_pair(v[2], v[3], oh[1]);
-                    mx = absmax3(absmax3(mx, v[0], v[1]), v[2], v[3]);
+                    oh[0] = gp_hi_pair(v[0], v[1]);
+                    oh[1] = gp_hi_pair(v[2], v[3]);
+                    ol[0] = gp_lo_pair(v[0], v[1], oh[0]);
+                    ol[1] = gp_lo_pair(v[2], v[3], oh[1]);
+                    mx = gp_absmax3(gp_absmax3(mx, v[0], v[1]), v[2], v[3]);
                     *reinterpret_cast<u32x2*>(wrow + ((c8 ^ sw) << 3)) = oh;
                     *reinterpret_cast<u32x2*>(wrow + 8192 + ((c8 ^ sw) << 3)) = ol;
                 }
@@ -608,6 +523,7 @@ __device__ __forceinline__ void epilogue_planes_thin(const ArgsP& a, f32x16 (&ac
 // ViT-L launch sat on the first 64 slots whatever their speed: a fc2 launch ended with 22 us of strip work on a quarter of
 // the chip.  One counter word per scratch, tagged with the launch's epoch (no reset between launches): count in the low 12 bits.
 constexpr int kStripCtr = 1030;  // header word (after the slot flags and the two error words)
+static_assert(kStripCtr > kErrWord && (size_t)(kStripCtr + 1) * sizeof(int) <= kHeaderBytes, "the strip counter lies behind the error words, inside the header");
 __device__ __forceinline__ int strip_grab(int* ctr, int tag)
 {
     // Once the word carries this launch's tag: one fetch-add per request.  The first arrivals of a launch still see the previous
@@ -660,15 +576,15 @@ __device__ __forceinline__ void strip_phase(const ArgsP& a, float* __restrict__ 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         // epilogue operands of this fragment (used by wave 0 only, requested now: their latency hides behind the K loop)
-        constexpr bool kBiasI = EPI == XEPI_BIAS_I || EPI == XEPI_BIAS_I_GELU || EPI == XEPI_BIAS_I_SCALE_RES || EPI == XEPI_BIAS_I_RELU ||
-                                EPI == PEPI_GELU_PLANES || EPI == PEPI_BIAS_I_PLANES;
+        constexpr bool kBiasI = EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU ||
+                                EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES;
         f32x4 pre_bias[4], pre_scale[4], pre_res[4];
         if (wave == 0) {
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int i = i0 + frag_row(4 * r4, lane);
                 if (kBiasI) pre_bias[r4] = *reinterpret_cast<const f32x4*>(a.bias + i);
-                if (EPI == XEPI_BIAS_I_SCALE_RES) {
+                if (EPI == GP_EPI_BIAS_I_SCALE_RES) {
                     pre_scale[r4] = *reinterpret_cast<const f32x4*>(a.scale + i);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pre_res[r4][e] = a.res[(unsigned)(i + e) * (unsigned)a.ldr + (unsigned)(j0 + l31)];
@@ -775,11 +691,11 @@ __device__ __forceinline__ void strip_phase(const ArgsP& a, float* __restrict__ 
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int i = i0 + frag_row(4 * r4, lane);
-                if (EPI == PEPI_GELU_PLANES || EPI == PEPI_BIAS_I_PLANES) {                    g16x4 oh, ol;
+                if (EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES) {                    g16x4 oh, ol;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x = acc[4 * r4 + e] * a.out_scale + pre_bias[r4][e];
-                        const float v = (EPI == PEPI_GELU_PLANES ? gelu_x(x) : x) * a.plane_scale;
+                        const float v = (EPI == GP_EPI_GELU_PLANES ? gelu_x(x) : x) * a.plane_scale;
                         const _Float16 hh = (_Float16)v;
                         oh[e] = hh;
                         ol[e] = (_Float16)(v - (float)hh);
@@ -793,18 +709,18 @@ __device__ __forceinline__ void strip_phase(const ArgsP& a, float* __restrict__ 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float v = acc[4 * r4 + e] * a.out_scale;
-                        if (EPI == XEPI_BIAS_I || EPI == XEPI_BIAS_I_GELU || EPI == XEPI_BIAS_I_SCALE_RES || EPI == XEPI_BIAS_I_RELU)
+                        if (EPI == GP_EPI_BIAS_I || EPI == GP_EPI_BIAS_I_GELU || EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_BIAS_I_RELU)
                             v = v + pre_bias[r4][e];
-                        if (EPI == XEPI_BIAS_J) v = v + a.bias[j];
-                        if (EPI == XEPI_BIAS_I_GELU) v = gelu_x(v);
-                        if (EPI == XEPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
-                        if (EPI == XEPI_BIAS_I_SCALE_RES) v = pre_res[r4][e] + pre_scale[r4][e] * v;
+                        if (EPI == GP_EPI_BIAS_J) v = v + a.bias[j];
+                        if (EPI == GP_EPI_BIAS_I_GELU) v = gelu_x(v);
+                        if (EPI == GP_EPI_BIAS_I_RELU) v = fmaxf(v, 0.f);
+                        if (EPI == GP_EPI_BIAS_I_SCALE_RES) v = pre_res[r4][e] + pre_scale[r4][e] * v;
                         a.D[(unsigned)(i + e) * (unsigned)a.ldd + (unsigned)j] = v;
                     }
                 }
             }
             if (bad) gp_raise(a.status, GP_ST_SPLIT_RANGE);
-            if ((EPI == PEPI_GELU_PLANES || EPI == PEPI_BIAS_I_PLANES) && a.amax) gp_record_amax(a.amax, strip_mx, 1.0f / a.plane_scale);
+            if ((EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES) && a.amax) gp_record_amax(a.amax, strip_mx, 1.0f / a.plane_scale);
         }
         __syncthreads();  // `red` and *next_f are rewritten for the next fragment
     }
@@ -832,38 +748,15 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
     constexpr int P_AHI = 0, P_ALO = TPLANE, P_BHI = 2 * TPLANE, P_BLO = 3 * TPLANE;
 
-    // ---- this slot's range of (tile, k-step) units inside its XCD's tile chunk (as gemm_split256_kernel)
-    const int p = blockIdx.x, x = p & 7, n = p >> 3, slots_x = gridDim.x >> 3;
-    const int T = a.tiles_i * a.tiles_j;
-    const int t_lo = (int)((long long)T * x / 8), n_t = (int)((long long)T * (x + 1) / 8) - t_lo;
-    const int nstep = a.K / TBK;
-    // Data-parallel rounds first: while the chunk holds two or more tiles per slot, round r gives slot n the whole tile
-    // r * slots_x + n -- the 32 slots of an XCD then sit on the same k-step of 32 neighbouring tiles (4 i-panels x 8
-    // j-panels) and share their operand slabs in that XCD's L2.  Only the last round + remainder is cut stream-K style
-    // (its slots run at staggered k offsets and get no L2 reuse: 1.9 GB fetched per fc1 launch when everything was).
-    const int rounds_dp = (!PAR && (a.dp & 1) && n_t / slots_x > 1) ? n_t / slots_x - 1 : 0;
-    const int n_dp = rounds_dp * slots_x;
-    const long long U = (long long)(n_t - n_dp) * nstep;
-    long long u0 = U * n / slots_x, u1 = U * (n + 1) / slots_x;
-    // PAR (fewer tiles than slots): S = floor(slots / tiles) slots per tile, each an equal share of the tile's k-steps; slot n holds
-    // part n % S of tile n / S, slots beyond S * tiles have no tile (they take strip fragments).  S = 1: whole tiles, no exchange.
+    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h).  PAR: S = floor(slots /
+    // tiles) slots per tile, at most a.par (the host's cap: k-steps per slot, see the launch).
     // (the GELU build keeps whole tiles, S = 1: with the partial-sum loop next to its epilogue hipcc spills 273 registers, and a
     // launch of T < 256 whole tiles on T slots is within 10 % of the split one at the sizes where it occurs -- fc1 below 16 crops)
-    constexpr bool kParSplit = PAR && PSPLIT && EPI != PEPI_GELU_PLANES;
-    const int par_S = kParSplit ? max(1, min(a.par, slots_x / max(n_t, 1))) : 1;  // a.par: the host's cap (k-steps per slot, see the launch)
-    if (PAR) {
-        const int tile = n / par_S, part = n - tile * par_S;
-        u0 = u1 = 0;
-        if (tile < n_t) {
-            u0 = (long long)tile * nstep + nstep * part / par_S;
-            u1 = (long long)tile * nstep + nstep * (part + 1) / par_S;
-        }
-    }
-    const int ta = (int)(u0 / nstep), sa = (int)(u0 % nstep);
-    const int tb = (int)(u1 / nstep), sb = (int)(u1 % nstep);
-    const int n_head = sb > 0 ? 1 : 0, n_rest = sa > 0 ? 1 : 0;
-    const int first_whole = ta + n_rest;
-    const int n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest;
+    constexpr bool kParSplit = PAR && PSPLIT && EPI != GP_EPI_GELU_PLANES;
+    const int T = a.tiles_i * a.tiles_j;
+    const int par_S = kParSplit ? max(1, min(a.par, (int)(gridDim.x >> 3) / max(GpSlotPlan::chunk_tiles(T), 1))) : 1;
+    const GpSlotPlan plan(T, a.K / TBK, !PAR && (a.dp & 1), PAR ? par_S : 0);
+    const int p = plan.p, x = plan.x, n = plan.n, n_seg = plan.n_seg;
 
     // staging: thread = (row tid >> 2 [+128], 16-byte k-chunk tid & 3) of each of the four planes
     const __amdgpu_buffer_rsrc_t r_ahi = __builtin_amdgcn_make_buffer_rsrc((void*)a.ahi, 0, a.tiles_i * TB * a.K * 2, 0x00020000);
@@ -872,7 +765,7 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
     const __amdgpu_buffer_rsrc_t r_blo = __builtin_amdgcn_make_buffer_rsrc((void*)a.blo, 0, a.tiles_j * TJ * a.K * 2, 0x00020000);
     const unsigned voff = (unsigned)(tid >> 2) * (unsigned)a.K * 2u + (unsigned)(tid & 3) * 16u;
     const unsigned half_rows = 128u * (unsigned)a.K * 2u;  // byte distance of row + 128
-    const int wofs = toff(tid >> 2, tid & 3);
+    const int wofs = gp_swz(tid >> 2, tid & 3);
     u32x4 rg[8];
     // fragment addressing
     const int ar_ = 64 * wr + (lane & 31), br_ = 32 * NJ * wc + (lane & 31), kh_ = lane >> 5;
@@ -885,49 +778,20 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
         a.trace[(size_t)p * 32 + 1] = (unsigned long long)n_seg;
     }
     for (int seg = 0; seg < n_seg; ++seg) {
-        const bool is_dp = seg < rounds_dp;
-        const bool is_head = !is_dp && seg - rounds_dp < n_head;
-        const bool is_rest = !is_dp && n_rest && seg == n_seg - 1;
-        const int t = is_dp ? seg * slots_x + n : n_dp + (is_head ? tb : (is_rest ? ta : first_whole + seg - rounds_dp - n_head));
-        const int seg_s0 = is_rest ? sa : 0, seg_s1 = is_head ? sb : nstep;
-        const int q = t_lo + t;
+        const GpSlotPlan::Segment sg = plan.segment(seg);
+        const bool is_head = sg.is_head, is_rest = sg.is_rest;
+        const int q = sg.tile;
         const int per_band = a.group * a.tiles_j;
         const int band = q / per_band, rr = q - band * per_band;
         const int first_i = band * a.group;
         const int gsz = min(a.group, a.tiles_i - first_i);
         const int i0 = (first_i + rr % gsz) * TB, j0 = (rr / gsz) * TJ;
 
-        const int s0 = seg_s0, s1 = seg_s1;
+        const int s0 = sg.u0, s1 = sg.u1;
         f32x16 acc[2][NJ];
         if (!PAR && is_rest) {
-            if (tid == 0) {
-                int spins = 0;
-                while (__hip_atomic_load(a.flags + (p - 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                    __builtin_amdgcn_s_sleep(16);
-                    if (++spins > kSpin) {
-                        __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            __syncthreads();
-            // piece u of thread tid at [u][tid] (a wave instruction covers 1 KB contiguous); buffer loads: one 32-bit lane offset + a
-            // scalar offset per piece (64-bit flat addresses 8 KB apart cost an address pair per piece: 100 spilled registers)
-            const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)(p - 8) * kFragFloats), 0,
-                                                                                 (int)(kFragFloats * sizeof(float)), 0x00020000);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NJ; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rf, (unsigned)tid * 16u, (unsigned)(((mi * NJ + ni) * 4 + r4) * TNT) * 16u, 0);
-                        const f32x4 vf = __builtin_bit_cast(f32x4, v);  // whole-vector cast (element-wise __builtin_bit_cast of vector lanes miscompiles: every r4 got lane group 0)
-                        acc[mi][ni][r4 * 4 + 0] = vf[0]; acc[mi][ni][r4 * 4 + 1] = vf[1];
-                        acc[mi][ni][r4 * 4 + 2] = vf[2]; acc[mi][ni][r4 * 4 + 3] = vf[3];
-                    }
+            gp_handoff_wait(a.flags, p - 8, p - 8, 8, a.epoch, a.status);
+            gp_frag_load<NJ>(acc, a.partial, p - 8);
         } else {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -978,42 +842,11 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
         if (ns > 1) gload(1);
         __syncthreads();
 
-#define X_MFMA(A_, B_, mi, ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_[mi], B_[ni], acc[mi][ni], 0, 0, 0)
         auto c_phase = [&](int s) __attribute__((always_inline)) {
             if (TIMING) { t0 = __builtin_readcyclecounter(); tc[5] += 1; }
             const _Float16* L = lds + (s & 1) * TBUF;
-            __builtin_amdgcn_s_setprio(1);  // before the fragment reads: they must not queue behind the other group's staging
-            g16x8 ah[2], al[2], bh[NJ], bl[NJ], ch[2], cl[2], dh[NJ], dl[NJ];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ah[mi] = *reinterpret_cast<const g16x8*>(L + P_AHI + arow + mi * 32 * TROW + ak0);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) bh[ni] = *reinterpret_cast<const g16x8*>(L + P_BHI + brow + ni * 32 * TROW + bk0);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) bl[ni] = *reinterpret_cast<const g16x8*>(L + P_BLO + brow + ni * 32 * TROW + bk0);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) al[mi] = *reinterpret_cast<const g16x8*>(L + P_ALO + arow + mi * 32 * TROW + ak0);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(ah, bh, 0, ni); X_MFMA(ah, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(ah, bl, 0, ni); X_MFMA(ah, bl, 1, ni); }
-            // second k16 block's fragments replace the dead ones (ah, bl) under the MFMAs in flight
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) ch[mi] = *reinterpret_cast<const g16x8*>(L + P_AHI + arow + mi * 32 * TROW + ak1);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) dh[ni] = *reinterpret_cast<const g16x8*>(L + P_BHI + brow + ni * 32 * TROW + bk1);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(al, bh, 0, ni); X_MFMA(al, bh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) dl[ni] = *reinterpret_cast<const g16x8*>(L + P_BLO + brow + ni * 32 * TROW + bk1);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) cl[mi] = *reinterpret_cast<const g16x8*>(L + P_ALO + arow + mi * 32 * TROW + ak1);
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(ch, dh, 0, ni); X_MFMA(ch, dh, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(ch, dl, 0, ni); X_MFMA(ch, dl, 1, ni); }
-#pragma unroll
-            for (int ni = 0; ni < NJ; ++ni) { X_MFMA(cl, dh, 0, ni); X_MFMA(cl, dh, 1, ni); }
-            __builtin_amdgcn_s_setprio(0);
+            const int a0[2] = {ak0, 32 * TROW + ak0}, a1[2] = {ak1, 32 * TROW + ak1};
+            gp_mfma3_step<NJ>(acc, L + P_AHI, L + P_ALO, arow, a0, a1, L + P_BHI, L + P_BLO, brow, bk0, bk1);
             if (TIMING) { t1 = __builtin_readcyclecounter(); tc[0] += t1 - t0; t0 = t1; }
         };
         auto m_phase = [&](int slab) __attribute__((always_inline)) {  // stages `slab`, loads slab + 1
@@ -1023,98 +856,28 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
             gload(min(slab + 1, ns - 1));  // unconditional (the last ones re-load an L2-hot slab, unused)
             if (TIMING) { t1 = __builtin_readcyclecounter(); tc[2] += t1 - t0; t0 = t1; }
         };
-        // One loop body for both groups; waves 4-7 run one memory phase ahead.  ONE barrier per k-step (ns - 1 for every
-        // wave); what it orders: C(s+1) after every wave's M(s+1), M(s+2) after every wave's C(s):
-        //     waves 0-3:  C0 M1 | C1 M2 | ...          waves 4-7:  M1 C0 | M2 C1 | ...
-        // After a barrier waves 0-3 start their MFMAs at once and waves 4-7 stage first, so the offset is kept by the code
-        // order; the matrix phases overlap in part (the pipe is shared, its work per step is the same).  Measured on the
-        // fc2 shape (profiles/r01_probe_planes256_variants.txt): strict alternation with two barriers per step 4170
-        // cycles per step, this 3670 (matrix pipe 84 % busy in-loop), without the matrix-phase priority 3850.
-        if (grp) m_phase(1);
-        for (int s = 0; s < ns; ++s) {
-            c_phase(s);
-            if (grp && s + 1 < ns) __syncthreads();
-            if (TIMING) { t1 = __builtin_readcyclecounter(); tc[1] += t1 - t0; }
-            m_phase(s + 1 + grp);
-            if (!grp && s + 1 < ns) __syncthreads();
-            if (TIMING) { t1 = __builtin_readcyclecounter(); tc[3] += t1 - t0; }
-        }
-#undef X_MFMA
+        auto after_c = [&]() __attribute__((always_inline)) { if (TIMING) { t1 = __builtin_readcyclecounter(); tc[1] += t1 - t0; } };
+        auto after_m = [&]() __attribute__((always_inline)) { if (TIMING) { t1 = __builtin_readcyclecounter(); tc[3] += t1 - t0; } };
+        gp_two_group_loop(ns, grp, c_phase, m_phase, after_c, after_m);
         if (TIMING && a.trace && tid == 0 && seg < 7) a.trace[(size_t)p * 32 + 4 + 4 * seg] = wall_clock64();
 
-        if (is_head) {  // publish the fragment for slot n+1 (agent-scope release by one lane)
-            const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)p * kFragFloats), 0,
-                                                                                 (int)(kFragFloats * sizeof(float)), 0x00020000);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NJ; ++ni)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        f32x4 vf;
-                        vf[0] = acc[mi][ni][r4 * 4 + 0]; vf[1] = acc[mi][ni][r4 * 4 + 1];
-                        vf[2] = acc[mi][ni][r4 * 4 + 2]; vf[3] = acc[mi][ni][r4 * 4 + 3];
-                        const u32x4 v = __builtin_bit_cast(u32x4, vf);
-                        __builtin_amdgcn_raw_buffer_store_b128(v, rf, (unsigned)tid * 16u, (unsigned)(((mi * NJ + ni) * 4 + r4) * TNT) * 16u, 0);
-                    }
-            // (write-through `sc1` stores through inline asm, which the guide prices at 3.0 us against 8.2 us per 64 KB-per-workgroup
-            // publish, measured 17 -> 14 us per 256 KB here: all slots publish at once and the 48 MB are bandwidth -- not kept)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (!(a.dp & 2))  // test hook (gp_gemm_planes256_set_dp(.. | 2)): a LOST hand-off -> the waiter must time out and flag it
-                    __hip_atomic_store(a.flags + p, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        if (is_head) {  // publish the fragment for the slot that continues (or owns) the tile
+            // test hook (gp_gemm_planes256_set_dp(.. | 2), probe builds): a LOST hand-off -> the waiter must time out and flag it
+            gp_frag_publish<NJ>(acc, a.partial, p, a.flags, a.epoch, !(a.dp & 2));
         } else {
             if (kParSplit && is_rest) {
-                // Parallel split-K (fewer tiles than slots: B < 64 crops at ViT-L).  Every slot of this tile started from a zero
-                // accumulator and ran its own k range at the same time; the slot holding the LAST range owns the tile: it adds
-                // the published partial accumulators of the slots before it -- in slot order, nearest first: a fixed order, the
-                // result depends on the shape only -- and runs the epilogue.  (The serial hand-over above keeps a split tile's
-                // summation order but makes its slots wait for each other: with T < slots every tile is split and a launch
-                // would take as long as one whole tile.)
-                const int m_lo = n - (par_S - 1);   // the S - 1 slots before this one hold the earlier k ranges of the tile
-                if (tid == 0) {
-                    for (int m = n - 1; m >= m_lo; --m) {
-                        int spins = 0;
-                        while (__hip_atomic_load(a.flags + (x + 8 * m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                            __builtin_amdgcn_s_sleep(16);
-                            if (++spins > kSpin) {
-                                __hip_atomic_store(a.flags + kErrWord, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                gp_raise(a.status, GP_ST_HANDOFF_SPLIT);
-                                break;
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                }
-                __syncthreads();
-                for (int m = n - 1; m >= m_lo; --m) {
-                    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)(x + 8 * m) * kFragFloats), 0,
-                                                                                         (int)(kFragFloats * sizeof(float)), 0x00020000);
-                    constexpr int RQ = 4;  // 16-byte loads in flight per lane (then their 16 adds); more spills in the GELU build
-#pragma unroll
-                    for (int q0 = 0; q0 < 8 * NJ; q0 += RQ) {
-                        u32x4 v[RQ];
-#pragma unroll
-                        for (int u = 0; u < RQ; ++u) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rf, (unsigned)tid * 16u, (unsigned)((q0 + u) * TNT) * 16u, 0);
-#pragma unroll
-                        for (int u = 0; u < RQ; ++u) {
-                            const int f = q0 + u, mi = f / (4 * NJ), ni = (f >> 2) % NJ, r4 = f & 3;
-                            const f32x4 vf = __builtin_bit_cast(f32x4, v[u]);
-                            acc[mi][ni][r4 * 4 + 0] += vf[0]; acc[mi][ni][r4 * 4 + 1] += vf[1];
-                            acc[mi][ni][r4 * 4 + 2] += vf[2]; acc[mi][ni][r4 * 4 + 3] += vf[3];
-                        }
-                    }
-                }
+                // Parallel split-K (fewer tiles than slots: B < 64 crops at ViT-L; GpSlotPlan): this slot holds the LAST k range of its
+                // tile and owns it: it adds the published partial accumulators of the S - 1 slots before it, nearest first
+                const int m_lo = n - (par_S - 1);
+                gp_handoff_wait(a.flags, x + 8 * (n - 1), x + 8 * m_lo, 8, a.epoch, a.status);
+                constexpr int RQ = 4;  // 16-byte loads in flight per lane (then their 16 adds); more spills in the GELU build
+                for (int m = n - 1; m >= m_lo; --m) gp_frag_add<NJ, RQ>(acc, a.partial, x + 8 * m);
             }
             int tid_ = threadIdx.x;
             asm volatile("" : "+v"(tid_));  // keep the epilogue's address arithmetic inside the segment loop
             __syncthreads();                // every wave has read its last operand fragments: the buffers are free
             char* wl = reinterpret_cast<char*>(lds) + (tid_ >> 6) * 16384;
-            if constexpr (EPI == PEPI_GELU_PLANES || EPI == PEPI_BIAS_I_PLANES)
+            if constexpr (EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES)
                 epilogue_planes_thin<EPI, NJ, kParSplit ? 1 : 4>(a, acc, wl, i0 + 64 * wr, j0 + 32 * NJ * wc, tid_ & 63, reinterpret_cast<const float*>(lds + 2 * TBUF) + 64 * wr);
             else
                 epilogue_f32_lds<EPI, NJ, !kParSplit>(a, acc, reinterpret_cast<float*>(wl), i0 + 64 * wr, j0 + 32 * NJ * wc, tid_ & 63);
@@ -1177,13 +940,13 @@ int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const
     GpProfScope prof(GP_PROF_GEMM_SPLIT, 2.0 * I * J * K, st);
     switch (epilogue) {
 #ifdef GP_PROBES   // plain / ReLU epilogues: tests of the tile machinery only (the ViT's f32-activation fallback uses 1-4)
-        case XEPI_NONE: launch256<XEPI_NONE>(a, act_is_b != 0, kSlots, st); break;
-        case XEPI_BIAS_I_RELU: launch256<XEPI_BIAS_I_RELU>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_NONE: launch256<GP_EPI_NONE>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_BIAS_I_RELU: launch256<GP_EPI_BIAS_I_RELU>(a, act_is_b != 0, kSlots, st); break;
 #endif
-        case XEPI_BIAS_I: launch256<XEPI_BIAS_I>(a, act_is_b != 0, kSlots, st); break;
-        case XEPI_BIAS_I_GELU: launch256<XEPI_BIAS_I_GELU>(a, act_is_b != 0, kSlots, st); break;
-        case XEPI_BIAS_I_SCALE_RES: launch256<XEPI_BIAS_I_SCALE_RES>(a, act_is_b != 0, kSlots, st); break;
-        case XEPI_BIAS_J: launch256<XEPI_BIAS_J>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_BIAS_I: launch256<GP_EPI_BIAS_I>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_BIAS_I_GELU: launch256<GP_EPI_BIAS_I_GELU>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_BIAS_I_SCALE_RES: launch256<GP_EPI_BIAS_I_SCALE_RES>(a, act_is_b != 0, kSlots, st); break;
+        case GP_EPI_BIAS_J: launch256<GP_EPI_BIAS_J>(a, act_is_b != 0, kSlots, st); break;
         default: GP_REQUIRE(false, "gp_gemm_split256: epilogue %d is not built (product: 1-4; 0 and 5 need -DGP_PROBES)", epilogue);
     }
     GP_CHECK_LAUNCH("gp_gemm_split256");
@@ -1238,12 +1001,12 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
                    ((uintptr_t)bhi % 16 == 0) && ((uintptr_t)blo % 16 == 0) && ((uintptr_t)scratch % 16 == 0),
                "gp_gemm_planes256: null / misaligned operand");
     GP_REQUIRE((long long)I * K * 2 < (1ll << 31) && (long long)J * K * 2 < (1ll << 31), "gp_gemm_planes256: operand planes too large");
-    const bool planes_out = epilogue == PEPI_GELU_PLANES || epilogue == PEPI_BIAS_I_PLANES;
+    const bool planes_out = epilogue == GP_EPI_GELU_PLANES || epilogue == GP_EPI_BIAS_I_PLANES;
     if (planes_out)
         GP_REQUIRE(ohi && olo && ldo % 4 == 0 && ((uintptr_t)ohi % 8 == 0) && ((uintptr_t)olo % 8 == 0) && bias, "gp_gemm_planes256: bad plane output");
     if (!planes_out)
         GP_REQUIRE(D && (long long)I * ldd < (1ll << 31) && (long long)I * (ldr > 0 ? ldr : 1) < (1ll << 31) && ldd % 4 == 0 && ldr % 4 == 0 &&
-                       ((uintptr_t)D % 16 == 0) && ((uintptr_t)res % 16 == 0) && (epilogue != XEPI_BIAS_J || (uintptr_t)bias % 16 == 0),
+                       ((uintptr_t)D % 16 == 0) && ((uintptr_t)res % 16 == 0) && (epilogue != GP_EPI_BIAS_J || (uintptr_t)bias % 16 == 0),
                    "gp_gemm_planes256: bad f32 output (16-byte rows)");
     if (planes_out)
         GP_REQUIRE(ldo % 8 == 0 && ((uintptr_t)ohi % 16 == 0) && ((uintptr_t)olo % 16 == 0), "gp_gemm_planes256: plane output rows must be 16-byte aligned");
@@ -1267,16 +1030,16 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     // plain GEMMs)
 #ifdef GP_PROBES
 #define GP_PLANES_EXTRA(...)                                                                                              \
-    case XEPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_NONE, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;           \
-    case XEPI_BIAS_I: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
-    case XEPI_BIAS_I_GELU: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_GELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break; \
-    case XEPI_BIAS_J: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_J, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
-    case XEPI_BIAS_I_RELU: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_RELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+    case GP_EPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;           \
+    case GP_EPI_BIAS_I: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
+    case GP_EPI_BIAS_I_GELU: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_GELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break; \
+    case GP_EPI_BIAS_J: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_J, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
+    case GP_EPI_BIAS_I_RELU: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_RELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;
     if (trace && a.par) {  // probe build of the parallel split-K kernel with per-slot time stamps
         switch (epilogue) {
-            case XEPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_GELU_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
             default: GP_REQUIRE(false, "gp_gemm_planes256_trace: epilogue %d has no traced parallel build", epilogue);
         }
         GP_CHECK_LAUNCH("gp_gemm_planes256_trace/par");
@@ -1284,10 +1047,10 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     }
     if (trace) {  // probe build with per-slot time stamps
         switch (epilogue) {
-            case XEPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case XEPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_GELU_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
             default: GP_REQUIRE(false, "gp_gemm_planes256_trace: epilogue %d has no traced build", epilogue);
         }
         GP_CHECK_LAUNCH("gp_gemm_planes256_trace");
@@ -1303,33 +1066,33 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     // style over all slots by the serial hand-over build was measured too: ViT-L forward at 12 / 16 / 40 / 48 crops 8.55 -> 8.95,
     // 10.39 -> 10.44, 22.95 -> 22.5, 25.19 -> 25.55 ms -- the hand-overs cost what the balance gains; not kept.)
     const long long T256 = (long long)a.tiles_i * a.tiles_j;
-    const bool epi_half = epilogue == XEPI_BIAS_I_SCALE_RES || epilogue == PEPI_GELU_PLANES || epilogue == PEPI_BIAS_I_PLANES;
+    const bool epi_half = epilogue == GP_EPI_BIAS_I_SCALE_RES || epilogue == GP_EPI_GELU_PLANES || epilogue == GP_EPI_BIAS_I_PLANES;
     if (a.par && g_planes_half && epi_half && 2 * T256 <= kSlots) {
         a.tiles_j = J_main / (TB / 2);
         switch (epilogue) {
-            case XEPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_GELU_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            default: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            default: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
         }
         GP_CHECK_LAUNCH("gp_gemm_planes256/par128");
         return GP_OK;
     }
-    if (a.par && 2 * T256 > kSlots && (epilogue == XEPI_BIAS_I_SCALE_RES || epilogue == PEPI_BIAS_I_PLANES)) {
+    if (a.par && 2 * T256 > kSlots && (epilogue == GP_EPI_BIAS_I_SCALE_RES || epilogue == GP_EPI_BIAS_I_PLANES)) {
         // 129-255 whole tiles, one per slot (S = floor(256 / tiles) = 1): the PAR build WITHOUT the split-K reduction (see PSPLIT)
         a.par = 1;
-        if (epilogue == XEPI_BIAS_I_SCALE_RES)
-            hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
+        if (epilogue == GP_EPI_BIAS_I_SCALE_RES)
+            hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
         else
-            hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
+            hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
         GP_CHECK_LAUNCH("gp_gemm_planes256/par-whole");
         return GP_OK;
     }
     if (a.par) {  // fewer tiles than slots: the parallel split-K build (its own instantiation: the serial hand-over kernel keeps its registers)
         switch (epilogue) {
             GP_PLANES_EXTRA(false, true)
-            case XEPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_GELU_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case PEPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
             default: GP_REQUIRE(false, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
         }
         GP_CHECK_LAUNCH("gp_gemm_planes256/par");
@@ -1337,9 +1100,9 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     }
     switch (epilogue) {
         GP_PLANES_EXTRA(false)
-        case XEPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_BIAS_I_SCALE_RES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        case PEPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_GELU_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        case PEPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<PEPI_BIAS_I_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+        case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+        case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
+        case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
         default: GP_REQUIRE(false, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
     }
 #undef GP_PLANES_EXTRA
@@ -1407,7 +1170,7 @@ int gp_gemm_planes256_timing(const void* a_hi, const void* a_lo, const void* b_h
             reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, kOutScale, g_planes_dp};
     if (++g_epoch256 == 0) ++g_epoch256;
     a.epoch = (int)g_epoch256;
-    hipLaunchKernelGGL((gemm_planes256_kernel<XEPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, (hipStream_t)stream, a);
     GP_CHECK_LAUNCH("gp_gemm_planes256_timing");
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     return hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_t256), 8 * sizeof(unsigned long long)) == hipSuccess ? GP_OK : GP_ELAUNCH;

@@ -9,7 +9,7 @@
 //
 // Token column of image b, token t:  m = b * T + t   (T = 257, no per-image padding);
 // all activation matrices have Mpad = round_up(B*T, 256) columns.
-#include "gp_common.h"
+#include "gp_tile256.h"  // gp_hi_pair (+ gp_common.h)
 
 int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J,
                    int K, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
 }
 
 // tokens = cat(cls, patches) + pos (HF modeling_dinov2.py:108-112) and the zeros of the pad columns are the patch-embed GEMM's
-// epilogue (gp_gemm.hip: EPI_EMBED)
+// epilogue (gp_gemm.hip: GP_EPI_EMBED)
 
 // ---- LayerNorm over C of channel-major X [C][Mpad], wide: block = 64 token columns x 16 channel slices (16 waves, 4128 waves in flight at
 // B=64 instead of 258), three short passes; the block's 64 x C tile is re-read from L2.
@@ -602,17 +602,10 @@ __device__ __forceinline__ unsigned lds_addr(const _Float16* p)  // byte address
 
 constexpr int ATH = 512;  // threads: eight waves = the eight full 32-query tiles (two waves per SIMD)
 
-// Pair conversions of the plane producers (as the GEMM epilogues, gp_split256.hip): two f32 values -> their packed f16 hi pair in one
-// v_cvt_pk_f16_f32, and the packed lo pair f16(v - hi) in one v_fma_mixlo_f16 + one v_fma_mixhi_f16 that read the f16 hi straight
-// from the packed register (v - hi is exact in f32, so the mixed fma's single rounding equals subtraction + conversion).
-typedef _Float16 av16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned attn_hi_pair(float v0, float v1)
-{
-    av16x2 h;
-    h[0] = (_Float16)v0;
-    h[1] = (_Float16)v1;
-    return __builtin_bit_cast(unsigned, h);
-}
+// Pair conversions of the plane producers: gp_hi_pair (gp_tile256.h, as the GEMM epilogues) packs two f32 values' f16 hi pair in one
+// v_cvt_pk_f16_f32.  The lo pair f16(v - hi) keeps a helper of its own: the same v_fma_mixlo_f16 + v_fma_mixhi_f16 as gp_lo_pair (v - hi
+// is exact in f32, so the mixed fma's single rounding equals subtraction + conversion) FOLLOWED BY s_nop 1 -- not the same instruction
+// sequence, and needed here only.
 __device__ __forceinline__ unsigned attn_lo_pair(float v0, float v1, unsigned hi)
 {
     unsigned lo;
@@ -801,7 +794,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(const _Float16* __
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
                     const float px = s[t][8 * m + e], py = s[t][8 * m + e + 1];
-                    const unsigned hp = attn_hi_pair(px, py);
+                    const unsigned hp = gp_hi_pair(px, py);
                     phu[e >> 1] = hp;
                     plu[e >> 1] = attn_lo_pair(px, py, hp);
                 }
@@ -843,7 +836,7 @@ __global__ __launch_bounds__(ATH) void attention_split_kernel(const _Float16* __
                     // the exact product) for hi while lo subtracts from the f32-rounded product -- at an f16 tie the two disagree by
                     // one f16 ulp of hi (seen as sparse 2^-k errors)
                     asm volatile("" : "+v"(v0), "+v"(v1));
-                    const unsigned hp = attn_hi_pair(v0, v1);
+                    const unsigned hp = gp_hi_pair(v0, v1);
                     hv[e >> 1] = hp;
                     lv[e >> 1] = attn_lo_pair(v0, v1, hp);
                 }
@@ -1220,7 +1213,7 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
     GP_CHECK_LAUNCH("gp_vit_forward/im2col");
     // BP = B*256 is always a multiple of 128.  Epilogue 8: + bias, + position table, re-indexed b*256+p -> b*257+1+p straight into X,
     // with the class-token columns and the zeroed pad columns
-    if ((rc = gp_gemm_launch(weights[W_PATCH_WT], C, col, BP, X, Mpad, C, BP, KPE_PAD, 8 /*EMBED*/,
+    if ((rc = gp_gemm_launch(weights[W_PATCH_WT], C, col, BP, X, Mpad, C, BP, KPE_PAD, GP_EPI_EMBED,
                              weights[W_PATCH_B], weights[W_POS_T], weights[W_CLS_POS], Mpad, SK, st)))
         return rc;
 
@@ -1262,14 +1255,14 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
                                    gp_gemm_planes256_usable(3 * C, Mpad, Mtok, C);
             if (fused_qkv) {
                 if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 3 * C, Mpad, Mtok, C,
-                                                   7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                                                   GP_EPI_BIAS_I_PLANES, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
                     return rc;
             } else {
                 if ((rc = gp_gemm_planes256_launch(sq[S_QK_HI], sq[S_QK_LO], Hhi, Hlo, nullptr, 0, Ahi, Alo, 3 * C, 2 * C, Mpad, Mtok, C,
-                                                   7 /*BIAS_I -> planes*/, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                                                   GP_EPI_BIAS_I_PLANES, w[L_QK_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
                     return rc;
                 if ((rc = gp_gemm_planes256_launch(sq[S_V_HI], sq[S_V_LO], Hhi, Hlo, nullptr, 0, Ahi + 2 * C, Alo + 2 * C, 3 * C, C, Mpad, Mtok, C,
-                                                   7 /*BIAS_I -> planes*/, w[L_V_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
+                                                   GP_EPI_BIAS_I_PLANES, w[L_V_B], nullptr, nullptr, 0, os_ln1, SK, st, nullptr, &po_qkv)))
                     return rc;
             }
             {
@@ -1280,17 +1273,17 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
             GP_CHECK_LAUNCH("gp_vit_forward/attention_split");
             // x = x + ls1 * proj(attn)   (the attention output carries the q | k | v scale)
             if ((rc = gp_gemm_planes256_launch(sq[S_PROJ_HI], sq[S_PROJ_LO], Hhi, Hlo, X, Mpad, nullptr, nullptr, 0, C, Mpad, Mtok, C,
-                                               3 /*BIAS_I_SCALE_RES*/, w[L_PROJ_B], w[L_LS1], X, Mpad, os_qkv, SK, st)))
+                                               GP_EPI_BIAS_I_SCALE_RES, w[L_PROJ_B], w[L_LS1], X, Mpad, os_qkv, SK, st)))
                 return rc;
             launch_layernorm_planes(X, Hhi, Hlo, w[L_LN2_G], w[L_LN2_B], C, Mpad, ln_eps, st, ps[PS_LN2], am ? am + PS_LN2 : nullptr, Mtok);
             GP_CHECK_LAUNCH("gp_vit_forward/layernorm_planes");
             // gelu(fc1(.)) straight to planes [Mpad][mlp_dim]
             if ((rc = gp_gemm_planes256_launch(sq[S_FC1_HI], sq[S_FC1_LO], Hhi, Hlo, nullptr, 0, Fhi, Flo, mlp_dim, mlp_dim, Mpad, Mtok, C,
-                                               6 /*GELU -> planes*/, w[L_FC1_B], nullptr, nullptr, 0, os_ln2, SK, st, nullptr, &po_gelu)))
+                                               GP_EPI_GELU_PLANES, w[L_FC1_B], nullptr, nullptr, 0, os_ln2, SK, st, nullptr, &po_gelu)))
                 return rc;
             // x = x + ls2 * fc2(.)
             if ((rc = gp_gemm_planes256_launch(sq[S_FC2_HI], sq[S_FC2_LO], Fhi, Flo, X, Mpad, nullptr, nullptr, 0, C, Mpad, Mtok, mlp_dim,
-                                               3 /*BIAS_I_SCALE_RES*/, w[L_FC2_B], w[L_LS2], X, Mpad, os_gelu, SK, st)))
+                                               GP_EPI_BIAS_I_SCALE_RES, w[L_FC2_B], w[L_LS2], X, Mpad, os_gelu, SK, st)))
                 return rc;
         }
     }
@@ -1309,28 +1302,28 @@ int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int he
             return gp_gemm_split_launch(act, ld_act, sp[which], sp[which + 1], D, ldd, I, J, K, act_is_b, epi, bias, scale, res, ldr, st);
         };
         // Q,K channel-major [2C][Mpad]
-        if (sp) rc = sgemm(Hn, Mpad, S_QK_HI, QK, Mpad, 2 * C, Mpad, C, 1, 1, w[L_QK_B], nullptr, nullptr, 0);
-        else rc = gp_gemm_launch(w[L_QK_WT], 2 * C, Hn, Mpad, QK, Mpad, 2 * C, Mpad, C, 1, w[L_QK_B], nullptr, nullptr, 0, SK, st);
+        if (sp) rc = sgemm(Hn, Mpad, S_QK_HI, QK, Mpad, 2 * C, Mpad, C, 1, GP_EPI_BIAS_I, w[L_QK_B], nullptr, nullptr, 0);
+        else rc = gp_gemm_launch(w[L_QK_WT], 2 * C, Hn, Mpad, QK, Mpad, 2 * C, Mpad, C, GP_EPI_BIAS_I, w[L_QK_B], nullptr, nullptr, 0, SK, st);
         if (rc) return rc;
         // V token-major [Mpad][C]: swap operand roles (A = activations, B = weights), bias along j
-        if (sp) rc = sgemm(Hn, Mpad, S_V_HI, Vt, C, Mpad, C, C, 0, 4 /*BIAS_J*/, w[L_V_B], nullptr, nullptr, 0);
-        else rc = gp_gemm_launch(Hn, Mpad, w[L_V_WT], C, Vt, C, Mpad, C, C, 4 /*BIAS_J*/, w[L_V_B], nullptr, nullptr, 0, SK, st);
+        if (sp) rc = sgemm(Hn, Mpad, S_V_HI, Vt, C, Mpad, C, C, 0, GP_EPI_BIAS_J, w[L_V_B], nullptr, nullptr, 0);
+        else rc = gp_gemm_launch(Hn, Mpad, w[L_V_WT], C, Vt, C, Mpad, C, C, GP_EPI_BIAS_J, w[L_V_B], nullptr, nullptr, 0, SK, st);
         if (rc) return rc;
         launch_attention_f32(QK, Vt, Hn, B, heads, C, Mpad, st);
         GP_CHECK_LAUNCH("gp_vit_forward/attention");
         // x = x + ls1 * proj(attn)
-        if (sp) rc = sgemm(Hn, Mpad, S_PROJ_HI, X, Mpad, C, Mpad, C, 1, 3, w[L_PROJ_B], w[L_LS1], X, Mpad);
-        else rc = gp_gemm_launch(w[L_PROJ_WT], C, Hn, Mpad, X, Mpad, C, Mpad, C, 3, w[L_PROJ_B], w[L_LS1], X, Mpad, SK, st);
+        if (sp) rc = sgemm(Hn, Mpad, S_PROJ_HI, X, Mpad, C, Mpad, C, 1, GP_EPI_BIAS_I_SCALE_RES, w[L_PROJ_B], w[L_LS1], X, Mpad);
+        else rc = gp_gemm_launch(w[L_PROJ_WT], C, Hn, Mpad, X, Mpad, C, Mpad, C, GP_EPI_BIAS_I_SCALE_RES, w[L_PROJ_B], w[L_LS1], X, Mpad, SK, st);
         if (rc) return rc;
         launch_layernorm(X, Hn, w[L_LN2_G], w[L_LN2_B], C, Mpad, ln_eps, st);
         GP_CHECK_LAUNCH("gp_vit_forward/layernorm");
-        if (sp) rc = sgemm(Hn, Mpad, S_FC1_HI, F, Mpad, mlp_dim, Mpad, C, 1, 2 /*GELU*/, w[L_FC1_B], nullptr, nullptr, 0);
-        else rc = gp_gemm_launch(w[L_FC1_WT], mlp_dim, Hn, Mpad, F, Mpad, mlp_dim, Mpad, C, 2 /*GELU*/, w[L_FC1_B], nullptr,
+        if (sp) rc = sgemm(Hn, Mpad, S_FC1_HI, F, Mpad, mlp_dim, Mpad, C, 1, GP_EPI_BIAS_I_GELU, w[L_FC1_B], nullptr, nullptr, 0);
+        else rc = gp_gemm_launch(w[L_FC1_WT], mlp_dim, Hn, Mpad, F, Mpad, mlp_dim, Mpad, C, GP_EPI_BIAS_I_GELU, w[L_FC1_B], nullptr,
                                  nullptr, 0, SK, st);
         if (rc) return rc;
         // x = x + ls2 * fc2(gelu(fc1))
-        if (sp) rc = sgemm(F, Mpad, S_FC2_HI, X, Mpad, C, Mpad, mlp_dim, 1, 3, w[L_FC2_B], w[L_LS2], X, Mpad);
-        else rc = gp_gemm_launch(w[L_FC2_WT], C, F, Mpad, X, Mpad, C, Mpad, mlp_dim, 3, w[L_FC2_B], w[L_LS2], X, Mpad, SK, st);
+        if (sp) rc = sgemm(F, Mpad, S_FC2_HI, X, Mpad, C, Mpad, mlp_dim, 1, GP_EPI_BIAS_I_SCALE_RES, w[L_FC2_B], w[L_LS2], X, Mpad);
+        else rc = gp_gemm_launch(w[L_FC2_WT], C, F, Mpad, X, Mpad, C, Mpad, mlp_dim, GP_EPI_BIAS_I_SCALE_RES, w[L_FC2_B], w[L_LS2], X, Mpad, SK, st);
         if (rc) return rc;
     }
     if (normalize == 2) {  // the split matcher's query planes instead of the f32 features (include/gigapose_hip.h)

@@ -1,4 +1,4 @@
-"""GPU: the ViT embedding as the patch-embed GEMM's epilogue (gp_gemm.hip: EPI_EMBED -- + bias, + position table, column
+"""GPU: the ViT embedding as the patch-embed GEMM's epilogue (gp_gemm.hip: GP_EPI_EMBED -- + bias, + position table, column
 b * 256 + p re-indexed to token b * 257 + 1 + p of the residual stream, class-token columns, zeroed pad columns) against a float64
 restatement of HF modeling_dinov2.py:97-112 (and :199-380 for the one-block case).
 
