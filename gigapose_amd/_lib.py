@@ -7,12 +7,15 @@ loaded (same SONAME libamdhip64.so.7) and shares its streams and allocations.
 """
 import ctypes
 import os
+import re
 
+import numpy as np
 import torch  # noqa: F401  (must precede the CDLL so both use one HIP runtime)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIGAPOSE_LIB") or os.path.join(_HERE, "libgigapose_hip.so")   # GIGAPOSE_LIB: another build of the same sources (A/B of two commits, tools/)
 PROBE_LIB_PATH = os.path.join(_HERE, "libgigapose_hip_probe.so")   # the same sources with -DGP_PROBES (include/gigapose_hip_probe.h)
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")   # the C headers: where every signature is stated (parse_prototypes)
 _lib = None          # the library calls go to: the product library unless probe_library() is active
 _product = None
 _probe = None
@@ -37,51 +40,117 @@ def default_numerics():
     return mode
 
 
-def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    import subprocess
-
-    r = subprocess.run(["make", "-j8", "-C", os.path.join(_HERE, "csrc")], capture_output=True, text=True)
-    if verbose or r.returncode != 0:
-        print(r.stdout, r.stderr)
-    if r.returncode != 0:
-        raise GigaPoseHipError("building libgigapose_hip.so failed")
-    return LIB_PATH
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
 
 
-def _load(path):
+def parse_prototypes(text):
+    """The `ret name(params);` prototypes of a C header -> {name: (restype, [argtypes])}.  Reads what include/*.h use and is no C front end: comments,
+    preprocessor lines and the extern "C" braces are dropped; a parameter is a pointer (-> c_void_p: None, an integer, a ctypes array or byref) or a named
+    int, float, double, long long or size_t; a function returns int, size_t, void or const char*.  Anything else raises: a prototype is never skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
+    protos = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?) ?(\w+) ?\((.*)\)", stmt)
+        ret = m and re.sub(r" ?\* ?", "*", m.group(1))
+        params = m and ([] if m.group(3).strip() in ("", "void") else m.group(3).split(","))
+        kinds = m and ["*" if "*" in p else " ".join(p.split()[:-1]) for p in params]   # a scalar is `type name`
+        if not m or ret not in _RETURNS or m.group(2) in protos or any(k != "*" and k not in _SCALARS for k in kinds):
+            raise GigaPoseHipError(f"cannot read the prototype `{stmt}`: expected `int|size_t|void|const char* name(params)`, each name once, "
+                                   f"every parameter a pointer or a named {' | '.join(_SCALARS)}")
+        protos[m.group(2)] = (_RETURNS[ret], [ctypes.c_void_p if k == "*" else _SCALARS[k] for k in kinds])
+    return protos
+
+
+def declared(*headers):
+    """The prototypes of include/<header>, ... together; a missing header is an error like a missing library."""
+    protos = {}
+    for path in (os.path.join(INCLUDE_DIR, h) for h in headers):
+        if not os.path.exists(path):
+            raise GigaPoseHipError(f"{path} not found: the ctypes signatures are read from the C headers beside the package (INTEGRATION.md section 2)")
+        with open(path) as fh:
+            protos.update(parse_prototypes(fh.read()))
+    return protos
+
+
+def _load(path, *headers, scope=" for the hot path"):
+    """CDLL(path) with restype and argtypes of every function the headers declare: a wrong argument kind is a ctypes.ArgumentError before the library is entered."""
     if not os.path.exists(path):
-        raise GigaPoseHipError(
-            f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(there is deliberately no CPU / PyTorch fallback for the hot path)")
+        raise GigaPoseHipError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                               f"(there is deliberately no CPU / PyTorch fallback{scope})")
     h = ctypes.CDLL(path)
-    h.gp_last_error.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in declared(*headers).items():
+        getattr(h, name).restype, getattr(h, name).argtypes = restype, argtypes
     return h
 
 
-class SideLibrary:
-    """A front-end library next to this file, exporting `<prefix>_*`: loaded on first use; a missing file is an error."""
+def _invoke(h, name, args):
+    fn = getattr(h, name)
+    if len(args) != len(fn.argtypes):   # ctypes itself rejects too few arguments but lets extra ones through
+        raise TypeError(f"{name} takes {len(fn.argtypes)} arguments (include/), got {len(args)}")
+    return fn(*args)
 
-    def __init__(self, file_name, prefix, restypes=None):
+
+class SideLibrary:
+    """A front-end library next to this file, exporting `<prefix>_*` as include/<its name>.h declares them: loaded on first use; a missing file is an error."""
+
+    def __init__(self, file_name, prefix):
         self.path = os.path.join(_HERE, file_name)
+        self.header = file_name[len("lib"):-len(".so")] + ".h"   # libgigapose_eval.so <-> include/gigapose_eval.h
         self.prefix = prefix
-        self._restypes = dict(restypes or {}, **{prefix + "_last_error": ctypes.c_char_p})   # entry points that do not return an int
         self._handle = None
 
     def lib(self):
         if self._handle is None:
-            if not os.path.exists(self.path):
-                raise GigaPoseHipError(f"{self.path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                                       "(there is deliberately no CPU / PyTorch fallback)")
-            self._handle = ctypes.CDLL(self.path)
-            for name, restype in self._restypes.items():
-                getattr(self._handle, name).restype = restype
+            self._handle = _load(self.path, self.header, scope="")
         return self._handle
 
     def call(self, name, *args):
-        rc = getattr(self.lib(), name)(*args)
+        rc = _invoke(self.lib(), name, args)
         if rc != 0:
             raise GigaPoseHipError(f"{name} failed (rc={rc}): {getattr(self.lib(), self.prefix + '_last_error')().decode()}")
+
+
+def arg(t, dtype, shape, who, what):
+    """Argument checks the front-end modules share.  Type, dtype, shape and layout of one argument (ValueError); on_gpu checks the devices once every argument has passed."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{who}: {what} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {what} is not contiguous")
+    return t
+
+
+def on_gpu(who, **tensors):
+    for what, t in tensors.items():
+        if not t.is_cuda:
+            raise GigaPoseHipError(f"{who} needs {what} on the GPU (no CPU fallback)")
+
+
+def checked(a, dtype, shape, who, what):
+    """A numpy array or a tensor anywhere -> a tensor whose shape and kind of dtype are checked; upload moves it."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        raise ValueError(f"{who}: expected {what} {tuple('*' if s is None else s for s in shape)}, got {tuple(t.shape)}")
+    if t.dtype.is_floating_point != dtype.is_floating_point:
+        raise ValueError(f"{who}: {what} has dtype {t.dtype}, expected {dtype}")
+    return t, dtype
+
+
+def upload(who, device, *checked):
+    if torch.device(device).type != "cuda":
+        raise GigaPoseHipError(f"{who} needs a GPU device (no CPU fallback)")
+    return [t.to(device=device, dtype=dtype).contiguous() for t, dtype in checked]
+
+
+def on_device(t, dtype, shape, who, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise GigaPoseHipError(f"{who} needs {what} on the GPU (no CPU fallback)")
+    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
 
 
 def chunked(N, limit):
@@ -102,7 +171,7 @@ def lib():
     global _lib, _product
     if _lib is None:
         if _product is None:
-            _product = _load(LIB_PATH)
+            _product = _load(LIB_PATH, "gigapose_hip.h")
         _lib = _product
     return _lib
 
@@ -117,7 +186,7 @@ class probe_library:
         global _lib, _probe
         lib()
         if _probe is None:
-            _probe = _load(PROBE_LIB_PATH)
+            _probe = _load(PROBE_LIB_PATH, "gigapose_hip.h", "gigapose_hip_probe.h")
         self._prev, _lib = _lib, _probe
         _reregister()
         return _probe
@@ -206,7 +275,7 @@ def ptr(t):
 
 
 def call(name, *args):
-    rc = getattr(lib(), name)(*args)
+    rc = _invoke(lib(), name, args)
     if rc != 0:
         raise GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gp_last_error().decode()}")
 

@@ -15,6 +15,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "gigapose_dist.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpd
 #include "../gp_front.h"
 

@@ -13,6 +13,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "gigapose_eval.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpe
 #include "../gp_front.h"
 

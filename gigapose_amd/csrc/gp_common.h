@@ -7,6 +7,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gigapose_hip.h"  // the C ABI (-I../../include): a definition that differs from its declaration is a compile error
+#ifdef GP_PROBES
+#include "gigapose_hip_probe.h"
+#endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -104,6 +108,25 @@ struct GpProfScope {
     int idx_;
     hipStream_t st_;
 };
+
+// The launchers one file defines and another calls (gp_vit.hip, gp_ist.hip; the C entry points wrap them), declared here and nowhere else: gp_gemm.hip (sk_ws:
+// optional stream-K scratch), gp_split.hip (j_limit: device int or null, tiles of columns j >= *j_limit exit at once), gp_split256.hip (J_valid <= J rows of B carry data).
+int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J, int K, int epilogue,
+                   const float* bias, const float* scale, const float* res, int ldr, float* sk_ws, hipStream_t st);
+size_t gp_gemm_streamk_bytes(), gp_gemm_streamk_header_bytes();   // of the scratch; of what a reset zeroes in it
+int gp_gemm_streamk_reset_launch(float* sk_ws, hipStream_t st);
+int gp_gemm_split_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
+                         int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr, hipStream_t st);
+int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K, int act_is_b,
+                                 int epilogue, const float* bias, const float* scale, const float* res, int ldr, const int* j_limit, hipStream_t st);
+bool gp_gemm_split256_usable(int I, int J, int K);
+size_t gp_gemm_split256_scratch_bytes();
+int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K, int act_is_b,
+                            int epilogue, const float* bias, const float* scale, const float* res, int ldr, float* scratch, hipStream_t st);
+bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K);
+int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi, void* olo, int ldo,
+                             int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
+                             float out_scale, float* scratch, hipStream_t st, unsigned long long* trace = nullptr, const GpPlaneOut* po = nullptr);
 
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) of the split kernels' epilogues (fc1), scaled by 2 hs (hs = 0.5: GELU itself; hs = half the plane
 // scale folds an activation plane's power-of-two scaling into it, bit for bit).  Form (round 6): erfc(|x| / sqrt 2) = 2^-Q(z), z = min(|x|, 9),

@@ -11,15 +11,7 @@
 // compact position.  Rows are independent, so a row's result does not depend on where the atomics put it.
 // (Typically 35-60 % of the 256 patches of a hypothesis carry a correspondence: 0.70 -> 0.3x ms per step.)
 // The two hidden layers are GEMMs on the transposed feature matrix X^T [2D][rows].
-#include "gp_common.h"
-
-int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J,
-                   int K, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                   float* sk_ws, hipStream_t st);
-
-int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
-                                 int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                                 const int* j_limit, hipStream_t st);
+#include "gp_common.h"  // + the GEMM launchers
 
 namespace {
 

@@ -486,12 +486,7 @@ __global__ __launch_bounds__(512, 4) void conv_split_kernel(const ConvSplitArgs 
     if (bad) gp_raise(a.status, GP_ST_SPLIT_RANGE_CONV);
 }
 
-// internal entry (gp_vit.hip).  act: f32 k-major activations [K][ld_act]; whi/wlo: pre-split weights [n_w][K].
-// act_is_b: D[i][j] = sum_k W[i][k] X[k][j]  (weights index i); else D[i][j] = sum_k X[k][i] W[j][k].
-int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
-                                 int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                                 const int* j_limit, hipStream_t st);
-
+// internal entries (gp_common.h; gp_vit.hip, gp_ist.hip)
 int gp_gemm_split_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
                          int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
                          hipStream_t st)
@@ -499,7 +494,6 @@ int gp_gemm_split_launch(const float* act, int ld_act, const void* whi, const vo
     return gp_gemm_split_launch_limited(act, ld_act, whi, wlo, D, ldd, I, J, K, act_is_b, epilogue, bias, scale, res, ldr, nullptr, st);
 }
 
-// j_limit (device int, may be null): only columns j < *j_limit carry data -- whole tiles beyond it exit at once
 int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
                                  int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
                                  const int* j_limit, hipStream_t st)

@@ -990,7 +990,7 @@ bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K)
 int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
                              void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
                              const float* res, int ldr, float out_scale, float* scratch, hipStream_t st, unsigned long long* trace,
-                             const GpPlaneOut* po = nullptr)
+                             const GpPlaneOut* po)
 {
     GP_REQUIRE(gp_gemm_planes256_usable(I, J, J_valid, K),
                "gp_gemm_planes256: I=%d, J=%d must be multiples of 256 with >= 8 tiles below J_valid=%d, K=%d of 32", I, J, J_valid, K);

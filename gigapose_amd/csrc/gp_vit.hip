@@ -9,26 +9,7 @@
 //
 // Token column of image b, token t:  m = b * T + t   (T = 257, no per-image padding);
 // all activation matrices have Mpad = round_up(B*T, 256) columns.
-#include "gp_tile256.h"  // gp_hi_pair (+ gp_common.h)
-
-int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J,
-                   int K, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                   float* sk_ws, hipStream_t st);
-int gp_gemm_split_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
-                         int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                         hipStream_t st);
-bool gp_gemm_split256_usable(int I, int J, int K);
-int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
-                            int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                            float* scratch, hipStream_t st);
-size_t gp_gemm_streamk_bytes();
-size_t gp_gemm_streamk_header_bytes();
-bool gp_gemm_split256_usable(int I, int J, int K);
-bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K);
-int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
-                             void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
-                             const float* res, int ldr, float out_scale, float* scratch, hipStream_t st, unsigned long long* trace = nullptr,
-                             const GpPlaneOut* po = nullptr);
+#include "gp_tile256.h"  // gp_hi_pair (+ gp_common.h: the GEMM launchers)
 
 namespace {
 
@@ -1085,13 +1066,7 @@ size_t gp_vit_workspace_bytes(int B, int dim, int mlp_dim)
 // per-layer table of pre-split weight planes (f16 hi / lo, PyTorch-native [out][in]) for the split-f16 mode
 // (entries 10..19, optional: the same five weights as x64 single-accumulator planes for the 256 x 256 kernel of gp_split256.hip)
 enum { S_QK_HI = 0, S_QK_LO, S_V_HI, S_V_LO, S_PROJ_HI, S_PROJ_LO, S_FC1_HI, S_FC1_LO, S_FC2_HI, S_FC2_LO, S_PER_LAYER = 10 };
-int gp_vit_forward_split2(const float* images, int B, int dim, int depth, int heads, int mlp_dim, float ln_eps,
-                          const float* const* weights, int n_weights, const void* const* split, int n_split,
-                          float* workspace, size_t workspace_bytes, float* out_features, int normalize,
-                          int stop_after_layers, const float* plane_scales, float* plane_amax, void* stream);
 
-int gp_attention_split_scaled(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int heads, int dim, int Mpad,
-                              float qkv_scale, void* stream);
 /* q | k | v planes (and the output planes) carry the power-of-two `qkv_scale` instead of the default 8 */
 int gp_attention_split_scaled(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int heads, int dim, int Mpad,
                               float qkv_scale, void* stream)

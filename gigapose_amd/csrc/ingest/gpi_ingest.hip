@@ -10,6 +10,7 @@
 // skeleton of gp_crop_geom.h, shared with gp_crop.hip's preprocess_kernel, over a pixel source that searches cum where the dense
 // one reads `masks[d][sy][sx]`, so the two routes agree bit for bit.  The host-side plumbing is gp_front.h's.
 // This library links no object of libgigapose_hip.so and exports only gpi_* names.
+#include "gigapose_ingest.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpi
 #include "../gp_front.h"
 #include "../gp_crop_geom.h"

@@ -10,6 +10,7 @@
 // This library links no object of libgigapose_hip.so or libgigapose_ingest.so and exports only gpo_* names.
 #include <limits.h>
 
+#include "gigapose_onboard.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpo
 #include "../gp_front.h"
 #include "../gp_crop_geom.h"

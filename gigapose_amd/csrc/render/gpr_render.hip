@@ -11,6 +11,7 @@
 #include <limits.h>
 #include <math.h>
 
+#include "gigapose_render.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpr
 #include "../gp_front.h"
 #include "../gp_raster_geom.h"   // Tri, setup_triangle, edge_in, edges: shared with texture/gpt_texture.hip

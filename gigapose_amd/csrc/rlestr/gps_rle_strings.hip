@@ -14,6 +14,7 @@
 // code gpi_rle_scan (csrc/ingest/gpi_ingest.hip) runs, so one launch serves a mixed batch and cum has the same bits either way.
 // The host-side plumbing is gp_front.h's.
 // This library links no object of the other libraries and exports only gps_* names.
+#include "gigapose_rlestr.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gps
 #include "../gp_front.h"
 #include "../gp_rle_scan.h"

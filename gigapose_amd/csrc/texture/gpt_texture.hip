@@ -10,6 +10,7 @@
 // This library links no object of the other libraries and exports only gpt_* names.
 #include <math.h>
 
+#include "gigapose_texture.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpt
 #include "../gp_front.h"
 #include "../gp_raster_geom.h"

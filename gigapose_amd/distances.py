@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluate import _arg, _checked, _on_gpu, _pose, _upload, group_estimates, match_greedy, read_estimates
+from .evaluate import group_estimates, match_greedy, pose_matrix, read_estimates
 
 MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_dist.h: Limits)
 MAX_VERTICES = 1 << 20
@@ -49,15 +49,15 @@ def add_sums(vertices, est, gt, symmetric, k=20):
     """gpd_add / gpd_adds (symmetric): vertices f32 (V,3), est, gt f64 (N,4,4) on the device -> sums int64 (N,), status int32 (N,)
     on the device.  N <= 65535, V <= 2^20.  The error of pair n is sums[n] / (V * 2^k) where status[n] == 0."""
     who = "add_sums"
-    vertices = _arg(vertices, torch.float32, (None, 3), who, "vertices")
-    est = _arg(est, torch.float64, (None, 4, 4), who, "est")
+    vertices = _lib.arg(vertices, torch.float32, (None, 3), who, "vertices")
+    est = _lib.arg(est, torch.float64, (None, 4, 4), who, "est")
     N, V = est.shape[0], vertices.shape[0]
-    gt = _arg(gt, torch.float64, (N, 4, 4), who, "gt")
+    gt = _lib.arg(gt, torch.float64, (N, 4, 4), who, "gt")
     _check_v(who, V)
     k = _check_k(who, k)
     if N > MAX_PAIRS_PER_CALL:
         raise ValueError(f"{who}: {N} pairs in one call (at most {MAX_PAIRS_PER_CALL}: add_errors chunks)")
-    _on_gpu(who, vertices=vertices, est=est, gt=gt)
+    _lib.on_gpu(who, vertices=vertices, est=est, gt=gt)
     sums = torch.empty(N, dtype=torch.int64, device=est.device)
     status = torch.empty(N, dtype=torch.int32, device=est.device)
     _call("gpd_adds" if symmetric else "gpd_add", _lib.ptr(vertices), _lib.i(V), _lib.ptr(est), _lib.ptr(gt), _lib.i(N), _lib.i(k),
@@ -81,13 +81,13 @@ def add_errors(vertices, est, gt, symmetric=False, k=20, device="cuda"):
     A distance is rounded to a multiple of 2^-k units before the mean is taken: the default k = 20 and millimetres give about
     1e-6 mm of resolution and a range of 2^22 mm (4 km); metres want the same k, a unit of micrometres a smaller one."""
     who = "add_errors"
-    vertices = _checked(vertices, torch.float32, (None, 3), who, "vertices")
-    est = _checked(est, torch.float64, (None, 4, 4), who, "est")
+    vertices = _lib.checked(vertices, torch.float32, (None, 3), who, "vertices")
+    est = _lib.checked(est, torch.float64, (None, 4, 4), who, "est")
     N, V = est[0].shape[0], vertices[0].shape[0]
-    gt = _checked(gt, torch.float64, (N, 4, 4), who, "gt")
+    gt = _lib.checked(gt, torch.float64, (N, 4, 4), who, "gt")
     _check_v(who, V)
     k = _check_k(who, k)
-    vertices, est, gt = _upload(who, device, vertices, est, gt)
+    vertices, est, gt = _lib.upload(who, device, vertices, est, gt)
     sums = torch.empty(N, dtype=torch.int64, device=device)
     status = torch.empty(N, dtype=torch.int32, device=device)
     for _, a, b in _lib.chunked(N, MAX_PAIRS_PER_CALL):
@@ -100,9 +100,9 @@ def add_errors(vertices, est, gt, symmetric=False, k=20, device="cuda"):
 def diameter2_key(vertices):
     """gpd_diameter2: vertices f32 (V,3) on the device -> int64 (1,) on the device holding the 64 bits of the key."""
     who = "diameter2_key"
-    vertices = _arg(vertices, torch.float32, (None, 3), who, "vertices")
+    vertices = _lib.arg(vertices, torch.float32, (None, 3), who, "vertices")
     _check_v(who, vertices.shape[0])
-    _on_gpu(who, vertices=vertices)
+    _lib.on_gpu(who, vertices=vertices)
     key = torch.empty(1, dtype=torch.int64, device=vertices.device)
     _call("gpd_diameter2", _lib.ptr(vertices), _lib.i(vertices.shape[0]), _lib.ptr(key), _lib.stream_ptr())
     return key
@@ -113,9 +113,9 @@ def model_diameter(vertices, device="cuda"):
     float: the square comes from the kernel, its root is numpy's.  vertices (V,3) numpy or a tensor anywhere, 1 <= V <= 2^20; one
     vertex gives 0.0; a vertex that is not finite raises ValueError."""
     who = "model_diameter"
-    vertices = _checked(vertices, torch.float32, (None, 3), who, "vertices")
+    vertices = _lib.checked(vertices, torch.float32, (None, 3), who, "vertices")
     _check_v(who, vertices[0].shape[0])
-    vertices, = _upload(who, device, vertices)
+    vertices, = _lib.upload(who, device, vertices)
     key = int(diameter2_key(vertices).cpu().numpy().view(np.uint64)[0])
     if key == BAD_KEY or not bool(torch.isfinite(vertices).all()):
         raise ValueError(f"{who}: a vertex is not finite")
@@ -125,8 +125,8 @@ def model_diameter(vertices, device="cuda"):
 @torch.no_grad()
 def roots(x):
     """gpd_root: x f64 (n,) on the device -> the library's square root of every element (the correctly rounded one)."""
-    x = _arg(x, torch.float64, (None,), "roots", "x")
-    _on_gpu("roots", x=x)
+    x = _lib.arg(x, torch.float64, (None,), "roots", "x")
+    _lib.on_gpu("roots", x=x)
     out = torch.empty_like(x)
     _call("gpd_root", _lib.ptr(x), ctypes.c_longlong(x.shape[0]), _lib.ptr(out), _lib.stream_ptr())
     return out
@@ -208,8 +208,8 @@ class AddScorer:
                 where.append((gi, len(est), len(kept), len(g)))
                 for e in kept:
                     for h in g:
-                        est.append(_pose(e["R"], e["t"]))
-                        gt.append(_pose(h["cam_R_m2c"], h["cam_t_m2c"]))
+                        est.append(pose_matrix(e["R"], e["t"]))
+                        gt.append(pose_matrix(h["cam_R_m2c"], h["cam_t_m2c"]))
             if est:
                 est, gt = np.stack(est), np.stack(gt)
                 v = self.models[obj]["vertices"]

@@ -30,7 +30,7 @@ DEPTH_BYTES_PER_CALL = 1 << 28                       # vsd_errors: each of the t
 TAUS = tuple(round(0.05 * i, 2) for i in range(1, 11))           # VSD misalignment tolerances, x diameter
 CORRECT_THS = tuple(round(0.05 * i, 2) for i in range(1, 11))    # thresholds of correctness: x diameter (MSSD), on e (VSD)
 MSPD_THS = tuple(float(5 * i) for i in range(1, 11))             # px at W = 640
-_eval = _lib.SideLibrary("libgigapose_eval.so", "gpe", {"gpe_pose_workspace_bytes": ctypes.c_size_t})
+_eval = _lib.SideLibrary("libgigapose_eval.so", "gpe")
 EVAL_LIB_PATH, lib, _call = _eval.path, _eval.lib, _eval.call
 
 
@@ -83,23 +83,6 @@ def symmetry_transforms(model_info, max_sym_disc_step=0.01):
 
 
 # ------------------------------------------------------------------------------------------------ the two entry points
-def _arg(t, dtype, shape, who, what):
-    """Type, dtype, shape and layout of one argument (ValueError); _on_gpu checks the devices once every argument has passed."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{who}: {what} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{who}: {what} is not contiguous")
-    return t
-
-
-def _on_gpu(who, **tensors):
-    for what, t in tensors.items():
-        if not t.is_cuda:
-            raise _lib.GigaPoseHipError(f"{who} needs {what} on the GPU (no CPU fallback)")
-
-
 def pose_workspace_bytes(N, S):
     return int(lib().gpe_pose_workspace_bytes(_lib.i(N), _lib.i(S)))
 
@@ -109,12 +92,12 @@ def mssd_mspd(vertices, syms, est, gt, K, zmin=0.0, workspace=None):
     """gpe_mssd_mspd: vertices f32 (V,3), syms f64 (S,4,4), est, gt f64 (N,4,4), K f64 (N,9) on the device -> the SQUARED
     errors mssd2, mspd2 f64 (N,) on the device.  N <= 65535.  `workspace`: int64, at least pose_workspace_bytes(N, S) bytes."""
     who = "mssd_mspd"
-    vertices = _arg(vertices, torch.float32, (None, 3), who, "vertices")
-    syms = _arg(syms, torch.float64, (None, 4, 4), who, "syms")
-    est = _arg(est, torch.float64, (None, 4, 4), who, "est")
+    vertices = _lib.arg(vertices, torch.float32, (None, 3), who, "vertices")
+    syms = _lib.arg(syms, torch.float64, (None, 4, 4), who, "syms")
+    est = _lib.arg(est, torch.float64, (None, 4, 4), who, "est")
     N, V, S = est.shape[0], vertices.shape[0], syms.shape[0]
-    gt = _arg(gt, torch.float64, (N, 4, 4), who, "gt")
-    K = _arg(K, torch.float64, (N, 9), who, "K")
+    gt = _lib.arg(gt, torch.float64, (N, 4, 4), who, "gt")
+    K = _lib.arg(K, torch.float64, (N, 9), who, "K")
     if V < 1 or S < 1:
         raise ValueError(f"{who}: needs at least one vertex and one symmetry transform (the identity), got V = {V}, S = {S}")
     if N > MAX_PAIRS_PER_CALL:
@@ -123,12 +106,12 @@ def mssd_mspd(vertices, syms, est, gt, K, zmin=0.0, workspace=None):
         raise ValueError(f"{who}: zmin must be finite")
     need = N * S * 14 * 8
     if workspace is None:
-        _on_gpu(who, est=est)
+        _lib.on_gpu(who, est=est)
         workspace = torch.empty(max(1, need // 8), dtype=torch.int64, device=est.device)
-    workspace = _arg(workspace, torch.int64, (None,), who, "workspace")
+    workspace = _lib.arg(workspace, torch.int64, (None,), who, "workspace")
     if workspace.numel() * 8 < need:
         raise ValueError(f"{who}: the workspace is too small ({workspace.numel() * 8} < {need} bytes)")
-    _on_gpu(who, vertices=vertices, syms=syms, est=est, gt=gt, K=K, workspace=workspace)
+    _lib.on_gpu(who, vertices=vertices, syms=syms, est=est, gt=gt, K=K, workspace=workspace)
     mssd2 = torch.empty(N, dtype=torch.float64, device=est.device)
     mspd2 = torch.empty(N, dtype=torch.float64, device=est.device)
     _call("gpe_mssd_mspd", _lib.ptr(vertices), _lib.i(V), _lib.ptr(syms), _lib.i(S), _lib.ptr(est), _lib.ptr(gt), _lib.ptr(K), _lib.i(N),
@@ -156,12 +139,12 @@ def vsd_counts(depth_est, depth_gt, depth_test, frame, ray, ray_index, delta, th
     frame, ray_index (N,) integers on the host or the device (checked against M, R on the host) -> counts int64 (N, 2+T) on the
     device: union, intersection, bad[t].  N <= 65535, T <= 16."""
     who = "vsd_counts"
-    depth_est = _arg(depth_est, torch.float32, (None, None, None), who, "depth_est")
+    depth_est = _lib.arg(depth_est, torch.float32, (None, None, None), who, "depth_est")
     N, H, W = depth_est.shape
-    depth_gt = _arg(depth_gt, torch.float32, (N, H, W), who, "depth_gt")
-    depth_test = _arg(depth_test, torch.float32, (None, H, W), who, "depth_test")
-    ray = _arg(ray, torch.float64, (None, H, W), who, "ray")
-    thr = _arg(thr, torch.float64, (N, None), who, "thr")
+    depth_gt = _lib.arg(depth_gt, torch.float32, (N, H, W), who, "depth_gt")
+    depth_test = _lib.arg(depth_test, torch.float32, (None, H, W), who, "depth_test")
+    ray = _lib.arg(ray, torch.float64, (None, H, W), who, "ray")
+    thr = _lib.arg(thr, torch.float64, (N, None), who, "thr")
     M, R, T = depth_test.shape[0], ray.shape[0], thr.shape[1]
     if not 1 <= T <= MAX_THRESHOLDS:
         raise ValueError(f"{who}: T = {T} thresholds (1 to {MAX_THRESHOLDS})")
@@ -172,7 +155,7 @@ def vsd_counts(depth_est, depth_gt, depth_test, frame, ray, ray_index, delta, th
     if math.isnan(delta):
         raise ValueError(f"{who}: delta is NaN")
     frame, ray_index = _host_index(frame, N, M, who, "frame"), _host_index(ray_index, N, R, who, "ray_index")
-    _on_gpu(who, depth_est=depth_est, depth_gt=depth_gt, depth_test=depth_test, ray=ray, thr=thr)
+    _lib.on_gpu(who, depth_est=depth_est, depth_gt=depth_gt, depth_test=depth_test, ray=ray, thr=thr)
     dev = depth_est.device
     frame, ray_index = torch.from_numpy(frame).to(dev), torch.from_numpy(ray_index).to(dev)
     counts = torch.empty(N, 2 + T, dtype=torch.int64, device=dev)
@@ -183,22 +166,6 @@ def vsd_counts(depth_est, depth_gt, depth_test, frame, ray, ray_index, delta, th
 
 
 # ------------------------------------------------------------------------------------------------ errors of any number of pairs
-def _checked(a, dtype, shape, who, what):
-    """A numpy array or a tensor anywhere -> a tensor whose shape and kind of dtype are checked; _upload moves it."""
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {tuple('*' if s is None else s for s in shape)}, got {tuple(t.shape)}")
-    if t.dtype.is_floating_point != dtype.is_floating_point:
-        raise ValueError(f"{who}: {what} has dtype {t.dtype}, expected {dtype}")
-    return t, dtype
-
-
-def _upload(who, device, *checked):
-    if torch.device(device).type != "cuda":
-        raise _lib.GigaPoseHipError(f"{who} needs a GPU device (no CPU fallback)")
-    return [t.to(device=device, dtype=dtype).contiguous() for t, dtype in checked]
-
-
 def _cameras(K, N, who):
     K = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)
     K = np.asarray(K, np.float64)
@@ -215,17 +182,17 @@ def pose_errors(vertices, syms, est, gt, K, zmin=0.0, device="cuda"):
     or tensors anywhere -> mssd, mspd: torch float64 (N,) on the HOST (+inf for a pair with a non-finite value, mspd also with a
     vertex whose depth is below zmin on either side).  The kernels return the squares; the roots are numpy's, on the host."""
     who = "pose_errors"
-    vertices = _checked(vertices, torch.float32, (None, 3), who, "vertices")
-    syms = _checked(syms, torch.float64, (None, 4, 4), who, "syms")
-    est = _checked(est, torch.float64, (None, 4, 4), who, "est")
+    vertices = _lib.checked(vertices, torch.float32, (None, 3), who, "vertices")
+    syms = _lib.checked(syms, torch.float64, (None, 4, 4), who, "syms")
+    est = _lib.checked(est, torch.float64, (None, 4, 4), who, "est")
     N, S = est[0].shape[0], syms[0].shape[0]
-    gt = _checked(gt, torch.float64, (N, 4, 4), who, "gt")
+    gt = _lib.checked(gt, torch.float64, (N, 4, 4), who, "gt")
     Kh = _cameras(K, N, who)
     if vertices[0].shape[0] < 1 or S < 1:
         raise ValueError(f"{who}: needs at least one vertex and one symmetry transform (the identity)")
     if not math.isfinite(zmin):
         raise ValueError(f"{who}: zmin must be finite")
-    vertices, syms, est, gt = _upload(who, device, vertices, syms, est, gt)
+    vertices, syms, est, gt = _lib.upload(who, device, vertices, syms, est, gt)
     Kd = torch.from_numpy(Kh).to(device)
     step = max(1, min(MAX_PAIRS_PER_CALL, WORKSPACE_BYTES_PER_CALL // (S * 14 * 8)))
     work = torch.empty(max(1, min(N, step) * S * 14), dtype=torch.int64, device=device)
@@ -262,13 +229,13 @@ def vsd_errors(mesh, est, gt, K, depth_test, frame, diameter, delta=15.0, taus=T
       "clipped" (N,) torch bool: the ESTIMATE dropped a triangle (a vertex behind znear, off beyond 16384 px or not finite) -- its
                 errors are 1.0 for every tau.  A clipped GROUND TRUTH raises ValueError."""
     who = "vsd_errors"
-    vertices = _checked(mesh[0], torch.float32, (None, 3), who, "vertices")
-    faces = _checked(mesh[1], torch.int32, (None, 3), who, "faces")
-    est64 = _checked(est, torch.float64, (None, 4, 4), who, "est")
+    vertices = _lib.checked(mesh[0], torch.float32, (None, 3), who, "vertices")
+    faces = _lib.checked(mesh[1], torch.int32, (None, 3), who, "faces")
+    est64 = _lib.checked(est, torch.float64, (None, 4, 4), who, "est")
     N = est64[0].shape[0]
-    gt64 = _checked(gt, torch.float64, (N, 4, 4), who, "gt")
+    gt64 = _lib.checked(gt, torch.float64, (N, 4, 4), who, "gt")
     Kh = _cameras(K, N, who)
-    depth_test = _checked(depth_test, torch.float32, (None, H, W), who, "depth_test")
+    depth_test = _lib.checked(depth_test, torch.float32, (None, H, W), who, "depth_test")
     frame = _host_index(frame, N, depth_test[0].shape[0], who, "frame")
     taus = np.asarray(taus, np.float64).reshape(-1)
     T = len(taus)
@@ -278,7 +245,7 @@ def vsd_errors(mesh, est, gt, K, depth_test, frame, diameter, delta=15.0, taus=T
     if diameter.shape not in ((), (N,)):
         raise ValueError(f"{who}: diameter must be a number or ({N},), got {diameter.shape}")
     diameter = np.broadcast_to(diameter, (N,))
-    vertices, faces, est64, gt64, depth_test = _upload(who, device, vertices, faces, est64, gt64, depth_test)
+    vertices, faces, est64, gt64, depth_test = _lib.upload(who, device, vertices, faces, est64, gt64, depth_test)
     thr = torch.from_numpy(np.ascontiguousarray(taus[None, :] * diameter[:, None])).to(device)
     est32, gt32 = est64.to(torch.float32), gt64.to(torch.float32)
     counts = torch.zeros(N, 2 + T, dtype=torch.int64, device=device)
@@ -340,7 +307,7 @@ def read_estimates(path):
     return out
 
 
-def _pose(R, t):
+def pose_matrix(R, t):
     P = np.eye(4)
     P[:3, :3], P[:3, 3] = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
     return P
@@ -416,8 +383,8 @@ class PoseScorer:
                 where.append((gi, len(est), len(kept), len(g)))
                 for e in kept:
                     for h in g:
-                        est.append(_pose(e["R"], e["t"]))
-                        gt.append(_pose(h["cam_R_m2c"], h["cam_t_m2c"]))
+                        est.append(pose_matrix(e["R"], e["t"]))
+                        gt.append(pose_matrix(h["cam_R_m2c"], h["cam_t_m2c"]))
                         K.append(self.K[key])
                         frame.append(self._frame_index[key])
             T = len(self.taus)

@@ -9,7 +9,6 @@ src/models/network/resnet.py:26-50, 318-381; Hydra targets in configs/model/ist_
   (gp_ist_regress) for every (detection, hypothesis, patch) row at once.
 """
 import ctypes
-import os
 
 import torch
 from torch import nn
@@ -156,9 +155,7 @@ class ResNet(nn.Module):
     def _conv_planes(self, cv, w, x, y, B, H, W, residual=None, relu=True, out_f32=None):
         """x, y, residual: (hi, lo) f16 plane pairs, channel-last, x 8 (gp_conv2d_planes)."""
         dev = x[0].device
-        lib = _lib.lib()
-        lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
-        need = lib.gp_conv2d_planes_workspace_bytes()
+        need = _lib.lib().gp_conv2d_planes_workspace_bytes()
         if self._conv_scratch is None or self._conv_scratch.device != dev:
             self._conv_scratch = torch.zeros((need + 3) // 4, dtype=torch.float32, device=dev)
         _lib.call("gp_conv2d_planes", _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(w[0]), _lib.ptr(w[1]),
@@ -271,9 +268,7 @@ class ResNet(nn.Module):
                                 torch.zeros(B, S + 6, S + 8, 4, dtype=torch.float16, device=dev))   # the frame stays zero
             _lib.call("gp_resize_stem_planes", _lib.ptr(images), _lib.ptr(self._framed[0]), _lib.ptr(self._framed[1]), _lib.i(B),
                       _lib.i(images.shape[2]), _lib.i(images.shape[3]), _lib.i(S), _lib.stream_ptr())
-            lib = _lib.lib()
-            lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
-            need = lib.gp_conv2d_planes_workspace_bytes()
+            need = _lib.lib().gp_conv2d_planes_workspace_bytes()
             if self._conv_scratch is None or self._conv_scratch.device != dev:
                 self._conv_scratch = torch.zeros((need + 3) // 4, dtype=torch.float32, device=dev)
             st, sw = pk["stem"], weights["stem"]
@@ -385,9 +380,7 @@ class ISTNet(nn.Module):
         cos_sin = torch.empty(B, k, P, 2, dtype=torch.float32, device=dev)
         if B == 0:
             return scales, cos_sin
-        lib = _lib.lib()
-        lib.gp_ist_workspace_bytes.restype = ctypes.c_size_t
-        need = lib.gp_ist_workspace_bytes(_lib.i(B), _lib.i(k), _lib.i(D), _lib.i(H))
+        need = _lib.lib().gp_ist_workspace_bytes(_lib.i(B), _lib.i(k), _lib.i(D), _lib.i(H))
         if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != dev:
             # zeroed once: the regressor's GEMMs run over compacted rows and the last 128-column tile is only partly filled --
             # its stale columns (never read back) must at least be finite, whatever the allocator handed out

@@ -31,7 +31,7 @@ from .tensor_collection import PandasTensorCollection
 
 MAX_VIEWS_PER_CALL = 65535                          # the grid's second dimension (gigapose_render.h: Limits)
 VIS_BYTES_PER_CALL = 1 << 30                        # default chunking: the visibility buffer of one call stays below this
-_render = _lib.SideLibrary("libgigapose_render.so", "gpr", {"gpr_raster_workspace_bytes": ctypes.c_size_t})
+_render = _lib.SideLibrary("libgigapose_render.so", "gpr")
 RENDER_LIB_PATH, lib, _call = _render.path, _render.lib, _render.call
 
 
@@ -181,14 +181,6 @@ def load_ply(path):
 
 
 # ------------------------------------------------------------------------------------------------ the renderer
-def _on_device(t, dtype, shape, who, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise _lib.GigaPoseHipError(f"{who} needs {what} on the GPU (no CPU fallback)")
-    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _k9(K):
     k = np.asarray(K, dtype=np.float32).reshape(9)
     if not (k[6] == 0 and k[7] == 0 and k[8] == 1):
@@ -200,8 +192,8 @@ def _k9(K):
 def project(vertices, poses, K, znear, out=None):
     """gpr_project: vertices f32 (V,3), poses f32 (N,4,4) on the device -> xy int32 (N,V,2) in 1/256 pixel, depth f32 (N,V).
     N <= 65535.  `out` = (xy, depth) are buffers to write into (their first N views are used)."""
-    vertices = _on_device(vertices, torch.float32, (None, 3), "project", "vertices")
-    poses = _on_device(poses, torch.float32, (None, 4, 4), "project", "poses")
+    vertices = _lib.on_device(vertices, torch.float32, (None, 3), "project", "vertices")
+    poses = _lib.on_device(poses, torch.float32, (None, 4, 4), "project", "poses")
     V, N = vertices.shape[0], poses.shape[0]
     xy, depth = out if out is not None else (torch.empty(N, V, 2, dtype=torch.int32, device=vertices.device),
                                              torch.empty(N, V, dtype=torch.float32, device=vertices.device))
@@ -215,10 +207,10 @@ def raster(xy, vdepth, faces, H, W, out=None, workspace=None):
     """gpr_raster: xy int32 (N,V,2), vdepth f32 (N,V), faces int32 (F,3) -> vis int64 (N,H,W) holding the unsigned 64-bit keys
     (depth bits << 32 | face; -1 = uncovered), clipped int32 (N,).  `out` = (vis, clipped) and `workspace` (int64, at least
     gpr_raster_workspace_bytes(N, F) bytes) are buffers to use."""
-    xy = _on_device(xy, torch.int32, (None, None, 2), "raster", "xy")
+    xy = _lib.on_device(xy, torch.int32, (None, None, 2), "raster", "xy")
     N, V = xy.shape[:2]
-    vdepth = _on_device(vdepth, torch.float32, (N, V), "raster", "vdepth")
-    faces = _on_device(faces, torch.int32, (None, 3), "raster", "faces")
+    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), "raster", "vdepth")
+    faces = _lib.on_device(faces, torch.int32, (None, 3), "raster", "faces")
     F, dev = faces.shape[0], xy.device
     vis, clipped = out if out is not None else (torch.empty(N, H, W, dtype=torch.int64, device=dev),
                                                 torch.empty(N, dtype=torch.int32, device=dev))
@@ -235,13 +227,13 @@ def raster(xy, vdepth, faces, H, W, out=None, workspace=None):
 @torch.no_grad()
 def resolve(vis, xy, vdepth, faces, colours, out=None):
     """gpr_resolve: the keys -> rgba u8 (N,H,W,4), depth f32 (N,H,W); `out` = (rgba, depth) are buffers to write into."""
-    vis = _on_device(vis, torch.int64, (None, None, None), "resolve", "vis")
+    vis = _lib.on_device(vis, torch.int64, (None, None, None), "resolve", "vis")
     N, H, W = vis.shape
-    xy = _on_device(xy, torch.int32, (N, None, 2), "resolve", "xy")
+    xy = _lib.on_device(xy, torch.int32, (N, None, 2), "resolve", "xy")
     V = xy.shape[1]
-    vdepth = _on_device(vdepth, torch.float32, (N, V), "resolve", "vdepth")
-    faces = _on_device(faces, torch.int32, (None, 3), "resolve", "faces")
-    colours = _on_device(colours, torch.uint8, (V, 3), "resolve", "colours")
+    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), "resolve", "vdepth")
+    faces = _lib.on_device(faces, torch.int32, (None, 3), "resolve", "faces")
+    colours = _lib.on_device(colours, torch.uint8, (V, 3), "resolve", "colours")
     rgba, depth = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=vis.device),
                                                torch.empty(N, H, W, dtype=torch.float32, device=vis.device))
     if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W):
@@ -281,16 +273,16 @@ class MeshRenderer:
         who = "MeshRenderer"
         if on_clipped not in ("raise", "ignore"):
             raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
-        vertices = _on_device(vertices, torch.float32, (None, 3), who, "vertices")
-        faces = _on_device(faces, torch.int32, (None, 3), who, "faces")
-        poses = _on_device(poses, torch.float32, (None, 4, 4), who, "poses")
+        vertices = _lib.on_device(vertices, torch.float32, (None, 3), who, "vertices")
+        faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
+        poses = _lib.on_device(poses, torch.float32, (None, 4, 4), who, "poses")
         V, F, N = vertices.shape[0], faces.shape[0], poses.shape[0]
         dev = vertices.device
         if colours is None:
             if colour is None:
                 raise ValueError(f"{who}: the mesh has no vertex colours and textures are out of scope: pass colour=(r, g, b)")
             colours = torch.tensor([colour], dtype=torch.uint8, device=dev).expand(V, 3)
-        colours = _on_device(colours, torch.uint8, (V, 3), who, "colours")
+        colours = _lib.on_device(colours, torch.uint8, (V, 3), who, "colours")
         H, W = self.H, self.W
         if views_per_call is None:
             views_per_call = max(1, VIS_BYTES_PER_CALL // (H * W * 8))

@@ -17,7 +17,6 @@ Vertex colours are IGNORED when a texture is given (BOP's textured models carry 
 several textures per model (a `texnumber` other than 0 is an error), vertex colour x texture modulation, OBJ / MTL files, and as in
 render.py near-plane clipping, shading other than ambient and anti-aliasing.  There is no CPU fallback.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -26,12 +25,11 @@ import torch
 
 from . import _lib, render
 from .onboard import TEMPLATE_K, TemplateOnboarder
-from .render import _on_device
 from .tensor_collection import PandasTensorCollection
 
 MAX_TEXTURE = 16384                                 # gigapose_texture.h: GPT_MAX_TEXTURE
 MAX_UV = 32768.0                                    # gigapose_texture.h: GPT_MAX_UV
-_texture = _lib.SideLibrary("libgigapose_texture.so", "gpt", {"gpt_mip_texels": ctypes.c_size_t})
+_texture = _lib.SideLibrary("libgigapose_texture.so", "gpt")
 TEXTURE_LIB_PATH, lib, _call = _texture.path, _texture.lib, _texture.call
 
 
@@ -121,7 +119,7 @@ def _check_texture_shape(shape, who):
 def build_mips(rgb):
     """gpt_build_mips: rgb u8 (Ht,Wt,3) on the device -> the pyramid, int32 (gpt_mip_texels(Ht, Wt),), holding the 32-bit texels
     R | G << 8 | B << 16 | 0xff << 24 of every level, level 0 first."""
-    rgb = _on_device(rgb, torch.uint8, (None, None, 3), "build_mips", "texture")
+    rgb = _lib.on_device(rgb, torch.uint8, (None, None, 3), "build_mips", "texture")
     _check_texture_shape(rgb.shape, "build_mips")
     Ht, Wt = rgb.shape[:2]
     pyramid = torch.empty(mip_texels(Ht, Wt), dtype=torch.int32, device=rgb.device)
@@ -134,17 +132,17 @@ def resolve_textured(vis, xy, vdepth, faces, corner_uv, pyramid, size, out=None)
     """gpt_resolve: the keys of render.raster + corner_uv f32 (F,3,2) + the pyramid of a size = (Ht, Wt) texture -> rgba u8
     (N,H,W,4), depth f32 (N,H,W); `out` = (rgba, depth) are buffers to write into."""
     who = "resolve_textured"
-    vis = _on_device(vis, torch.int64, (None, None, None), who, "vis")
+    vis = _lib.on_device(vis, torch.int64, (None, None, None), who, "vis")
     N, H, W = vis.shape
-    xy = _on_device(xy, torch.int32, (N, None, 2), who, "xy")
+    xy = _lib.on_device(xy, torch.int32, (N, None, 2), who, "xy")
     V = xy.shape[1]
-    vdepth = _on_device(vdepth, torch.float32, (N, V), who, "vdepth")
-    faces = _on_device(faces, torch.int32, (None, 3), who, "faces")
+    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), who, "vdepth")
+    faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
     F = faces.shape[0]
-    corner_uv = _on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
+    corner_uv = _lib.on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
     Ht, Wt = int(size[0]), int(size[1])
     _check_texture_shape((Ht, Wt, 3), who)
-    pyramid = _on_device(pyramid, torch.int32, (mip_texels(Ht, Wt),), who, "pyramid")
+    pyramid = _lib.on_device(pyramid, torch.int32, (mip_texels(Ht, Wt),), who, "pyramid")
     rgba, depth = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=vis.device),
                                                torch.empty(N, H, W, dtype=torch.float32, device=vis.device))
     if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W):
@@ -171,20 +169,20 @@ class TexturedMeshRenderer:
         who = "TexturedMeshRenderer"
         if on_clipped not in ("raise", "ignore"):
             raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
-        vertices = _on_device(vertices, torch.float32, (None, 3), who, "vertices")
-        faces = _on_device(faces, torch.int32, (None, 3), who, "faces")
+        vertices = _lib.on_device(vertices, torch.float32, (None, 3), who, "vertices")
+        faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
         V, F = vertices.shape[0], faces.shape[0]
-        corner_uv = _on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
+        corner_uv = _lib.on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
         if isinstance(texture, (tuple, list)):
             pyramid, size = texture
             size = (int(size[0]), int(size[1]))
             _check_texture_shape(size + (3,), who)
-            pyramid = _on_device(pyramid, torch.int32, (mip_texels(*size),), who, "pyramid")
+            pyramid = _lib.on_device(pyramid, torch.int32, (mip_texels(*size),), who, "pyramid")
         else:
-            texture = _on_device(texture, torch.uint8, (None, None, 3), who, "texture")
+            texture = _lib.on_device(texture, torch.uint8, (None, None, 3), who, "texture")
             _check_texture_shape(texture.shape, who)
             pyramid, size = None, tuple(texture.shape[:2])
-        poses = _on_device(poses, torch.float32, (None, 4, 4), who, "poses")
+        poses = _lib.on_device(poses, torch.float32, (None, 4, 4), who, "poses")
         N, dev = poses.shape[0], vertices.device
         if pyramid is None:
             pyramid = build_mips(texture)

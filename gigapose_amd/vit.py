@@ -9,7 +9,6 @@ used as CPU oracle.  All arithmetic is in the HIP library; this class owns weigh
 """
 import ctypes
 import math
-import os
 
 import torch
 from torch import nn
@@ -244,9 +243,7 @@ class Dinov2ViT(nn.Module):
         self._packed = (device, tensors, table, split, split_table)
 
     def _workspace(self, B, device):
-        lib = _lib.lib()
-        lib.gp_vit_workspace_bytes.restype = ctypes.c_size_t
-        need = lib.gp_vit_workspace_bytes(_lib.i(B), _lib.i(self.dim), _lib.i(self.mlp_dim))
+        need = _lib.lib().gp_vit_workspace_bytes(_lib.i(B), _lib.i(self.dim), _lib.i(self.mlp_dim))
         if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != device:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
         return self._ws, need

@@ -11,7 +11,7 @@
  *     asserts at the same places, cited per function);
  *   - tensors are dense, row-major in the order written, f32 unless stated otherwise;
  *   - P = 256 patches (16x16 grid of 14-px patches on a 224x224 crop).
- * This header is the PRODUCT interface: what gigapose_amd/*.py, bench.py and a host integration call.  A/B switches, time-stamped probe
+ * This header is the PRODUCT interface: what gigapose_amd's modules, bench.py and a host integration call.  A/B switches, time-stamped probe
  * builds, test-only epilogues and error-word readers live in gigapose_hip_probe.h and exist only in libgigapose_hip_probe.so (the same
  * sources compiled with -DGP_PROBES; tests and tools/ load it where they need a hook).
  */

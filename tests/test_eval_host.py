@@ -84,7 +84,6 @@ def test_eval_argument_validation_of_the_library_needs_no_gpu():
     assert vsd(counts=ctypes.c_void_p(12)) == -1 and b"aligned" in err()
     assert vsd(est=null, gt=null, test=null, frame=null, ray=null, ri=null, thr=null, counts=null, N=0) == 0
 
-    lib.gpe_pose_workspace_bytes.restype = ctypes.c_size_t
     assert lib.gpe_pose_workspace_bytes(1500, 630) == 1500 * 630 * 14 * 8
     assert lib.gpe_pose_workspace_bytes(65535, 2 ** 31 - 1) == 65535 * (2 ** 31 - 1) * 14 * 8              # size_t arithmetic
     assert lib.gpe_pose_workspace_bytes(-1, 5) == 0 and lib.gpe_pose_workspace_bytes(5, -1) == 0

@@ -43,7 +43,6 @@ def clean_status():
 @functools.lru_cache(maxsize=None)  # per library, zeroed once, as ResNet._conv_planes keeps it: hand-overs are tagged with a per-launch epoch
 def _scratch(binary):
     lib = _lib.lib()
-    lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_conv2d_planes_workspace_bytes()
     return torch.zeros((nb + 3) // 4, dtype=torch.float32, device=DEV), nb
 

@@ -120,7 +120,6 @@ def test_layernorm_planes_branch_vs_float64(tag, C, Mpad, slices, contiguous):
 
 
 def set_ln_reg(mode):
-    _lib.lib().gp_vit_set_ln_reg.restype = None
     _lib.lib().gp_vit_set_ln_reg(ctypes.c_int(mode))
 
 

@@ -47,7 +47,6 @@ def ln_planes_live(x_tm, gamma, beta, live):
     lo = torch.full_like(hi, float("nan"))
     g, b = gamma.to(DEV), beta.to(DEV)
     lib = _lib.lib()
-    lib.gp_vit_set_ln_live.restype = None
     try:
         lib.gp_vit_set_ln_live(ctypes.c_int(live))
         _lib.call("gp_layernorm_planes", _lib.ptr(X), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(g), _lib.ptr(b), _lib.i(C), _lib.i(Mpad), _lib.f(EPS),

@@ -45,7 +45,6 @@ def split_planes(x, scale):
 
 def scaled_gemm(A, Bm, epi, bias, b_scale, out_scale_planes, j_valid=None, amax=None):
     lib = _lib.lib()
-    lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_gemm_split256_workspace_bytes()
     ws = torch.zeros(nb // 4, device=DEV)
     (ahi, alo), (bhi, blo) = split_planes(A, 64.0), split_planes(Bm, b_scale)

@@ -363,7 +363,6 @@ def run_conv_planes(X, Wt, alpha, beta, R, stride, pad):
     of32 = torch.zeros(B, cout, oh, oh, device=DEV)
     ta, tb = torch.from_numpy(alpha).to(DEV), torch.from_numpy(beta).to(DEV)
     lib = _lib.lib()
-    lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_conv2d_planes_workspace_bytes()
     ws = torch.zeros(nb // 4, device=DEV)
     _lib.status_word(DEV).zero_()
@@ -397,7 +396,6 @@ def test_conv_halo_kernel_matches_the_gather_kernel():
     shape the halo kernel does not take (3 x 3 / stride 1 on 56 x 56 among them)."""
     rs = np.random.RandomState(77)
     lib = _lib.lib()
-    lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_conv2d_planes_workspace_bytes()
     ws = torch.zeros(nb // 4, device=DEV)
     for (cin, cout, hw, B) in [(128, 128, 64, 4), (192, 192, 32, 8), (512, 512, 16, 16)]:
@@ -454,7 +452,6 @@ def split256_gemm(act, W, act_is_b, epi=None, bias=None, scale=None, res=None):
     from gigapose_amd.vit import split_planes_x64
 
     lib = _lib.lib()
-    lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_gemm_split256_workspace_bytes()
     K = act.shape[0]
     I, J = (W.shape[0], act.shape[1]) if act_is_b else (act.shape[1], W.shape[0])
@@ -627,7 +624,6 @@ def planes256_gemm(A, Bm, epi, bias=None, scale=None, res=None, a_scale=64.0, b_
     The status word is cleared before the launch and read (and cleared) after it: a lost stream-K hand-over or a value beyond the
     planes' range raises in either build; the probe build's error-word reader is asserted as well."""
     lib = _lib.lib()
-    lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_gemm_split256_workspace_bytes()
     ws = torch.zeros(nb // 4, device=DEV)
 

@@ -111,7 +111,6 @@ def stem_module(cout, seed):
 
 def scratch():
     lib = _lib.lib()
-    lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
     nb = lib.gp_conv2d_planes_workspace_bytes()
     return torch.zeros((nb + 3) // 4, dtype=torch.float32, device=DEV), nb
 

@@ -52,7 +52,6 @@ def hip_gemm_sk(A, B, epi, bias, scale, res):
     from gigapose_amd import _lib
 
     lib = _lib.lib()
-    lib.gp_gemm_streamk_workspace_bytes.restype = ctypes.c_size_t
     nbytes = lib.gp_gemm_streamk_workspace_bytes()
     K, I = A.shape
     J = B.shape[1]

@@ -87,7 +87,6 @@ def test_render_argument_validation_needs_no_gpu():
     assert b"aligned" in err()
     assert lib.gpr_resolve(null, null, null, 5, null, 3, null, 0, 48, 64, null, null, null) == 0
 
-    lib.gpr_raster_workspace_bytes.restype = ctypes.c_size_t
     assert lib.gpr_raster_workspace_bytes(162, 20480) >= 162 * 20480 * 8
     assert lib.gpr_raster_workspace_bytes(65535, 2 ** 31 - 1) >= 65535 * (2 ** 31 - 1) * 8          # size_t arithmetic
     assert lib.gpr_raster_workspace_bytes(-1, 5) == 0

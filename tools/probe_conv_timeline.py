@@ -17,7 +17,6 @@ dev = "cuda"
 if os.environ.get("GP_LIB"):   # a library built with other macros (tools/patches/conv_epi_probe.diff, -DGP_CONV_PROBE=..)
     _lib.LIB_PATH = os.path.abspath(os.environ["GP_LIB"])
 lib = _lib.lib()
-lib.gp_conv2d_planes_workspace_bytes.restype = ctypes.c_size_t
 nb = lib.gp_conv2d_planes_workspace_bytes()
 ws = torch.zeros(nb // 4, device=dev)
 trace = torch.zeros(256, 8, dtype=torch.int64, device=dev)

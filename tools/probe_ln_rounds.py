@@ -10,7 +10,6 @@ from gigapose_amd import _lib
 
 _lib.use_probe_library()
 lib = _lib.lib()
-lib.gp_vit_set_ln_live.restype = None
 dev = torch.device("cuda", 0)
 C = 1024
 g = torch.randn(C, device=dev)

@@ -52,9 +52,7 @@ class HybridViT:
 
     def __init__(self, vit):
         self.vit = vit
-        lib = _lib.lib()
-        lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
-        self.nb = lib.gp_gemm_split256_workspace_bytes()
+        self.nb = _lib.lib().gp_gemm_split256_workspace_bytes()
         self.ws = torch.zeros(self.nb // 4, device=DEV)
         f32 = lambda t: t.detach().float().to(DEV).contiguous()
         self.layers = []

@@ -7,7 +7,6 @@ from gigapose_amd import _lib
 _lib.use_probe_library()   # hooks / traced builds / error words live in libgigapose_hip_probe.so (include/gigapose_hip_probe.h)
 dev = "cuda"
 lib = _lib.lib()
-lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
 NB = lib.gp_gemm_split256_workspace_bytes()
 ws = torch.zeros(NB // 4, device=dev)
 def timeit(fn, iters=8, warm=3):

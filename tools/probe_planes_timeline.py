@@ -11,7 +11,6 @@ dev = "cuda"
 if os.environ.get("GP_LIB"):   # a library built with other macros (e.g. -DGP_EPI_PROBE=.., tools/patches/epi_probe.diff)
     _lib.LIB_PATH = os.path.abspath(os.environ["GP_LIB"])
 lib = _lib.lib()
-lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
 NB = lib.gp_gemm_split256_workspace_bytes()
 ws = torch.zeros(NB // 4, device=dev)
 def planes(W, scale):

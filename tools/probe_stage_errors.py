@@ -56,9 +56,7 @@ def main():
     torch.cuda.synchronize()
     X = vit._ws[: C * Mpad].view(C, Mpad).clone()                 # residual stream after L blocks, channel-major [C][Mpad]
     blk = vit.blocks[L]
-    lib = _lib.lib()
-    lib.gp_gemm_split256_workspace_bytes.restype = ctypes.c_size_t
-    nb = lib.gp_gemm_split256_workspace_bytes()
+    nb = _lib.lib().gp_gemm_split256_workspace_bytes()
     ws = torch.zeros(nb // 4, device=DEV)
     st = _lib.stream_ptr
     os_ = 1.0 / (8.0 * 64.0)

@@ -19,7 +19,6 @@ def timeit(fn, iters=5, warm=2):
 
 import ctypes
 lib = _lib.lib()
-lib.gp_gemm_streamk_workspace_bytes.restype = ctypes.c_size_t
 nbytes = lib.gp_gemm_streamk_workspace_bytes()
 ws = torch.zeros(nbytes // 4, device=dev)
 for mode in []:
