@@ -14,7 +14,7 @@ motion that solves them (unpivoted LDL^T, Cayley transform: no root, no transcen
   DepthRefiner(models, cameras, ...)            .refine(estimates) -> a copy with R, t replaced + status, inliers, covered, rms
   write_estimates(path, estimates)              the csv evaluate.read_estimates reads: csv -> refine -> csv -> PoseScorer.score_csv
 Out of scope: nearest-neighbour association (a point is compared with the measurement on its own ray), robust kernels beyond
-the gate, re-scoring hypotheses (scores are left as they are), the MegaPose network, colour.  There is no CPU fallback: a
+the gate, the MegaPose network, colour; scores are left as they are (choosing among hypotheses: gigapose_amd/verify.py).  There is no CPU fallback: a
 missing library is an error.
 """
 import ctypes
