@@ -211,6 +211,10 @@ STATUS_BITS = {1: "a stream-K accumulator hand-over of the split GEMM timed out 
                16: "split numerics: an IST activation left the range of the f16 planes (|x| >= 8190; on ResNet.conv_kernel = '128': |x| > 65504) "
                    "or is not finite -- use ResNet.conv_kernel = '128' for this checkpoint (GigaPose falls back by itself), beyond that numerics 'chain'"}
 SPLIT_RANGE_BITS = 4 | 16
+# Not a device fault, hence outside STATUS_BITS (raise_status never reports it) and outside SPLIT_RANGE_BITS: under a sharded bank the
+# pose recovery's crop-transform flag (reference lib3d/torch.py:54-55) travels in the all-gathered copy of the status word, in this bit,
+# so that every rank raises the reference's AssertionError in the same flush (GigaPose._run_rows, sharded_flow.py).  No kernel sets it.
+CROP_TRANSFORM_BIT = 1 << 30
 _status = {}          # device index -> the int32 word on that device
 _registered = set()   # device indices whose word the ACTIVE library has in its per-device table
 
@@ -249,6 +253,7 @@ def take_status():
 
 
 def raise_status(bits):
+    bits &= ~CROP_TRANSFORM_BIT   # the caller's AssertionError, not a device fault
     if bits:
         msgs = [m for b, m in STATUS_BITS.items() if bits & b]
         raise GigaPoseHipError("device status 0x%x: %s" % (bits, "; ".join(msgs)))

@@ -573,6 +573,10 @@ class GigaPose(_Base):
             # decision in the same place; and all ranks' exchange words (they arrived with exchange #1)
             from .sharding import all_gather_rows
 
+            if flag is not None:
+                # the crop-transform flag (0 / 1, gp_recover_poses) rides in the gathered word: a rank-local assert would leave the
+                # peers in their next collective.  On the device, in stream order; the word is cleared below like every other bit
+                word.bitwise_or_(flag * _lib.CROP_TRANSFORM_BIT)
             words, _ = all_gather_rows(word.view(1, 1), self.template_shard[2])
             host["status"] = torch.zeros(words.shape[0], dtype=torch.int32, pin_memory=True)
             host["status"].copy_(words.reshape(-1), non_blocking=True)
@@ -663,10 +667,10 @@ class GigaPose(_Base):
     def flush_pending(self):
         """Run what is queued and write every outstanding file (on_test_epoch_end calls it; a caller that reads the npz files between
         test_steps calls it too).  With a sharded bank this is a COLLECTIVE: every rank of the shard group must call it (the ranks
-        agree inside the flushes on when all queues are empty, sharded_flow.py)."""
+        agree inside the flushes on when all queues are empty, sharded_flow.py); a rank that has no dataset to run its padding
+        flushes on raises instead of leaving its peers waiting."""
         if self.template_shard is not None:
-            if self._sharded_flow is not None or self.test_dataset_name is not None:
-                self._flow().drain()
+            self._flow().drain()
             return
         while self._pending:
             self._launch_flush()

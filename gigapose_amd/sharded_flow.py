@@ -19,6 +19,13 @@ step (gigapose_amd/sharding.py) are fixed-size collectives, so:
   * the guard-rail word of flush j is all-gathered at the end of flush j (one 4-byte-per-rank collective) so that every rank
     takes the range-recovery decision (re-calibration = an all-reduce; re-onboarding) in the same F(j): then all ranks drop
     the results of j and j + 1, recover together, put both flushes' crops back at the front of their queues and carry on.
+    Everything that decides whether a rank raises or goes on to its next collective is taken from that shared word or from a
+    count every rank holds identically, never from a rank's own images: giving up (a trip that would start the third recovery
+    in a row -- a clean flush in between resets the count -- raises on every rank), and the reference's crop-transform assert
+    (the pose recovery's flag travels in the word as `_lib.CROP_TRANSFORM_BIT`);
+  * a flush runs under the dataset its crops were queued under.  The queue never holds crops of two datasets: a `push()` after
+    the driver re-pointed the model raises until every rank has called `flush_pending()` (a collective, unlike the flush the
+    unsharded queue does by itself in that case).
 """
 import collections
 import os.path as osp
@@ -34,10 +41,11 @@ DONE = 1   # bit 0 of the exchange word: this rank is draining and has nothing q
 class _Image:
     """One queued image: its batch, and the host rows that have come back so far."""
 
-    def __init__(self, batch, idx_batch, log_dir, test_setting):
+    def __init__(self, batch, idx_batch, dataset_name, log_dir, test_setting):
         self.batch, self.idx_batch, self.n = batch, idx_batch, len(batch.infos)
-        self.log_dir, self.test_setting = log_dir, test_setting      # bound when queued (a driver may re-point the model later)
-        self.got, self.scores, self.poses, self.seconds, self.attempts = 0, None, None, 0.0, 0
+        # bound when queued (a driver may re-point the model later)
+        self.dataset_name, self.log_dir, self.test_setting = dataset_name, log_dir, test_setting
+        self.got, self.scores, self.poses, self.seconds = 0, None, None, 0.0
 
     def reset(self):
         self.got, self.seconds = 0, 0.0
@@ -51,6 +59,8 @@ class ShardedFlow:
         self.in_flight = None
         self.dummies = None
         self.last_all_done = False
+        self.last_dataset = None              # what the last flush ran under: an all-dummy flush has no crop to take it from
+        self.recoveries_in_a_row = 0          # range recoveries since the last clean flush: the same number on every rank
 
     # -------------------------------------------------------------------------------------------------------------- host side
     @property
@@ -59,7 +69,12 @@ class ShardedFlow:
 
     def push(self, batch, idx_batch):
         m = self.model
-        img = _Image(batch, idx_batch, m.log_dir, m.test_setting)
+        held = self._held_dataset()
+        if held is not None and held != m.test_dataset_name:
+            raise ValueError(f"sharded test_step: crops of dataset {held!r} are still queued or in flight and the model now points to "
+                             f"{m.test_dataset_name!r}; call flush_pending() first -- a collective: EVERY rank of the shard group must "
+                             "call it -- then push again (nothing was queued by this call, nothing queued before it is lost)")
+        img = _Image(batch, idx_batch, m.test_dataset_name, m.log_dir, m.test_setting)
         if img.n == 0:                        # an image without detections: its (empty) file, now
             k = m.testing_metric.k
             self._save(img, np.zeros((0, k), np.float32), np.zeros((0, k, 4, 4), np.float32))
@@ -68,6 +83,14 @@ class ShardedFlow:
         self.queued += img.n
         while self.queued >= self.rows:
             self._tick(final=False)
+
+    def _held_dataset(self):
+        """The dataset of the crops this rank still owes a file for (queued, or launched and not finished); None without any."""
+        if self.queue:
+            return self.queue[0][0].dataset_name
+        if self.in_flight is not None and self.in_flight["segs"]:
+            return self.in_flight["segs"][0][0].dataset_name
+        return None
 
     def drain(self):
         """Collective: every rank of the shard group must call it (on_test_epoch_end does).  Returns once every rank's queue is
@@ -88,9 +111,6 @@ class ShardedFlow:
 
     def _launch(self, final):
         m = self.model
-        dataset_name = m.test_dataset_name
-        if dataset_name not in m.template_datas:
-            m.set_template_data(dataset_name)
         F, segs, n = self.rows, [], 0
         while self.queue and n < F:
             img, a, b = self.queue.popleft()
@@ -101,6 +121,14 @@ class ShardedFlow:
             segs.append((img, a, b))
             n += b - a
         self.queued -= n
+        # the dataset the crops were queued under (push keeps the queue to one); an all-dummy flush: the last one launched
+        dataset_name = segs[0][0].dataset_name if segs else (self.last_dataset if self.last_dataset is not None else m.test_dataset_name)
+        if dataset_name is None:
+            raise RuntimeError("sharded flush_pending() / test_step is a collective of the shard group, and this rank has no dataset to run "
+                               "its padding flushes on: set test_dataset_name (as on the ranks that hold images) before calling it")
+        if dataset_name not in m.template_datas:
+            m.set_template_data(dataset_name)
+        self.last_dataset = dataset_name
         flag = DONE if (final and not self.queue) else 0
         inputs, labels = self._inputs(segs, n, F)
         job = m._run_rows(inputs, labels, dataset_name, aux=flag, live_rows=n)
@@ -151,7 +179,8 @@ class ShardedFlow:
             self._recover(job, bits)
             return
         _lib.raise_status(bits)
-        if int(job["host"]["bad_crop_M"][0]) != 0:   # reference lib3d/torch.py:54-55
+        self.recoveries_in_a_row = 0
+        if bits & _lib.CROP_TRANSFORM_BIT:           # reference lib3d/torch.py:54-55; SOME rank's flag, so every rank is here
             m._clear_crop_flag(job["dataset_name"])
             raise AssertionError("tar_M must be an isotropic scale + translation")
         total_s = 1e-3 * job["ev"][0].elapsed_time(job["ev"][1])
@@ -176,8 +205,11 @@ class ShardedFlow:
         """A plane value left f16's range in flush `job` on SOME rank (`bits` is the OR over the ranks, so every rank is here, in
         the same F(j), with flush j + 1 queued behind).  All ranks: wait for j + 1, drop both results, recover together
         (GigaPose._recover_range: plane scales re-calibrated on both flushes' own rows -- two all-reduces on every rank -- or
-        the wide kernels + re-onboarding), put the crops of both flushes back at the front of the queue.  Images whose crops
-        have tripped three times raise (on every rank: the bits are shared)."""
+        the wide kernels + re-onboarding), put the crops of both flushes back at the front of the queue.  The crop-transform
+        flag is left alone here: it is persistent on the device, so the rerun's word carries it and the rerun's F raises.
+        A trip that would start the third recovery in a row raises instead: the count is kept per flow, stepped here and reset
+        by a clean flush in _finish, both decided by the shared bits, so every rank holds the same number and raises in the same
+        F(j).  (Trips with a clean flush between them do not add up, however long an image stays queued.)"""
         m = self.model
         nxt, self.in_flight = self.in_flight, None
         m._drain_device()
@@ -185,16 +217,13 @@ class ShardedFlow:
         images = [j["inputs"]["tar_img"] for j in jobs]
         while len(images) < 2:                # keep the number of calibration collectives equal on all ranks (the last F has no successor)
             images.append(images[0][:0])
-        worst = max([img.attempts for j in jobs for img, _, _ in j["segs"]] + [job.get("attempts", 0)])
-        if worst >= 2 or not m._recover_range(bits, images):
+        if self.recoveries_in_a_row >= 2 or not m._recover_range(bits, images):
             _lib.raise_status(bits)
+        self.recoveries_in_a_row += 1
         back = []
         for j in jobs:
             for img, a, b in j["segs"]:
                 back.append((img, a, b))
-        touched = {id(img): img for img, _, _ in back}
-        for img in touched.values():
-            img.attempts += 1
         # an image cut by an EARLIER flush keeps the rows it already has; only these segments run again
         for seg in reversed(back):
             self.queue.appendleft(seg)

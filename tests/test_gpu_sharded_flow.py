@@ -5,8 +5,11 @@
     test.py:55-60).  Nobody raises; every per-image npz equals, BYTE FOR BYTE in `chain` numerics (except `time`), the file the
     UNSHARDED per-image flow writes for the same image in the same process;
 (b) one rank over RCCL with the collectives forced (GIGAPOSE_FORCE_COLLECTIVES=1): the same flow through the nccl backend's
-    all_gather_into_tensor / all_to_all_single on device buffers, including the status-word all-gather and the done-word exchange.
+    all_gather_into_tensor / all_to_all_single on device buffers, including the status-word all-gather and the done-word exchange;
+(c) two ranks again, ONE crop of rank 0 with a crop transform that is no isotropic scale: the pose recovery's device flag travels in
+    the gathered status word, so both ranks raise the reference's AssertionError in the same flush and clear their flags.
 """
+import json
 import os
 
 import numpy as np
@@ -41,8 +44,7 @@ def _load(log_dir, idx):
         return {k: z[k] for k in z.files}
 
 
-def _run(tmp, sub, numerics, sizes, rank, dev, sharded, rows, n_templates=11):
-    from gigapose_amd import _lib
+def _build(tmp, sub, numerics, rank, dev, sharded, rows, n_templates=11):
     from gigapose_testing import factory
 
     log_dir = os.path.join(tmp, f"{sub}_r{rank}")
@@ -56,6 +58,13 @@ def _run(tmp, sub, numerics, sizes, rank, dev, sharded, rows, n_templates=11):
         model.enable_template_sharding()
     model.template_datasets = {"syn": tset}
     model.set_template_data("syn")
+    return log_dir, tset, model
+
+
+def _run(tmp, sub, numerics, sizes, rank, dev, sharded, rows, n_templates=11):
+    from gigapose_amd import _lib
+
+    log_dir, tset, model = _build(tmp, sub, numerics, rank, dev, sharded, rows, n_templates)
     for i, n in enumerate(sizes):
         if n == 0 and not sharded:
             continue   # (the per-image flow has nothing to compare an empty image with)
@@ -105,6 +114,63 @@ def _worker(rank, world, port, tmp):
 
 def test_sharded_test_step_with_different_detection_counts_per_rank_two_ranks_on_one_gpu(tmp_path):
     spawn.spawn_and_join(_worker, (2, _free_port(), str(tmp_path)), nprocs=2, deadline_s=SPAWN_S)
+
+
+FLAG_SIZES = {0: [3, 4, 2], 1: [4, 4, 4]}   # flushes of 4 rows: rank 0's image 1 is cut 1 + 3, its crop 2 lies in flush 1
+
+
+def _flag_worker(rank, world, port, tmp):
+    """Records how this rank's test_steps / flush_pending ended, its number of _run_rows calls and its device flag afterwards."""
+    import torch.distributed as dist
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    spawn.init_gloo(rank, world, port, COLLECTIVE_S)
+    out, calls = dict(exc=None, msg=None, step=None), [0]
+    try:
+        log_dir, tset, model = _build(tmp, "flag", "chain", rank, dev, sharded=True, rows=4)
+        run_rows = model._run_rows
+
+        def counted(*a, **kw):
+            calls[0] += 1
+            return run_rows(*a, **kw)
+
+        model._run_rows = counted
+        try:
+            for i, n in enumerate(FLAG_SIZES[rank]):
+                out["step"] = i
+                batch = _image(tset, 300 + 10 * rank + i, n, 20 + 10 * rank + i, dev)
+                if (rank, i) == (0, 1):
+                    batch.tar_M[2, 0, 0] *= 1.5    # no longer an isotropic scale (reference lib3d/torch.py:54-55)
+                assert model.test_step(batch, i) == 0
+            out["step"] = "flush_pending"
+            model.flush_pending()
+            out["step"] = "done"
+        except Exception as e:   # recorded: the test compares the ranks
+            out.update(exc=type(e).__name__, msg=str(e))
+        torch.cuda.synchronize()
+        out.update(run_rows=calls[0], flag=int(model.pose_recovery["syn"]._flag.item()), first_file=os.path.exists(os.path.join(log_dir, "predictions", "0.npz")))
+        with open(os.path.join(tmp, f"flag_r{rank}.json"), "w") as f:
+            json.dump(out, f)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_a_crop_transform_flag_on_one_rank_raises_on_both_ranks_in_the_same_flush(tmp_path):
+    """Rank 0: L(0) at its second test_step, L(1) F(0) at its third, L(2) F(1) in flush_pending; rank 1: one launch per test_step.  F(1)
+    sees rank 0's flag in the shared word: rank 0 raises in flush_pending, rank 1 in its third test_step, both after three _run_rows
+    calls; F(0) was clean, so each rank's first image is on disk; both device flags are cleared."""
+    spawn.spawn_and_join(_flag_worker, (2, _free_port(), str(tmp_path)), nprocs=2, deadline_s=SPAWN_S)
+    outs = []
+    for rank in (0, 1):
+        with open(tmp_path / f"flag_r{rank}.json") as f:
+            outs.append(json.load(f))
+        print(f"rank {rank}: {outs[-1]}")
+    for rank, o in enumerate(outs):
+        assert o["exc"] == "AssertionError" and o["msg"] == "tar_M must be an isotropic scale + translation", (rank, o)
+        assert o["flag"] == 0 and o["first_file"], (rank, o)
+    assert outs[0]["run_rows"] == outs[1]["run_rows"] == 3
+    assert outs[0]["step"] == "flush_pending" and outs[1]["step"] == 2
 
 
 @pytest.mark.parametrize("numerics", ["chain", "split"])
