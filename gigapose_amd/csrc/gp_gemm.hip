@@ -282,7 +282,8 @@ int gp_gemm_launch(const float* A, int lda, const float* B, int ldb, float* D, i
             launch<GP_EPI_BIAS_I_GELU>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
         case GP_EPI_BIAS_I_SCALE_RES:
-            GP_REQUIRE(bias && scale && res && ldr >= J, "gp_gemm_kmajor: bias/scale/residual required");
+            GP_REQUIRE(bias && scale && res, "gp_gemm_kmajor: bias/scale/residual required");
+            GP_REQUIRE(ldr >= J, "gp_gemm_kmajor: ldr=%d is below J=%d", ldr, J);
             launch<GP_EPI_BIAS_I_SCALE_RES>(A, lda, B, ldb, D, ldd, I, J, K, bias, scale, res, ldr, sk_ws, st);
             break;
         case GP_EPI_BIAS_J:

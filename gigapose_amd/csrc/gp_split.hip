@@ -504,6 +504,16 @@ int gp_gemm_split_launch_limited(const float* act, int ld_act, const void* whi, 
                    ((uintptr_t)wlo % 16 == 0),
                "gp_gemm_split: null / misaligned operand");
     GP_REQUIRE((long long)I * ldd < (1ll << 31) && (long long)I * (ldr > 0 ? ldr : 1) < (1ll << 31), "gp_gemm_split: output too large");
+    GP_REQUIRE(ld_act >= (act_is_b ? J : I), "gp_gemm_split: ld_act=%d is below the activation extent %d", ld_act, act_is_b ? J : I);
+    GP_REQUIRE(ldd >= J, "gp_gemm_split: ldd=%d is below J=%d", ldd, J);
+    // what the chosen epilogue reads (the 32 bias rows of a lane are f32x4 loads: gemm_split_kernel)
+    const bool bias_i = epilogue == GP_EPI_BIAS_I || epilogue == GP_EPI_BIAS_I_GELU || epilogue == GP_EPI_BIAS_I_SCALE_RES || epilogue == GP_EPI_BIAS_I_RELU;
+    GP_REQUIRE(bias || !(bias_i || epilogue == GP_EPI_BIAS_J), "gp_gemm_split: epilogue %d needs a bias", epilogue);
+    GP_REQUIRE(!bias_i || (uintptr_t)bias % 16 == 0, "gp_gemm_split: bias must be 16-byte aligned for epilogue %d", epilogue);
+    if (epilogue == GP_EPI_BIAS_I_SCALE_RES) {
+        GP_REQUIRE(scale && res, "gp_gemm_split: epilogue 3 needs scale and residual");
+        GP_REQUIRE(ldr >= J, "gp_gemm_split: ldr=%d is below J=%d", ldr, J);
+    }
     SplitArgs a{act, ld_act, (const _Float16*)whi, (const _Float16*)wlo, D, ldd, K, bias, scale, res, ldr, I / SBM, J / SBN, 8, j_limit};
     // algorithmic flops (the kernel executes 3x as f16 MFMAs).  Column-limited launches (the IST regressor's compacted rows) compute
     // an unknown fraction of their J columns (the count lives on the device): they are timed as "other", with no work figure, so

@@ -923,16 +923,37 @@ bool gp_gemm_split256_usable(int I, int J, int K)
 
 size_t gp_gemm_split256_scratch_bytes() { return kHeaderBytes + sizeof(float) * kFragFloats * kSlots; }
 
-// scratch: flags zeroed by the caller once per forward (hipMemsetAsync of the first 8 KiB); one scratch per stream
-int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
-                            int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
-                            float* scratch, hipStream_t st)
+// Everything gp_gemm_split256 refuses, before any HIP call (the C entry runs it ahead of its scratch reset as well)
+static int split256_check(const float* act, int ld_act, const void* whi, const void* wlo, const float* D, int ldd, int I, int J, int K,
+                          int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr, const float* scratch)
 {
     GP_REQUIRE(gp_gemm_split256_usable(I, J, K), "gp_gemm_split256: I=%d, J=%d must be multiples of 256 with >= 256 tiles, K=%d of 32", I, J, K);
     GP_REQUIRE(act && whi && wlo && D && scratch && ld_act % 2 == 0 && ((uintptr_t)act % 8 == 0) && ((uintptr_t)whi % 16 == 0) &&
                    ((uintptr_t)wlo % 16 == 0) && ((uintptr_t)scratch % 16 == 0),
                "gp_gemm_split256: null / misaligned operand");
     GP_REQUIRE((long long)I * ldd < (1ll << 31) && (long long)I * (ldr > 0 ? ldr : 1) < (1ll << 31), "gp_gemm_split256: output too large");
+    GP_REQUIRE(ld_act >= (act_is_b ? J : I), "gp_gemm_split256: ld_act=%d is below the activation extent %d", ld_act, act_is_b ? J : I);
+    GP_REQUIRE(ldd >= J, "gp_gemm_split256: ldd=%d is below J=%d", ldd, J);
+#ifdef GP_PROBES
+    const bool built = epilogue >= GP_EPI_NONE && epilogue <= GP_EPI_BIAS_I_RELU;
+#else
+    const bool built = epilogue >= GP_EPI_BIAS_I && epilogue <= GP_EPI_BIAS_J;
+#endif
+    GP_REQUIRE(built, "gp_gemm_split256: epilogue %d is not built (product: 1-4; 0 and 5 need -DGP_PROBES)", epilogue);
+    GP_REQUIRE(bias || epilogue == GP_EPI_NONE, "gp_gemm_split256: epilogue %d needs a bias", epilogue);
+    if (epilogue == GP_EPI_BIAS_I_SCALE_RES) {
+        GP_REQUIRE(scale && res, "gp_gemm_split256: epilogue 3 needs scale and residual");
+        GP_REQUIRE(ldr >= J, "gp_gemm_split256: ldr=%d is below J=%d", ldr, J);
+    }
+    return GP_OK;
+}
+
+// scratch: flags zeroed by the caller once per forward (hipMemsetAsync of the first 8 KiB); one scratch per stream
+int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J,
+                            int K, int act_is_b, int epilogue, const float* bias, const float* scale, const float* res, int ldr,
+                            float* scratch, hipStream_t st)
+{
+    if (const int rc = split256_check(act, ld_act, whi, wlo, D, ldd, I, J, K, act_is_b, epilogue, bias, scale, res, ldr, scratch)) return rc;
     Args256 a{act, ld_act, (const _Float16*)whi, (const _Float16*)wlo, D, ldd, K, bias, scale, res, ldr, I / TB, J / TB, 4,
               reinterpret_cast<int*>(scratch), reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, gp_status_buffer()};
     g_epoch256 = (g_epoch256 + 1) & 0x3fffffff;  // bit 30 marks this kernel's epochs: it may share a scratch (and its
@@ -987,11 +1008,19 @@ bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K)
     return gp_gemm_split256_usable(I, J_main, K) || (g_planes_par && planes_par_usable(I, J_main, K));
 }
 
-int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
-                             void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
-                             const float* res, int ldr, float out_scale, float* scratch, hipStream_t st, unsigned long long* trace,
-                             const GpPlaneOut* po)
+// Everything the plane GEMM refuses, before any HIP call (the C entry runs it ahead of its scratch reset as well).
+// Byte ranges: the tile epilogues store (and read the residual) through raw buffer resources of kRsrcBytes = 0x7ffffff0 bytes with
+// 32-bit BYTE offsets -- epilogue_f32_lds: voffset (half * ld + j) * 4 + scalar offset row * ld * 4, 16 bytes per access, largest at
+// row I - 1, column J - 4: it ends at ((I - 1) ld + J) * 4; epilogue_planes_thin: voffset (j * ldo + i) * 2 + scalar offset
+// rows * ldo * 2, largest at token row J - 1, column I - 8: it ends at ((J - 1) ldo + I) * 2.  An access that ends beyond the resource
+// is dropped by the range check (a store vanishes, a load returns 0: no fault, no status bit), and from 2^32 bytes on the offset
+// arithmetic wraps; so each end must lie within kRsrcBytes.  (The strip phase and the 256 x 128 f32 epilogue use flat addresses
+// with 32-bit ELEMENT offsets, which the same bounds cover.)
+static int planes256_check(const void* ahi, const void* alo, const void* bhi, const void* blo, const float* D, int ldd, const void* ohi,
+                           const void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
+                           const float* res, int ldr, const float* scratch, const GpPlaneOut* po)
 {
+    constexpr long long kRsrcBytes = 0x7ffffff0ll;
     GP_REQUIRE(gp_gemm_planes256_usable(I, J, J_valid, K),
                "gp_gemm_planes256: I=%d, J=%d must be multiples of 256 with >= 8 tiles below J_valid=%d, K=%d of 32", I, J, J_valid, K);
     int J_main, strip_fj;
@@ -1002,23 +1031,55 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
                "gp_gemm_planes256: null / misaligned operand");
     GP_REQUIRE((long long)I * K * 2 < (1ll << 31) && (long long)J * K * 2 < (1ll << 31), "gp_gemm_planes256: operand planes too large");
     const bool planes_out = epilogue == GP_EPI_GELU_PLANES || epilogue == GP_EPI_BIAS_I_PLANES;
-    if (planes_out)
-        GP_REQUIRE(ohi && olo && ldo % 4 == 0 && ((uintptr_t)ohi % 8 == 0) && ((uintptr_t)olo % 8 == 0) && bias, "gp_gemm_planes256: bad plane output");
-    if (!planes_out)
-        GP_REQUIRE(D && (long long)I * ldd < (1ll << 31) && (long long)I * (ldr > 0 ? ldr : 1) < (1ll << 31) && ldd % 4 == 0 && ldr % 4 == 0 &&
-                       ((uintptr_t)D % 16 == 0) && ((uintptr_t)res % 16 == 0) && (epilogue != GP_EPI_BIAS_J || (uintptr_t)bias % 16 == 0),
-                   "gp_gemm_planes256: bad f32 output (16-byte rows)");
-    if (planes_out)
+#ifdef GP_PROBES
+    const bool built = epilogue >= GP_EPI_NONE && epilogue <= GP_EPI_BIAS_I_PLANES;
+#else
+    const bool built = epilogue == GP_EPI_BIAS_I_SCALE_RES || planes_out;
+#endif
+    GP_REQUIRE(built, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
+    GP_REQUIRE(bias || epilogue == GP_EPI_NONE, "gp_gemm_planes256: epilogue %d needs a bias", epilogue);
+    GP_REQUIRE((uintptr_t)bias % 16 == 0, "gp_gemm_planes256: bias must be 16-byte aligned");
+    if (planes_out) {
+        GP_REQUIRE(ohi && olo && ldo % 4 == 0 && ((uintptr_t)ohi % 8 == 0) && ((uintptr_t)olo % 8 == 0), "gp_gemm_planes256: bad plane output");
         GP_REQUIRE(ldo % 8 == 0 && ((uintptr_t)ohi % 16 == 0) && ((uintptr_t)olo % 16 == 0), "gp_gemm_planes256: plane output rows must be 16-byte aligned");
+        GP_REQUIRE(ldo >= I, "gp_gemm_planes256: ldo=%d is below I=%d", ldo, I);
+        GP_REQUIRE(((long long)(J - 1) * ldo + I) * 2 <= kRsrcBytes,
+                   "gp_gemm_planes256: output planes of J=%d rows x ldo=%d end beyond the 0x7ffffff0 bytes their stores can address", J, ldo);
+    } else {
+        GP_REQUIRE(D && (long long)I * ldd < (1ll << 31) && (long long)I * (ldr > 0 ? ldr : 1) < (1ll << 31) && ldd % 4 == 0 && ldr % 4 == 0 &&
+                       ((uintptr_t)D % 16 == 0) && ((uintptr_t)res % 16 == 0),
+                   "gp_gemm_planes256: bad f32 output (16-byte rows)");
+        GP_REQUIRE(ldd >= J, "gp_gemm_planes256: ldd=%d is below J=%d", ldd, J);
+        GP_REQUIRE(((long long)(I - 1) * ldd + J) * 4 <= kRsrcBytes,
+                   "gp_gemm_planes256: D of I=%d rows x ldd=%d ends beyond the 0x7ffffff0 bytes its stores can address", I, ldd);
+        if (epilogue == GP_EPI_BIAS_I_SCALE_RES) {
+            GP_REQUIRE(scale && res && (uintptr_t)scale % 16 == 0, "gp_gemm_planes256: epilogue 3 needs a 16-byte aligned scale and a residual");
+            GP_REQUIRE(ldr >= J, "gp_gemm_planes256: ldr=%d is below J=%d", ldr, J);
+            GP_REQUIRE(((long long)(I - 1) * ldr + J) * 4 <= kRsrcBytes,
+                       "gp_gemm_planes256: residual of I=%d rows x ldr=%d ends beyond the 0x7ffffff0 bytes its loads can address", I, ldr);
+        }
+    }
+    if (po)   // per-tensor output scale of the plane epilogues 6 / 7
+        GP_REQUIRE(po->scale > 0.f && (planes_out || (po->scale == kActScale && !po->amax)),
+                   "gp_gemm_planes256: a plane scale other than 8 needs epilogue 6 or 7 (got %d)", epilogue);
+    return GP_OK;
+}
+
+int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
+                             void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
+                             const float* res, int ldr, float out_scale, float* scratch, hipStream_t st, unsigned long long* trace,
+                             const GpPlaneOut* po)
+{
+    if (const int rc = planes256_check(ahi, alo, bhi, blo, D, ldd, ohi, olo, ldo, I, J, J_valid, K, epilogue, bias, scale, res, ldr, scratch, po)) return rc;
+    int J_main, strip_fj;
+    planes_ragged(J, J_valid, J_main, strip_fj);
     ArgsP a{(const _Float16*)ahi, (const _Float16*)alo, (const _Float16*)bhi, (const _Float16*)blo, D, ldd, (_Float16*)ohi, (_Float16*)olo, ldo,
             K, bias, scale, res, ldr, I / TB, J_main / TB, 4, reinterpret_cast<int*>(scratch),
             reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, out_scale, g_planes_dp, trace, gp_status_buffer(),
             J_main, strip_fj, (long long)(I / TB) * (J_main / TB) < kSlots ? max(1, (K / TBK) / g_planes_par_min_steps) : 0};
     a.plane_scale = kActScale;
     a.amax = nullptr;
-    if (po) {   // per-tensor output scale of the plane epilogues 6 / 7
-        GP_REQUIRE(po->scale > 0.f && (planes_out || (po->scale == kActScale && !po->amax)),
-                   "gp_gemm_planes256: a plane scale other than 8 needs epilogue 6 or 7 (got %d)", epilogue);
+    if (po) {   // per-tensor output scale of the plane epilogues 6 / 7 (planes256_check: only there may it differ from 8)
         a.plane_scale = po->scale;
         a.amax = po->amax;
     }
@@ -1128,6 +1189,7 @@ int gp_gemm_split256(const float* act, int ld_act, const void* whi, const void* 
                      float* scratch, size_t scratch_bytes, void* stream)
 {
     GP_REQUIRE(scratch && scratch_bytes >= gp_gemm_split256_scratch_bytes(), "gp_gemm_split256: scratch too small");
+    if (const int rc = split256_check(act, ld_act, whi, wlo, D, ldd, I, J, K, act_is_b, epilogue, bias, scale, residual, ldr, scratch)) return rc;
     if (hipMemsetAsync(scratch, 0, kHeaderBytes, (hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     return gp_gemm_split256_launch(act, ld_act, whi, wlo, D, ldd, I, J, K, act_is_b, epilogue, bias, scale, residual, ldr, scratch,
                                    (hipStream_t)stream);
@@ -1151,8 +1213,10 @@ int gp_gemm_planes256_scaled(const void* a_hi, const void* a_lo, const void* b_h
                              size_t scratch_bytes, void* stream)
 {
     GP_REQUIRE(scratch && scratch_bytes >= gp_gemm_split256_scratch_bytes(), "gp_gemm_planes256_scaled: scratch too small");
-    if (hipMemsetAsync(scratch, 0, kHeaderBytes, (hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     const GpPlaneOut po{plane_scale, amax};
+    if (const int rc = planes256_check(a_hi, a_lo, b_hi, b_lo, D, ldd, out_hi, out_lo, ldo, I, J, J_valid, K, epilogue, bias, scale, residual, ldr, scratch, &po))
+        return rc;
+    if (hipMemsetAsync(scratch, 0, kHeaderBytes, (hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     return gp_gemm_planes256_launch(a_hi, a_lo, b_hi, b_lo, D, ldd, out_hi, out_lo, ldo, I, J, J_valid, K, epilogue, bias, scale, residual, ldr,
                                     out_scale, scratch, (hipStream_t)stream, nullptr, &po);
 }

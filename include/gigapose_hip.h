@@ -139,7 +139,8 @@ int gp_select_topk(const float* sim_avg, const uint8_t* idx_t2s, const float* sc
  * (src/models/network/ist_net.py:140-155).
  * epilogue: 0 none | 1 +bias[i] | 2 gelu_erf(+bias[i]) | 3 residual[i][j] + scale[i]*(acc+bias[i])
  *           (D may alias residual) | 4 +bias[j] | 5 relu(+bias[i]).
- * Requires I % 128 == 0, J % 128 == 0, K % 16 == 0, lda/ldb % 4 == 0, 16-byte aligned A/B. */
+ * Requires I % 128 == 0, J % 128 == 0, K % 16 == 0, lda/ldb % 4 == 0, 16-byte aligned A/B, lda >= I, ldb >= J, ldd >= J,
+ * I * ldd < 2^31 elements (and I * ldr), non-null bias / scale / residual where the epilogue reads them, ldr >= J with a residual. */
 int gp_gemm_kmajor(const float* A, int lda, const float* B, int ldb, float* D, int ldd, int I, int J,
                    int K, int epilogue, const float* bias, const float* scale, const float* residual,
                    int ldr, void* stream);
@@ -163,7 +164,10 @@ int gp_gemm_kmajor_sk(const float* A, int lda, const float* B, int ldb, float* D
  *   gp_split_weights: W^T (K, n) f32 k-major (row stride ldw) -> planes hi, lo (n, K) f16.
  *   gp_gemm_split: act (K, ld_act) f32 k-major activations; whi / wlo (n_w, K) pre-split weights;
  *     act_is_b != 0: D[i][j] = sum_k W[i][k] act[k][j];  act_is_b == 0: D[i][j] = sum_k act[k][i] W[j][k].
- *     epilogues as gp_gemm_kmajor.  Requires I, J % 128 == 0, K % 32 == 0. */
+ *     epilogues as gp_gemm_kmajor.  Requires I, J % 128 == 0, K % 32 == 0, ld_act % 4 == 0, 16-byte aligned act / whi / wlo,
+ *     ld_act >= the activation extent (J with act_is_b, else I), ldd >= J, I * ldd < 2^31 elements (and I * ldr), non-null bias /
+ *     scale / residual where the epilogue reads them, ldr >= J with a residual, and a 16-byte aligned bias for the epilogues that add
+ *     it along i (1, 2, 3, 5: the kernel loads four rows at once). */
 int gp_split_weights(const float* Wt, int K, int n, int ldw, void* hi, void* lo, void* stream);
 /* (Also splits the ACTIVATIONS that feed gp_conv2d_nhwc_split.  A value with |x| > 65504 -- the hi plane would hold inf -- or a non-finite
  * one raises bit 16 of the status word, GP_STATUS_SPLIT_RANGE_CONV; the planes written are the same either way.) */
@@ -201,7 +205,9 @@ int gp_vit_forward(const float* images, int B, int dim, int depth, int heads, in
  * lo = f16(64 w - hi)), work balanced by stream-K with deterministic accumulator hand-offs.  Same arguments as
  * gp_gemm_split plus a device scratch of gp_gemm_split256_workspace_bytes() bytes (one per stream); requires
  * I, J % 256 == 0, K % 32 == 0, (I/256)*(J/256) >= 256, |activation| < 8190; epilogues 1-4 (0 and 5 in the probe library).  A lost
- * hand-over raises GP_STATUS_HANDOFF_SPLIT in the status word. */
+ * hand-over raises GP_STATUS_HANDOFF_SPLIT in the status word.  Leading dimensions and pointers as gp_gemm_split (ld_act >= the
+ * activation extent, ldd >= J, ldr >= J with a residual, non-null bias / scale / residual where the epilogue reads them; ld_act % 2 == 0,
+ * act 8-byte aligned; no alignment asked of bias).  Every refusal precedes the reset of the scratch. */
 size_t gp_gemm_split256_workspace_bytes(void);
 int gp_split256_weights(const float* W, size_t count, void* hi, void* lo, void* stream);
 int gp_gemm_split256(const float* act, int ld_act, const void* whi, const void* wlo, float* D, int ldd, int I, int J, int K,
@@ -222,7 +228,12 @@ int gp_gemm_split256(const float* act, int ld_act, const void* whi, const void* 
  * Needs (I / 256) * (J_valid / 256) >= 8 tiles and at least one k-step per slot; below 256 tiles the slots of a tile split its K in
  * parallel (fixed-order reduction), below 128 the tiles are 256 x 128.
  * plane_scale: the power of two the OUTPUT planes of epilogues 6 / 7 carry (the consumer GEMM then runs with out_scale = 1 / (64 s));
- * amax: NULL, or (calibration passes) a device float that receives max |x| of the planes written (atomic max on the f32 bits). */
+ * amax: NULL, or (calibration passes) a device float that receives max |x| of the planes written (atomic max on the f32 bits).
+ * Requires 16-byte aligned planes and scratch; a non-null, 16-byte aligned bias for every epilogue but 0; for the f32 epilogues D and
+ * residual 16-byte aligned, ldd % 4 == 0, ldr % 4 == 0, ldd >= J and, for epilogue 3, a residual, a 16-byte aligned scale and ldr >= J;
+ * for epilogues 6 / 7 out_hi / out_lo 16-byte aligned, ldo % 8 == 0 and ldo >= I.  The tile epilogues address their outputs with 32-bit
+ * byte offsets inside 0x7ffffff0 bytes: the last byte of D, ((I - 1) ldd + J) * 4, of the residual, ((I - 1) ldr + J) * 4, and of each
+ * output plane, ((J - 1) ldo + I) * 2, must not exceed that (just under 2 GiB each).  Every refusal precedes the reset of the scratch. */
 int gp_split_planes(const float* X, size_t count, float scale, void* hi, void* lo, void* stream);
 int gp_gemm_planes256_scaled(const void* a_hi, const void* a_lo, const void* b_hi, const void* b_lo, float* D, int ldd, void* out_hi,
                              void* out_lo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,

@@ -25,7 +25,8 @@ import torch
 from gigapose_amd import _lib
 from gigapose_testing import synthetic as syn
 from oracle import ist_torch
-from test_gpu_vit import hip_gemm, run_vit
+from gigapose_testing import gemm_layout as gl
+from test_gpu_vit import hip_gemm, run_vit, view_ptr
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -80,18 +81,27 @@ def epilogue_f64(epi, acc, mag, bias, scale, res):
     return want, bound
 
 
-def split_gemm(act, W, act_is_b, epi=0, bias=None, scale=None, res=None):
-    """act (K, n_act) f32 k-major, W (n_w, K) f32 [out][in]."""
+def split_gemm(act, W, act_is_b, epi=0, bias=None, scale=None, res=None, layout=None):
+    """act (K, n_act) f32 k-major, W (n_w, K) f32 [out][in].  layout (gigapose_testing.gemm_layout.Layout): the activation as a window of
+    a NaN-filled array, D inside a sentinel-filled buffer; returns (that buffer, (residual array after, before) or None) on the device."""
     from gigapose_amd import _lib
     from gigapose_amd.vit import split_planes
 
     K = act.shape[0]
     I, J = (W.shape[0], act.shape[1]) if act_is_b else (act.shape[1], W.shape[0])
     hi, lo = split_planes(torch.from_numpy(W).to(DEV))
-    ta = torch.from_numpy(act).to(DEV)
-    D = torch.empty(I, J, device=DEV)
     tb = None if bias is None else torch.from_numpy(bias).to(DEV)
     ts = None if scale is None else torch.from_numpy(scale).to(DEV)
+    if layout is not None:
+        ta = gl.embed(torch.from_numpy(act).to(DEV), layout.a_ld or act.shape[1], layout.a_col)[1]
+        flat, D, tr, ldr, pair = gl.place_output(layout, I, J, epi, None if res is None else torch.from_numpy(res).to(DEV), DEV)
+        _lib.call("gp_gemm_split", view_ptr(ta), _lib.i(ta.stride(0)), _lib.ptr(hi), _lib.ptr(lo), view_ptr(D), _lib.i(D.stride(0)), _lib.i(I),
+                  _lib.i(J), _lib.i(K), _lib.i(1 if act_is_b else 0), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), view_ptr(tr), _lib.i(ldr),
+                  _lib.stream_ptr())
+        torch.cuda.synchronize()
+        return flat, pair
+    ta = torch.from_numpy(act).to(DEV)
+    D = torch.empty(I, J, device=DEV)
     tr = None if res is None else torch.from_numpy(res).to(DEV)
     _lib.call("gp_gemm_split", _lib.ptr(ta), _lib.i(act.shape[1]), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I),
               _lib.i(J), _lib.i(K), _lib.i(1 if act_is_b else 0), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), _lib.ptr(tr), _lib.i(J),
@@ -444,10 +454,11 @@ def test_ist_backbone_split_vs_chain_and_torch():
     assert e_split < 2e-5 and e_split <= 1.5 * e_chain + 1e-7 and e_128 <= 1.5 * e_chain + 1e-7
 
 
-def split256_gemm(act, W, act_is_b, epi=None, bias=None, scale=None, res=None):
+def split256_gemm(act, W, act_is_b, epi=None, bias=None, scale=None, res=None, layout=None, scratch=None):
     """gp_gemm_split256 through the C-ABI.  act (K, n_act) f32 k-major, W (n_w, K) f32 [out][in].  epi None: the plain contraction, as
     epilogue 1 with a zero bias (acc * out_scale + 0: exact up to the sign of zero; epilogue 0 is built into the probe library only).
-    A lost stream-K hand-over raises through the status word (both builds) and, where the build has the reader, the scratch's error word."""
+    A lost stream-K hand-over raises through the status word (both builds) and, where the build has the reader, the scratch's error word.
+    layout: as split_gemm's; scratch: the caller's workspace instead of a fresh one (two launches that share one)."""
     from gigapose_amd import _lib
     from gigapose_amd.vit import split_planes_x64
 
@@ -458,22 +469,29 @@ def split256_gemm(act, W, act_is_b, epi=None, bias=None, scale=None, res=None):
     if epi is None:
         epi, bias = 1, np.zeros(I, np.float32)
     hi, lo = split_planes_x64(torch.from_numpy(W).to(DEV))
-    ta = torch.from_numpy(act).to(DEV)
-    D = torch.from_numpy(res).to(DEV).clone() if epi == 3 else torch.empty(I, J, device=DEV)
     tb = None if bias is None else torch.from_numpy(bias).to(DEV)
     ts = None if scale is None else torch.from_numpy(scale).to(DEV)
-    ws = torch.full((nb // 4,), float("nan"), device=DEV)
+    if layout is not None:
+        ta = gl.embed(torch.from_numpy(act).to(DEV), layout.a_ld or act.shape[1], layout.a_col)[1]
+        flat, D, tr, ldr, pair = gl.place_output(layout, I, J, epi, None if res is None else torch.from_numpy(res).to(DEV), DEV)
+    else:
+        ta = torch.from_numpy(act).to(DEV)
+        D = torch.from_numpy(res).to(DEV).clone() if epi == 3 else torch.empty(I, J, device=DEV)
+        tr, ldr = (D if epi == 3 else None), J
+    ws = torch.full((nb // 4,), float("nan"), device=DEV) if scratch is None else scratch
     _lib.status_word(DEV).zero_()
     for _ in range(2):  # second launch: stale flags of the first must not satisfy it
-        if epi == 3:
+        if epi == 3 and tr is D:
             D.copy_(torch.from_numpy(res))
-        _lib.call("gp_gemm_split256", _lib.ptr(ta), _lib.i(act.shape[1]), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I),
-                  _lib.i(J), _lib.i(K), _lib.i(1 if act_is_b else 0), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), _lib.ptr(D if epi == 3 else None),
-                  _lib.i(J), _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
+        _lib.call("gp_gemm_split256", view_ptr(ta), _lib.i(ta.stride(0)), _lib.ptr(hi), _lib.ptr(lo), view_ptr(D), _lib.i(D.stride(0)), _lib.i(I),
+                  _lib.i(J), _lib.i(K), _lib.i(1 if act_is_b else 0), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), view_ptr(tr),
+                  _lib.i(ldr), _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
     torch.cuda.synchronize()
     if hasattr(lib, "gp_gemm_split256_error"):   # the scratch's error word: its reader is in the probe library only
         assert lib.gp_gemm_split256_error(_lib.ptr(ws), _lib.stream_ptr()) == 0, "a stream-K hand-off timed out"
     _lib.check_status()                          # both builds: GP_STATUS_HANDOFF_SPLIT, a stream-K hand-over timed out (read and cleared)
+    if layout is not None:
+        return flat, pair
     return D.cpu().numpy()
 
 
@@ -618,8 +636,11 @@ def test_attention_split_matches_f64():
     assert torch.count_nonzero(ohi[M:]) == 0  # pad rows untouched
 
 
-def planes256_gemm(A, Bm, epi, bias=None, scale=None, res=None, a_scale=64.0, b_scale=8.0, j_valid=None):
+def planes256_gemm(A, Bm, epi, bias=None, scale=None, res=None, a_scale=64.0, b_scale=8.0, j_valid=None, layout=None):
     """A [I][K], Bm [J][K] f32 -> D[i][j] through gp_split_planes + gp_gemm_planes256 (epi 6: returns the (hi, lo) planes O[j][i]).
+    layout (gigapose_testing.gemm_layout.Layout): D at an offset of a sentinel-filled buffer with its own ldd and, with r_ld, a residual of
+    its own (returns (buffer, (residual array after, before) or None)); epilogues 6 / 7 write columns o_col .. o_col + I of rows of o_ld
+    halves in the layout's buffers or fresh sentinel-filled ones (returns the (hi, lo) flat buffers).
     j_valid: rows of Bm that carry data (gp_gemm_planes256_ragged: tiles below floor(j_valid / 256) * 256, strip above).
     The status word is cleared before the launch and read (and cleared) after it: a lost stream-K hand-over or a value beyond the
     planes' range raises in either build; the probe build's error-word reader is asserted as well."""
@@ -635,18 +656,34 @@ def planes256_gemm(A, Bm, epi, bias=None, scale=None, res=None, a_scale=64.0, b_
 
     (ahi, alo), (bhi, blo) = planes(A, a_scale), planes(Bm, b_scale)
     I, J, K = A.shape[0], Bm.shape[0], A.shape[1]
-    D = res.clone() if res is not None else torch.zeros(I, J, device=DEV)
-    ohi = torch.zeros(J, I, dtype=torch.float16, device=DEV)
-    olo = torch.zeros_like(ohi)
     _lib.status_word(DEV).zero_()
-    _lib.call("gp_gemm_planes256_scaled", _lib.ptr(ahi), _lib.ptr(alo), _lib.ptr(bhi), _lib.ptr(blo), _lib.ptr(D), _lib.i(J), _lib.ptr(ohi),
-              _lib.ptr(olo), _lib.i(I), _lib.i(I), _lib.i(J), _lib.i(J if j_valid is None else j_valid), _lib.i(K), _lib.i(epi), _lib.ptr(bias),
-              _lib.ptr(scale), _lib.ptr(D), _lib.i(J), _lib.f(1.0 / (a_scale * b_scale)), _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
+    if layout is not None:
+        # the product's calls: plane epilogues get no f32 operand (D = residual = NULL, ldd = ldr = 0), f32 epilogues no planes
+        if epi in (6, 7):
+            fhi, flo, ldo = gl.place_planes(layout, I, J, DEV)
+            D = tr = None
+            ldd = ldr = 0
+            ohi, olo = fhi[layout.o_col:], flo[layout.o_col:]
+        else:
+            flat, D, tr, ldr, pair = gl.place_output(layout, I, J, epi, res, DEV)
+            ldd, ohi, olo, ldo = D.stride(0), None, None, 0
+        _lib.call("gp_gemm_planes256_scaled", _lib.ptr(ahi), _lib.ptr(alo), _lib.ptr(bhi), _lib.ptr(blo), view_ptr(D), _lib.i(ldd), view_ptr(ohi),
+                  view_ptr(olo), _lib.i(ldo), _lib.i(I), _lib.i(J), _lib.i(J if j_valid is None else j_valid), _lib.i(K), _lib.i(epi), _lib.ptr(bias),
+                  _lib.ptr(scale), view_ptr(tr), _lib.i(ldr), _lib.f(1.0 / (a_scale * b_scale)), _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
+    else:
+        D = res.clone() if res is not None else torch.zeros(I, J, device=DEV)
+        ohi = torch.zeros(J, I, dtype=torch.float16, device=DEV)
+        olo = torch.zeros_like(ohi)
+        _lib.call("gp_gemm_planes256_scaled", _lib.ptr(ahi), _lib.ptr(alo), _lib.ptr(bhi), _lib.ptr(blo), _lib.ptr(D), _lib.i(J), _lib.ptr(ohi),
+                  _lib.ptr(olo), _lib.i(I), _lib.i(I), _lib.i(J), _lib.i(J if j_valid is None else j_valid), _lib.i(K), _lib.i(epi), _lib.ptr(bias),
+                  _lib.ptr(scale), _lib.ptr(D), _lib.i(J), _lib.f(1.0 / (a_scale * b_scale)), _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
     torch.cuda.synchronize()
     if hasattr(lib, "gp_gemm_split256_error"):   # the scratch's error word: its reader is in the probe library only.  Asserted BEFORE the
         # status word is read: tests/test_gpu_guards.py::test_lost_handoff_raises expects this assertion and then reads the status bit itself
         assert lib.gp_gemm_split256_error(_lib.ptr(ws), _lib.stream_ptr()) == 0
     _lib.check_status()                          # both builds: a lost hand-over (GP_STATUS_HANDOFF_SPLIT), a value beyond the planes (read and cleared)
+    if layout is not None:
+        return (fhi, flo) if epi in (6, 7) else (flat, pair)
     return (ohi, olo) if epi in (6, 7) else D
 
 

@@ -14,15 +14,40 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def hip_gemm(A, B, epi=0, bias=None, scale=None, res=None):
+def view_ptr(t):
+    """Device pointer of a view (a window of a wider array is not contiguous: _lib.ptr refuses it)."""
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def laid_out_kmajor(A, B, epi, res, layout):
+    """The operand windows and output buffers of a gp_gemm_kmajor(_sk) launch under gigapose_testing.gemm_layout.Layout."""
+    from gigapose_testing import gemm_layout as gl
+
+    K, I = A.shape
+    J = B.shape[1]
+    tA = gl.embed(torch.from_numpy(A).to(DEV), layout.a_ld or I, layout.a_col)[1]
+    tB = gl.embed(torch.from_numpy(B).to(DEV), layout.b_ld or J, layout.b_col)[1]
+    flat, D, tr, ldr, pair = gl.place_output(layout, I, J, epi, None if res is None else torch.from_numpy(res).to(DEV), DEV)
+    return tA, tB, flat, D, tr, ldr, pair
+
+
+def hip_gemm(A, B, epi=0, bias=None, scale=None, res=None, layout=None):
+    """layout (gigapose_testing.gemm_layout.Layout): operands as windows of NaN-filled arrays, D inside a sentinel-filled buffer; returns
+    (that buffer, (residual array after, before) or None) on the device for gemm_layout.check instead of D."""
     from gigapose_amd import _lib
 
     K, I = A.shape
     J = B.shape[1]
-    tA, tB = torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)
-    D = torch.empty(I, J, device=DEV)
     tb = None if bias is None else torch.from_numpy(bias).to(DEV)
     ts = None if scale is None else torch.from_numpy(scale).to(DEV)
+    if layout is not None:
+        tA, tB, flat, D, tr, ldr, pair = laid_out_kmajor(A, B, epi, res, layout)
+        _lib.call("gp_gemm_kmajor", view_ptr(tA), _lib.i(tA.stride(0)), view_ptr(tB), _lib.i(tB.stride(0)), view_ptr(D), _lib.i(D.stride(0)),
+                  _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), view_ptr(tr), _lib.i(ldr), _lib.stream_ptr())
+        torch.cuda.synchronize()
+        return flat, pair
+    tA, tB = torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)
+    D = torch.empty(I, J, device=DEV)
     tr = None if res is None else torch.from_numpy(res).to(DEV)
     _lib.call("gp_gemm_kmajor", _lib.ptr(tA), _lib.i(I), _lib.ptr(tB), _lib.i(J), _lib.ptr(D), _lib.i(J),
               _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), _lib.ptr(tr), _lib.i(J),
@@ -46,8 +71,8 @@ def test_gemm_bit_exact_vs_fmaf_chain(epi):
     np.testing.assert_allclose(got if epi == 0 else got, ref, rtol=1e-6)
 
 
-def hip_gemm_sk(A, B, epi, bias, scale, res):
-    """gp_gemm_kmajor_sk: same contraction with the stream-K scratch (tile count not a multiple of the slots)."""
+def hip_gemm_sk(A, B, epi, bias, scale, res, layout=None):
+    """gp_gemm_kmajor_sk: same contraction with the stream-K scratch (tile count not a multiple of the slots).  layout: as hip_gemm's."""
     import ctypes
     from gigapose_amd import _lib
 
@@ -55,19 +80,28 @@ def hip_gemm_sk(A, B, epi, bias, scale, res):
     nbytes = lib.gp_gemm_streamk_workspace_bytes()
     K, I = A.shape
     J = B.shape[1]
-    tA, tB = torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)
-    D = torch.from_numpy(res).to(DEV).clone() if epi == 3 else torch.empty(I, J, device=DEV)
     tb, ts = torch.from_numpy(bias).to(DEV), torch.from_numpy(scale).to(DEV)
-    tr = D if epi == 3 else None                     # in-place residual, as the ViT uses it
     ws = torch.full((nbytes // 4,), float("nan"), device=DEV)
     _lib.call("gp_gemm_streamk_reset", _lib.ptr(ws), _lib.stream_ptr())
+    _lib.status_word(DEV).zero_()
+    if layout is not None:
+        tA, tB, flat, D, tr, ldr, pair = laid_out_kmajor(A, B, epi, res, layout)
+    else:
+        tA, tB = torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)
+        D = torch.from_numpy(res).to(DEV).clone() if epi == 3 else torch.empty(I, J, device=DEV)
+        tr, ldr = (D if epi == 3 else None), J       # in-place residual, as the ViT uses it
     for _ in range(2):                               # second launch: flags of the first must not satisfy it
-        if epi == 3:
+        if epi == 3 and tr is D:
             D.copy_(torch.from_numpy(res))
-        _lib.call("gp_gemm_kmajor_sk", _lib.ptr(tA), _lib.i(I), _lib.ptr(tB), _lib.i(J), _lib.ptr(D), _lib.i(J),
-                  _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), _lib.ptr(tr), _lib.i(J),
+        _lib.call("gp_gemm_kmajor_sk", view_ptr(tA), _lib.i(tA.stride(0)), view_ptr(tB), _lib.i(tB.stride(0)), view_ptr(D), _lib.i(D.stride(0)),
+                  _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(tb), _lib.ptr(ts), view_ptr(tr), _lib.i(ldr),
                   _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
-    assert lib.gp_gemm_streamk_error(_lib.ptr(ws), _lib.stream_ptr()) == 0, "a stream-K hand-off timed out"
+    if hasattr(lib, "gp_gemm_streamk_error"):        # the scratch's error word: its reader is in the probe library only
+        assert lib.gp_gemm_streamk_error(_lib.ptr(ws), _lib.stream_ptr()) == 0, "a stream-K hand-off timed out"
+    torch.cuda.synchronize()
+    _lib.check_status()                              # both builds: GP_STATUS_HANDOFF_CHAIN
+    if layout is not None:
+        return flat, pair
     return D.cpu().numpy()
 
 
