@@ -31,7 +31,7 @@ def hip_conv(X, W, alpha, beta, res, stride, pad, relu, nchw=False):
     return Y.cpu().numpy()
 
 
-@pytest.mark.parametrize("cin,cout,k,stride,pad,hw,B,bn,res,relu", [
+CONV_SHAPES = [
     (3, 128, 7, 2, 3, 64, 1, True, False, True),     # stem shape (K=147 -> padded 160)
     (8, 64, 3, 1, 1, 16, 2, True, True, True),       # BasicBlock conv2 + residual (direct kernel, 16x16 window)
     (24, 128, 3, 1, 1, 32, 2, True, True, True),     # direct kernel, 32x8 window, 3 channel chunks, 2 co tiles
@@ -39,9 +39,10 @@ def hip_conv(X, W, alpha, beta, res, stride, pad, relu, nchw=False):
     (16, 192, 3, 2, 1, 32, 1, True, False, True),    # strided block entry, Cout = 3*64
     (24, 64, 1, 2, 0, 32, 1, True, False, False),    # downsample 1x1 stride 2
     (32, 64, 1, 1, 0, 16, 1, False, False, False),   # layer4_outconv (no BN)
-])
-@pytest.mark.probes
-def test_conv_bit_exact_vs_oracle(cin, cout, k, stride, pad, hw, B, bn, res, relu):
+]
+
+
+def conv_case(cin, cout, k, stride, pad, hw, B, bn, res):
     rs = np.random.RandomState(cin * 7 + cout)
     X = rs.standard_normal((cin, B, hw, hw)).astype(np.float32)
     W = (rs.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
@@ -49,6 +50,13 @@ def test_conv_bit_exact_vs_oracle(cin, cout, k, stride, pad, hw, B, bn, res, rel
     beta = rs.standard_normal(cout).astype(np.float32) if bn else None
     oh = (hw + 2 * pad - k) // stride + 1
     R = rs.standard_normal((cout, B, oh, oh)).astype(np.float32) if res else None
+    return X, W, alpha, beta, R
+
+
+@pytest.mark.parametrize("cin,cout,k,stride,pad,hw,B,bn,res,relu", CONV_SHAPES)
+def test_conv_bit_exact_vs_oracle(cin, cout, k, stride, pad, hw, B, bn, res, relu):
+    """On the product library (the chain reference of the backbone tests): all seven shapes bit for bit against the oracle's fmaf chain."""
+    X, W, alpha, beta, R = conv_case(cin, cout, k, stride, pad, hw, B, bn, res)
     got = hip_conv(X, W, alpha, beta, R, stride, pad, relu)
     ref = oracle.conv2d_cm(X, W, alpha, beta, R, stride, pad, relu)
     np.testing.assert_array_equal(got.view(np.uint32), ref.view(np.uint32))
@@ -65,15 +73,27 @@ def test_conv_bit_exact_vs_oracle(cin, cout, k, stride, pad, hw, B, bn, res, rel
     if not res:
         nchw = hip_conv(X, W, alpha, beta, None, stride, pad, relu, nchw=True)
         np.testing.assert_array_equal(nchw, got.transpose(1, 0, 2, 3))
-    if k == 3 and stride == 1:  # the generic im2col-gather kernel must agree with the direct one bit-for-bit
-        from gigapose_amd import _lib
 
-        _lib.lib().gp_conv_set_direct(0)
-        try:
-            generic = hip_conv(X, W, alpha, beta, R, stride, pad, relu)
-        finally:
-            _lib.lib().gp_conv_set_direct(1)
-        np.testing.assert_array_equal(generic.view(np.uint32), got.view(np.uint32))
+
+@pytest.mark.probes     # gp_conv_set_direct: an A/B switch of the probe build
+@pytest.mark.parametrize("cin,cout,k,stride,pad,hw,B,bn,res,relu", CONV_SHAPES)
+def test_conv_generic_kernel_equals_the_direct_one(cin, cout, k, stride, pad, hw, B, bn, res, relu):
+    """The probe build: every shape bit for bit against the oracle as well, and where the direct kernel runs (3 x 3 / stride 1) the generic
+    im2col-gather kernel must agree with it bit for bit."""
+    from gigapose_amd import _lib
+
+    X, W, alpha, beta, R = conv_case(cin, cout, k, stride, pad, hw, B, bn, res)
+    got = hip_conv(X, W, alpha, beta, R, stride, pad, relu)
+    ref = oracle.conv2d_cm(X, W, alpha, beta, R, stride, pad, relu)
+    np.testing.assert_array_equal(got.view(np.uint32), ref.view(np.uint32))
+    if not (k == 3 and stride == 1):
+        return
+    _lib.lib().gp_conv_set_direct(0)
+    try:
+        generic = hip_conv(X, W, alpha, beta, R, stride, pad, relu)
+    finally:
+        _lib.lib().gp_conv_set_direct(1)
+    np.testing.assert_array_equal(generic.view(np.uint32), got.view(np.uint32))
 
 
 def test_resize_matches_torch():

@@ -26,6 +26,7 @@ from gigapose_amd import _lib
 from gigapose_testing import synthetic as syn
 from oracle import ist_torch
 from gigapose_testing import gemm_layout as gl
+from gigapose_testing import conv_plans
 from test_gpu_vit import hip_gemm, run_vit, view_ptr
 
 pytestmark = pytest.mark.gpu
@@ -389,6 +390,23 @@ def run_conv_planes(X, Wt, alpha, beta, R, stride, pad):
 @pytest.mark.parametrize("cin,cout,k,stride,pad,hw,B,res", CONV_PLANES_SHAPES)
 def test_conv_planes_vs_f64(cin, cout, k, stride, pad, hw, B, res):
     """gp_conv2d_planes (gp_conv256.hip) against an f64 convolution + BN + residual + ReLU: both outputs (planes, f32 NCHW)."""
+    X, Wt, alpha, beta, R, t = conv_planes_case(cin, cout, k, stride, pad, hw, B, res)
+    of32, oh_, ol_ = run_conv_planes(X, Wt, alpha, beta, R, stride, pad)
+    got_planes = ((oh_.double() + ol_.double()) / 8.0).cpu().numpy().transpose(0, 3, 1, 2)
+    tol = max(1.0, np.abs(t).max())
+    print(f"[{binary_name()}] conv planes {cin}->{cout} k{k} s{stride} {hw}x{hw} B={B}: max err / max|y| f32 out {np.abs(of32.cpu().numpy() - t).max() / tol:.2e}, planes {np.abs(got_planes - t).max() / tol:.2e}")
+    np.testing.assert_allclose(of32.cpu().numpy(), t, rtol=0, atol=2e-6 * tol)
+    np.testing.assert_allclose(got_planes, t, rtol=0, atol=3e-6 * tol)
+
+
+@also_on_probe_binary
+@pytest.mark.parametrize("cin,cout,k,stride,pad,hw,B,res", [s for s, _, _ in conv_plans.STAGE_SHAPES],
+                         ids=[f"{'-'.join(map(str, s))}:{c.split()[0]}-{c.split()[1]}" for s, c, _ in conv_plans.STAGE_SHAPES])
+def test_conv_planes_launch_plans_vs_f64(cin, cout, k, stride, pad, hw, B, res):
+    """gp_conv2d_planes under the launch plans a batch size selects (gigapose_testing/conv_plans.py: STAGE_SHAPES -- the gather kernel's
+    middle segment and its chains of hand-overs at slots_x = 2 .. 16, the halo kernel's serial plan with cut tiles and data-parallel rounds,
+    its parallel split with two par_S, with S = 1 and idle slots, at Cout = 64, at 7 / 8 / 255 / 256 / 257 tiles), each at the smallest shape
+    that has the plan (tests/test_conv_plans.py holds the list to the model).  Same reference and tolerances as test_conv_planes_vs_f64."""
     X, Wt, alpha, beta, R, t = conv_planes_case(cin, cout, k, stride, pad, hw, B, res)
     of32, oh_, ol_ = run_conv_planes(X, Wt, alpha, beta, R, stride, pad)
     got_planes = ((oh_.double() + ol_.double()) / 8.0).cpu().numpy().transpose(0, 3, 1, 2)
