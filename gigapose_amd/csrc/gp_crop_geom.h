@@ -2,7 +2,8 @@
 // onboard/gpo_onboard.hip (RGBA renders).  Header only; written ONCE: the translation units must never disagree on a pixel.
 //   - the source-index arithmetic: both resizes of CropResizePad.__call__ (src/utils/crop.py:11-61) are nearest-neighbour, so
 //     output pixel (y, x) maps to one source pixel through the composed index maps below -- exactly the integer / float
-//     arithmetic of ATen's nearest kernels, restated in oracle/crop_numpy.py;
+//     arithmetic of ATen's CPU nearest kernels as measured on torch 2.10 (oracle/crop_numpy.py states it, and
+//     tests/test_crop_aten_sweep.py holds that statement to ATen itself);
 //   - the kernel skeleton, grid (target rows, items), block = 256 threads, thread = output column: crop_block_enter (geometry,
 //     error flag or M, barrier) and crop_row_normalized (the row loop over a pixel source, Normalize's stores).
 #pragma once
@@ -17,16 +18,24 @@ struct CropGeom {
     int h1, w1;              // size after the first resize
     int pad_t, pad_l, hp, wp;
     float inv1;              // (float)(1.0 / scale): source-index scale of the first resize
-    int mode1y, mode1x;      // 0 identity, 1 dst >> 1, 2 floorf(dst * inv1)
+    int mode1y, mode1x;      // 0 identity, 1 dst >> 1, 2 min(floorf(dst * inv1), in - 1)
     float s2y, s2x;          // in/out scales of the final resize
     int mode2y, mode2x;
     float scale32;
     int bad;
 };
 
-__device__ __forceinline__ int resize_mode(int out, int in) { return out == in ? 0 : (out == 2 * in ? 1 : 2); }
+// ATen's CPU upsample_nearest2d has two kernels and picks one per call, for both dimensions: the one whose nearest_idx
+// (UpSample.h) returns dst for out == in and dst >> 1 for out == 2 * in runs only while out_h + out_w <= 128 (or on a
+// channels-last input of more than 3 channels: never a slice of an NCHW frame); the generic kernel floors every index.
+// The two differ under a scale_factor that is not exactly 1 or 2.
+constexpr int kAtenVectorizedMaxHW = 128;
+__device__ __forceinline__ int resize_mode(int out, int in, bool shortcuts)
+{
+    return !shortcuts ? 2 : (out == in ? 0 : (out == 2 * in ? 1 : 2));
+}
 
-// ATen nearest_idx (UpSample.h): identity / >>1 shortcuts, else min(floorf(dst * scale), in - 1)
+// source index of one dimension: the shortcuts where resize_mode granted them, else min(floorf(dst * scale), in - 1)
 __device__ __forceinline__ int nearest_src(int dst, int in, int mode, float scale)
 {
     if (mode == 0) return dst;
@@ -44,7 +53,9 @@ __device__ void make_geom(const long long* box, int H, int W, int target, CropGe
     g.x0 = (int)bx0;
     g.y0 = (int)by0;
     const int bw = (int)(bx1 - bx0), bh = (int)(by1 - by0);
-    g.scale32 = (float)target / (float)(bw > bh ? bw : bh);            // crop.py:20 (float32 tensor division)
+    // crop.py:20, `target_size / int32_tensor`: Tensor.__rtruediv__ is reciprocal() * target, TWO float32 roundings (built
+    // with -ffp-contract=off -fno-fast-math: a true division, then a multiply)
+    g.scale32 = (1.0f / (float)(bw > bh ? bw : bh)) * (float)target;
     const double scale = (double)g.scale32;                            // .item()
     g.cw = (int)((bx1 < W ? bx1 : W) - bx0);                            // slicing clamps (crop.py:31)
     g.ch = (int)((by1 < H ? by1 : H) - by0);
@@ -52,8 +63,9 @@ __device__ void make_geom(const long long* box, int H, int W, int target, CropGe
     g.w1 = (int)floor((double)g.cw * scale);
     if (g.h1 <= 0 || g.w1 <= 0) { g.bad = 1; return; }
     g.inv1 = (float)(1.0 / scale);
-    g.mode1y = resize_mode(g.h1, g.ch);
-    g.mode1x = resize_mode(g.w1, g.cw);
+    const bool short1 = g.h1 + g.w1 <= kAtenVectorizedMaxHW;
+    g.mode1y = resize_mode(g.h1, g.ch, short1);
+    g.mode1x = resize_mode(g.w1, g.cw, short1);
     g.pad_t = g.pad_l = 0;
     g.hp = g.h1;
     g.wp = g.w1;
@@ -68,8 +80,8 @@ __device__ void make_geom(const long long* box, int H, int W, int target, CropGe
         g.wp = g.w1 + g.pad_l + pad_r;
     }
     if (g.hp <= 0 || g.wp <= 0) { g.bad = 1; return; }
-    g.mode2y = resize_mode(target, g.hp);
-    g.mode2x = resize_mode(target, g.wp);
+    g.mode2y = resize_mode(target, g.hp, true);                        // in / out is exactly 1 or 0.5 there: the shortcuts
+    g.mode2x = resize_mode(target, g.wp, true);                        // and the floor agree, whichever kernel runs
     g.s2y = (float)g.hp / (float)target;                               // scales not given: in / out
     g.s2x = (float)g.wp / (float)target;
 }

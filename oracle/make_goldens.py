@@ -468,6 +468,25 @@ def gen_crop():
     print("crop: images", tuple(out["images"].shape), "M[0]", out["M"][0].tolist())
 
 
+def gen_crop_sizes():
+    """CropResizePad(target_size=56) itself on the box list of the crop stage's GPU tests (gigapose_testing/crop_aten.py:
+    gpu_boxes, the boxes it refuses at 56 removed) and a one-channel index image of 97 x 131: closes the loop between the
+    ATen chain of crop_aten.py, a restatement of ten reference lines, and those lines.  The long sides whose scale has
+    two roundings are the same at 56 as at 224 (the scale differs by a factor of 4, exact in binary)."""
+    ref_shim.install()
+    from src.utils.crop import CropResizePad
+
+    from gigapose_testing import crop_aten
+
+    H, W = crop_aten.GPU_FRAME
+    boxes, _ = crop_aten.gpu_boxes(56)
+    image = crop_aten.index_image(H, W)
+    out = CropResizePad(target_size=56)(torch.from_numpy(boxes), images=torch.from_numpy(image)[None].expand(len(boxes), -1, -1, -1))
+    np.savez_compressed(os.path.join(GOLD, "crop_sizes.npz"), images=out["images"].numpy(), M=out["M"].numpy(), boxes=boxes,
+                        input_checksum=np.float64(image.astype(np.float64).sum() + boxes.sum()))
+    print("crop_sizes: images", tuple(out["images"].shape), "file", os.path.getsize(os.path.join(GOLD, "crop_sizes.npz")), "bytes")
+
+
 def gen_bop_csv():
     """The reference's BOP writer (src/utils/inout.py:278-367) on synthetic per-batch npz files, for an LM-O-named
     and a plain dataset: the csv texts are the golden."""
@@ -511,7 +530,7 @@ def gen_signatures():
     print("signatures:", len(sigs), "classes; model config:", cfg["_target_"])
 
 
-STAGES = {"signatures": gen_signatures, "bop_csv": gen_bop_csv, "val": gen_val, "matcher": gen_matcher, "matcher_variants": gen_matcher_variants, "ist": gen_ist, "pose": gen_pose, "pose_scored": gen_pose_scored, "pose_edges": gen_pose_edges, "e2e": gen_e2e, "crop": gen_crop,
+STAGES = {"signatures": gen_signatures, "bop_csv": gen_bop_csv, "val": gen_val, "matcher": gen_matcher, "matcher_variants": gen_matcher_variants, "ist": gen_ist, "pose": gen_pose, "pose_scored": gen_pose_scored, "pose_edges": gen_pose_edges, "e2e": gen_e2e, "crop": gen_crop, "crop_sizes": gen_crop_sizes,
           "matcher_big": lambda: gen_matcher_big(["match_cfg2", "match_cfg3"]), "matcher_cfg5": lambda: gen_matcher_big(["match_cfg5"]), "e2e_cfg2": lambda: gen_e2e("e2e_cfg2"), "e2e_cfg3": lambda: gen_e2e("e2e_cfg3"),
           "e2e_cfg2_f64": lambda: gen_e2e_f64("e2e_cfg2"), "e2e_cfg3_f64": lambda: gen_e2e_f64("e2e_cfg3"), "e2e_f64": lambda: gen_e2e_f64("e2e")}
 

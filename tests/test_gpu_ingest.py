@@ -114,6 +114,35 @@ def test_rle_route_equals_dense_route_bit_for_bit(seed, H, W, D, target):
         check_scan_and_decode(counts, offsets, case["masks"])
 
 
+@pytest.mark.parametrize("target", [224, 37])
+def test_rle_route_and_frame_ingest_equal_the_dense_route_on_the_defect_sizes(target):
+    """The box list of the crop tests against ATen (gigapose_testing/crop_aten.py: the long sides whose scale has two roundings,
+    the doubled / kept extents on either side of ATen's kernel choice, clamped, identity and 2x boxes): the run-length kernel
+    and FrameIngest around it write the dense kernel's bits -- which tests/test_gpu_crop.py holds to ATen at these boxes."""
+    from gigapose_amd.crop import DetectionPreprocessor
+    from gigapose_amd.ingest import FrameIngest, RleDetectionPreprocessor, mask_to_rle_counts
+    from gigapose_testing import crop_aten
+
+    case = crop_aten.gpu_case(target)
+    H, W = crop_aten.GPU_FRAME
+    dense, rle, (counts, offsets) = both_routes(case, target)
+    assert_same_bits(dense, rle)
+    boxes = case["boxes"]
+    dets = [[dict(bbox=[int(b[0]), int(b[1]), int(b[2] - b[0]), int(b[3] - b[1])], category_id=1, score=0.5, time=0.05,
+                  segmentation=dict(counts=mask_to_rle_counts(m).tolist(), size=[H, W])) for b, m in zip(boxes, case["masks"])]]
+    batch = FrameIngest(target_size=target)(case["rgb"], np.eye(3, dtype=np.float32)[None], [dict(scene_id=1, view_id=1)], dets)
+    for key in ("tar_img", "tar_mask", "tar_M"):
+        assert torch.equal(getattr(batch, key), dense[key]), key
+    # a refused box among them: both routes name it, in the same words
+    bad = dict(case, boxes=np.concatenate([boxes[:2], case["refused"][-1:], boxes[2:4]]), masks=case["masks"][:5], im_id=case["im_id"][:5])
+    c5, o5 = encode(bad["masks"])
+    with pytest.raises(ValueError, match="detection 2 has an empty / out-of-frame box") as e_dense:
+        DetectionPreprocessor(target_size=target)(_t(bad["rgb"]), _t(bad["masks"]), _t(bad["boxes"]), _t(bad["im_id"]))
+    with pytest.raises(ValueError, match="detection 2 has an empty / out-of-frame box") as e_rle:
+        RleDetectionPreprocessor(target_size=target)(_t(bad["rgb"]), _t(c5), _t(o5), _t(bad["boxes"]), _t(bad["im_id"]))
+    assert str(e_dense.value).split(": ", 1)[1] == str(e_rle.value).split(": ", 1)[1]
+
+
 def runs_in_span(counts, H, x0, x1):
     """List entries a block has to look at for the columns [x0, x1): prefix sums in (x0*H, x1*H - 1]."""
     cum = np.cumsum(counts.astype(np.int64))

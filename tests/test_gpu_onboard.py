@@ -156,6 +156,48 @@ def test_explicit_boxes_equal_the_existing_crop_kernel(classes):
     assert_bits(out["M"], ref["M"], "M")
 
 
+@pytest.mark.parametrize("target", [224, 37])
+def test_onboarder_equals_the_dense_crop_kernel_on_the_defect_sizes(target):
+    """The box list of the crop tests against ATen (gigapose_testing/crop_aten.py) through gpo_crop_templates: explicit boxes for
+    the whole list, and RenderedTemplates (alpha boxes) for the boxes that lie inside the frame -- the dense kernel's bits, which
+    tests/test_gpu_crop.py holds to ATen at these boxes.  A refused box is named and its outputs stay untouched."""
+    from gigapose_amd.crop import CropResizePad
+    from gigapose_amd.onboard import RenderedTemplates, TemplateOnboarder
+    from gigapose_testing import crop_aten
+
+    H, W = crop_aten.GPU_FRAME
+    boxes, refused = crop_aten.gpu_boxes(target)
+    inside = np.asarray([b for b in boxes if b[2] <= W and b[3] <= H], np.int64)
+    assert len(inside) >= 30
+    mean, std = torch.tensor(syn.CLIP_MEAN).view(3, 1, 1), torch.tensor(syn.CLIP_STD).view(3, 1, 1)
+
+    def dense(rgba, bx):
+        planar = (torch.from_numpy(rgba).permute(0, 3, 1, 2).float() / 255).contiguous()     # the division on the CPU: IEEE
+        ref = CropResizePad(target_size=target)(_t(bx), planar.to(DEV))
+        images = ref["images"].cpu()
+        return ((images[:, :3] - mean) / std).contiguous(), images[:, 3].contiguous(), ref["M"]
+
+    # explicit boxes, every box of the list, on renders whose alpha covers more than the box
+    rgba = renders.renders_with_boxes(71, H, W, [(0, 0, W, H)] * len(boxes))
+    out = TemplateOnboarder(target_size=target)(_t(rgba), boxes=boxes, out=nan_outputs(len(boxes), target))
+    rgb, mask, M = dense(rgba, boxes)
+    assert_bits(out["rgb"], rgb, "rgb"), assert_bits(out["mask"], mask, "mask"), assert_bits(out["M"], M, "M")
+    # the alpha boxes: RenderedTemplates on renders drawn for the boxes inside the frame
+    rgba = renders.renders_with_boxes(72, H, W, inside)
+    item = RenderedTemplates([(rgba, renders.object_poses(1, len(inside)))], device=DEV, target_size=target)[0]
+    rgb, mask, M = dense(rgba, inside)
+    assert_bits(item.rgb, rgb, "rgb"), assert_bits(item.mask, mask, "mask"), assert_bits(item.M, M, "M")
+    # a refused box in the middle
+    bx = np.concatenate([boxes[:2], refused[-1:], boxes[2:4]])
+    bufs = nan_outputs(5, target)
+    with pytest.raises(ValueError, match=r"template 2 has an empty / out-of-frame box, or its box scales to an empty crop"):
+        TemplateOnboarder(target_size=target)(_t(rgba[:5]), boxes=bx, out=bufs)
+    keep = [0, 1, 3, 4]
+    rgb, mask, M = dense(rgba[keep], bx[keep])
+    assert_bits(bufs["rgb"][keep], rgb, "rgb"), assert_bits(bufs["mask"][keep], mask, "mask"), assert_bits(bufs["M"][keep], M, "M")
+    assert all(bool(torch.isnan(bufs[key][2]).all()) for key in ("rgb", "mask", "M")), "the refused template's outputs were written"
+
+
 def test_word_index_past_2_to_31():
     """7000 renders at 480 x 640 are 2.15e9 pixels (8.6 GB): the last render lies past a 32-bit word index, every render after
     the 1748th past a 32-bit byte offset.  The batch is zeros made on the device; only the first and the last render are real."""
