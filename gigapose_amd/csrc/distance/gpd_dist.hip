@@ -18,6 +18,7 @@
 #include "gigapose_dist.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpd
 #include "../gp_front.h"
+#include "../gp_root.h"    // root(): the correctly rounded square root, the library's one fused operation (the header)
 
 namespace {
 
@@ -32,19 +33,6 @@ constexpr u64 kBadKey = ~0ull;
 static_assert(kTile == kChunk, "the diameter kernel pairs query chunks with staged tiles");
 
 __device__ __forceinline__ bool finite(double x) { return fabs(x) <= DBL_MAX; }
-
-// the correctly rounded square root: the compiler's root and one correction step, the library's one fused operation (the header)
-__device__ __forceinline__ double root(double x)
-{
-    if (!(x > 0.0 && x < (double)INFINITY)) return sqrt(x);
-    const bool small = x < 0x1p-500;
-    const double xs = small ? x * 0x1p512 : x;
-    double r = sqrt(xs);
-    const double lo = __longlong_as_double(__double_as_longlong(r) - 1), hi = __longlong_as_double(__double_as_longlong(r) + 1);
-    if (fma(lo, r, -xs) >= 0.0) r = lo;
-    else if (fma(r, hi, -xs) < 0.0) r = hi;
-    return small ? r * 0x1p-256 : r;
-}
 
 struct Rows {
     double m[12];

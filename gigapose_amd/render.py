@@ -14,7 +14,8 @@ gigapose_testing/raster_ref.py; tests/test_gpu_render.py holds the kernels to it
   MeshTemplates                         drop-in for model.template_datasets[name], beside onboard.RenderedTemplates
   save_renders(out_dir, rgba, depth)    {view:06d}.png + {view:06d}_depth.png, the reference's layout; onboard.load_renders reads it
 Textured models (YCB-V, HB) are drawn by texture.py (libgigapose_texture.so), which takes gpr_project's and gpr_raster's output and
-resolves it through a mip-mapped texture; this module stays with vertex colours.  Out of scope here: shading other than ambient, near-plane clipping (a triangle with a vertex behind znear is
+resolves it through a mip-mapped texture; models with neither colour nor texture (T-LESS, ITODD) by shade.py (libgigapose_shade.so),
+which lights them; this module stays with vertex colours.  Out of scope here: shading other than ambient, near-plane clipping (a triangle with a vertex behind znear is
 dropped and counted), anti-aliasing, big-endian PLY, generating the icosphere poses (the caller passes them).  There is no CPU
 fallback: the kernels need the GPU, a missing library is an error.
 """
