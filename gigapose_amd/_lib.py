@@ -292,3 +292,7 @@ def i(v):
 
 def f(v):
     return ctypes.c_float(float(v))
+
+
+def d(v):
+    return ctypes.c_double(float(v))

@@ -3,12 +3,11 @@
 // degrees of freedom a silhouette holds.  The reference has no such stage; the header's definitions are the contract.
 // mask_moments_kernel: one workgroup per detection, the runs of ones strided over its threads, every run summed in closed form
 // (head segment, full columns, tail segment): no pixel is visited.
-// moments_kernel has the shape of counts_kernel (verify/gpv_verify.hip), which walks the same keys the same way: grid (chunk of
-// 4096 box pixels, pair); a workgroup whose chunk lies beyond the pair's clamped box returns before it reads a key.  The box is
-// walked row by row, 256 consecutive box pixels per step, so a wave's 8-byte key loads are contiguous within a row.  A thread
-// keeps the eight counters of its 16 pixels in registers, then wave shuffles, LDS, and one atomic add of int64 per counter that
-// is not 0 per workgroup that saw a covered pixel.  The mask value of a COVERED pixel is the parity of its rank among the
-// detection's prefix sums: a bisection of the pair's slice.
+// moments_kernel walks the pair's box as gp_key_walk.h states it: grid (chunk of 4096 box pixels, pair); the pair rules are judged
+// first (a missing or bad mask sets its bit even for an empty box), then a workgroup whose chunk lies beyond the pair's clamped
+// box returns before it reads a key.  A thread keeps the eight counters of its 16 pixels in registers, then the header's wave and
+// workgroup sums, and one atomic add of int64 per counter that is not 0 per workgroup that saw a covered pixel.  The mask value
+// of a COVERED pixel is the parity of its rank among the detection's prefix sums: a bisection of the pair's slice.
 // update_kernel: one thread per pair -- the exact integer comparison of two intersections over union, the shape values, the
 // rational turn, Heron's step for the scale, the shift; the new pose as f64 and f32.  No square root, no transcendental.
 // Only integers are merged; no float atomics.  gigapose_testing/maskfit_ref.py restates the arithmetic; the two agree bit for
@@ -19,21 +18,13 @@
 #include "gigapose_maskfit.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpm
 #include "../gp_front.h"
-#include "../gp_rle_scan.h"
+#include "../gp_key_walk.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPix = 16;                      // box pixels of a thread
-constexpr int kChunk = kThreads * kPix;       // box pixels of a workgroup
 constexpr int kLive = 8;                      // the counters of a pair's row that are written
 constexpr int kMoments = 6;                   // n, sum x, y, xx, xy, yy
-constexpr long long kMaxPixels = 1ll << 22;
 constexpr int kMaxSide = 16384;
-constexpr u64 kEmptyKey = ~0ull;
-constexpr double kInf = (double)INFINITY;
 static_assert(GPM_ROW == 16 && GPM_MASK_ROW == kLive && GPM_INTER == kMoments && GPM_EDGE == kLive - 1, "the layout of a row of moments");
 
 __device__ __forceinline__ long long s1(long long m) { return m * (m + 1) / 2; }                 // 0 + 1 + .. + m;  0 for m = -1
@@ -63,29 +54,6 @@ __device__ __forceinline__ void add_columns(long long (&v)[kMoments], long long 
     v[5] += c * s2(H - 1);
 }
 
-// the sum over the workgroup of each v[i], in thread i < kCount (other threads return 0); one barrier
-template <int kCount>
-__device__ __forceinline__ long long workgroup_sum(long long (&v)[kCount], long long (&part)[kWaves][kLive])
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < kCount; ++i) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) v[i] += __shfl_xor(v[i], w, 64);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kCount; ++i) part[tid >> 6][i] = v[i];
-    }
-    __syncthreads();
-    long long out = 0;
-    if (tid < kCount) {
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) out += part[w][tid];
-    }
-    return out;
-}
-
 // grid (D).  mm (D,8), mstatus (D): every entry is written
 __global__ __launch_bounds__(kThreads) void mask_moments_kernel(const int* __restrict__ cum, const int* __restrict__ offsets, int total,
                                                                 int H, int W, long long* __restrict__ mm, int* __restrict__ mstatus)
@@ -93,7 +61,7 @@ __global__ __launch_bounds__(kThreads) void mask_moments_kernel(const int* __res
     __shared__ long long part[kWaves][kLive];
     const int d = blockIdx.x, tid = threadIdx.x;
     int lo, hi;
-    const bool good = list_range(offsets, d, total, lo, hi) && cum[hi - 1] == H * W;    // uniform over the workgroup
+    const bool good = mask_slice(offsets, d, (int)gridDim.x, total, cum, H, W, lo, hi);  // uniform over the workgroup
     if (tid == 0) mstatus[d] = good ? 0 : GPM_BAD_MASK;
     if (!good) {
         if (tid < GPM_MASK_ROW) mm[GPM_MASK_ROW * (size_t)d + tid] = 0;
@@ -115,20 +83,9 @@ __global__ __launch_bounds__(kThreads) void mask_moments_kernel(const int* __res
         add_segment(v, xb, 0, yb);
         if (xb - xa >= 2) add_columns(v, xa + 1, xb - 1, H);
     }
-    const long long sum = workgroup_sum<kMoments>(v, part);
-    if (tid < GPM_MASK_ROW) mm[GPM_MASK_ROW * (size_t)d + tid] = tid < kMoments ? sum : 0;
-}
-
-// #{i in [lo, hi) : cum[i] <= p} for a non-decreasing cum; every index read lies in [lo, hi)
-__device__ __forceinline__ int rank_of(const int* __restrict__ cum, int lo, int hi, int p)
-{
-    int a = lo, b = hi;
-    while (a < b) {
-        const int mid = a + ((b - a) >> 1);
-        if (cum[mid] <= p) a = mid + 1;
-        else b = mid;
-    }
-    return a - lo;
+    wave_totals(v, part);
+    __syncthreads();
+    if (tid < GPM_MASK_ROW) mm[GPM_MASK_ROW * (size_t)d + tid] = tid < kMoments ? workgroup_total(part, tid) : 0;
 }
 
 // grid (ceil(H*W / 4096), N).  rows (N,16), status (N): zeroed by the caller
@@ -143,28 +100,22 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const u64* __restrict
     int bad = 0, lo = 0, hi = 0;
     const int d = det[n];
     if (d < 0) bad = GPM_NO_MASK;
-    else if (d >= D || !list_range(offsets, d, total, lo, hi) || cum[hi - 1] != H * W) bad = GPM_BAD_MASK;
+    else if (!mask_slice(offsets, d, D, total, cum, H, W, lo, hi)) bad = GPM_BAD_MASK;
     if (bad) {
         if (tid == 0 && blockIdx.x == 0) atomicOr(status + n, bad);
         return;
     }
-    const int* bx = box + 4 * (size_t)n;
-    const int x0 = max(bx[0], 0), y0 = max(bx[1], 0), x1 = min(bx[2], W - 1), y1 = min(bx[3], H - 1);
-    if (x1 < x0 || y1 < y0) return;
-    const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);  // <= H*W <= 2^22
-    const int first = blockIdx.x * kChunk;                  // < 2^22 + 4096
-    if (first >= area) return;                              // beyond the box: no key has been read
+    BoxWalk walk;
+    if (!walk.open(box, n, H, W)) return;                   // no key has been read
+    const int x0 = walk.x0, y0 = walk.y0, x1 = walk.x1, y1 = walk.y1;
     const bool ex0 = x0 > 0, ey0 = y0 > 0, ex1 = x1 < W - 1, ey1 = y1 < H - 1;   // the box's edges that are not the frame's
     const u64* keys = vis + (size_t)n * H * W;
 
     long long v[kLive];
 #pragma unroll
     for (int i = 0; i < kLive; ++i) v[i] = 0;
-    for (int s = 0; s < kPix; ++s) {
-        const int idx = first + s * kThreads + tid;
-        if (idx >= area) break;
-        const int row = idx / bw, px = x0 + (idx - row * bw), py = y0 + row;
-        if (keys[(size_t)py * W + px] == kEmptyKey) continue;
+    walk.for_each(W, [&](int px, int py, size_t at) {
+        if (keys[at] == kEmptyKey) return;
         const long long x = px, y = py;                     // < 16384: a product below 2^28
         v[0] += 1;
         v[1] += x;
@@ -174,10 +125,14 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const u64* __restrict
         v[5] += y * y;
         v[GPM_INTER] += rank_of(cum, lo, hi, px * H + py) & 1;                  // px*H + py < H*W <= 2^22
         v[GPM_EDGE] += ((px == x0 && ex0) || (px == x1 && ex1) || (py == y0 && ey0) || (py == y1 && ey1)) ? 1 : 0;
+    });
+    wave_totals(v, part);
+    __syncthreads();
+    if (tid < kLive) {
+        const long long sum = workgroup_total(part, tid);
+        // a counter that is not 0 belongs to a workgroup that saw a covered pixel
+        if (sum) add_to_row(rows, GPM_ROW, n, tid, sum);
     }
-    const long long sum = workgroup_sum<kLive>(v, part);
-    // a counter that is not 0 belongs to a workgroup that saw a covered pixel; the result is not used
-    if (tid < kLive && sum) atomicAdd(reinterpret_cast<u64*>(rows) + GPM_ROW * (size_t)n + tid, (u64)sum);
 }
 
 struct Shape {

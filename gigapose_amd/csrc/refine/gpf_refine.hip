@@ -2,11 +2,11 @@
 // with same-pixel association on the render library's z-buffer of 64-bit keys.
 //   reference: the role of src/megapose/inference/icp_refiner.py (render, compare with the measured depth, move the pose, keep
 //   the input on failure); nothing of it is restated here, the header's definitions are the contract.
-// accumulate_kernel, grid (chunk of 4096 box pixels, pair): a workgroup whose chunk lies beyond the pair's clamped box returns
-// before it reads a key.  The box is walked row by row, 256 consecutive box pixels per step, so a wave's 8-byte key loads are
-// contiguous within a row.  A thread keeps the 30 integer sums of its 16 pixels in registers (every term is quantised before it
-// is added), then wave shuffles, LDS, and ONE 32-lane atomic add of int64 into the pair's 256-byte row per workgroup that saw a
-// covered pixel, at most one atomic OR for the status.  No float atomics.
+// accumulate_kernel walks the pair's box as gp_key_walk.h states it: grid (chunk of 4096 box pixels, pair); a workgroup whose chunk
+// lies beyond the pair's clamped box returns before it reads a key, or the pair's frame.  A thread keeps the 30 integer sums of its
+// 16 pixels in registers (every term is quantised before it is added), then the header's wave and workgroup sums, and ONE 32-lane
+// atomic add of int64 into the pair's 256-byte row per workgroup that saw a covered pixel, at most one atomic OR for the status.
+// No float atomics.
 // update_kernel: one thread per pair -- 6 x 6 LDL^T, the Cayley transform, the new pose as f64 and f32.
 // No square root and no transcendental function.  gigapose_testing/refine_ref.py restates the arithmetic in numpy; the two agree
 // bit for bit.  The host-side plumbing is gp_front.h's.  This library links no object of the other libraries and exports only
@@ -17,19 +17,12 @@
 #include "gigapose_refine.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpf
 #include "../gp_front.h"
+#include "../gp_key_walk.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPix = 16;                      // box pixels of a thread
-constexpr int kChunk = kThreads * kPix;       // box pixels of a workgroup
 constexpr int kTerms = 28;                    // 21 + 6 + 1
 constexpr int kLive = 30;                     // + covered, count
-constexpr long long kMaxPixels = 1ll << 22;
-constexpr u64 kEmptyKey = ~0ull;
-constexpr double kInf = (double)INFINITY;
 static_assert(GPF_SUMS == 32 && GPF_SUM_COUNT == kLive - 1 && GPF_SUM_EE == kTerms - 1, "the layout of a row of sums");
 
 // (int64) rint(v) for |v| < 2^51: v + 1.5 * 2^52 is v rounded half to even to an integer, held in the low bits of the sum
@@ -63,15 +56,11 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const u64* __restr
                                                               const double* __restrict__ scale, int H, int W, long long* __restrict__ sums,
                                                               int* __restrict__ status)
 {
-    __shared__ long long part[kWaves][GPF_SUMS];
+    __shared__ long long part[kWaves][kLive];
     __shared__ int bad_part[kWaves];
     const int n = blockIdx.y, tid = threadIdx.x;
-    const int* bx = box + 4 * (size_t)n;
-    const int x0 = max(bx[0], 0), y0 = max(bx[1], 0), x1 = min(bx[2], W - 1), y1 = min(bx[3], H - 1);
-    if (x1 < x0 || y1 < y0) return;                         // uniform over the workgroup, like every return below
-    const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);  // <= H*W <= 2^22
-    const int first = blockIdx.x * kChunk;                  // < 2^22 + 4096
-    if (first >= area) return;                              // beyond the box: nothing has been read but the box
+    BoxWalk walk;
+    if (!walk.open(box, n, H, W)) return;                   // uniform over the workgroup, like every return below; no status is set
     const int fr = frame[n];
     if (fr < 0 || fr >= M) {
         if (tid == 0 && blockIdx.x == 0) atomicOr(status + n, GPF_BAD_INDEX);
@@ -90,18 +79,14 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const u64* __restr
 #pragma unroll
     for (int i = 0; i < kLive; ++i) acc[i] = 0;
     int bad = 0;
-    for (int s = 0; s < kPix; ++s) {
-        const int idx = first + s * kThreads + tid;
-        if (idx >= area) break;
-        const int row = idx / bw, px = x0 + (idx - row * bw), py = y0 + row;
-        const size_t at = (size_t)py * W + px;
+    walk.for_each(W, [&](int px, int py, size_t at) {
         const u64 key = keys[at];
-        if (key == kEmptyKey) continue;
+        if (key == kEmptyKey) return;
         acc[GPF_SUM_COVERED] += 1;
         const unsigned f = (unsigned)(key & 0xffffffffull);
         if (f >= (unsigned)F) {
             bad |= GPF_BAD_INDEX;
-            continue;
+            return;
         }
         const double zr = (double)__uint_as_float((unsigned)(key >> 32));
         const double dm = (double)dmap[at];
@@ -111,9 +96,9 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const u64* __restr
         const double mm = (m0 * m0 + m1 * m1) + m2 * m2;
         if (!(mm < kInf)) {
             bad |= GPF_BAD_INDEX;
-            continue;
+            return;
         }
-        if (!(dm > 0.0 && dm < kInf && fabs(r) <= gt && mm > 0.0)) continue;
+        if (!(dm > 0.0 && dm < kInf && fabs(r) <= gt && mm > 0.0)) return;
         const double b = ((double)py - k5) / k4;
         const double a = (((double)px - k2) - k1 * b) / k0;
         const double q0 = a * zr, q1 = b * zr, q2 = zr;
@@ -135,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const u64* __restr
         keep = keep && (ee <= GPF_TERM_MAX);
         if (!keep) {
             bad |= GPF_RANGE;
-            continue;
+            return;
         }
         acc[GPF_SUM_COUNT] += 1;
         int o = 0;
@@ -147,27 +132,15 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const u64* __restr
 #pragma unroll
         for (int i = 0; i < 6; ++i) acc[GPF_SUM_RHS + i] += quantise(h[i] * e);
         acc[GPF_SUM_EE] += quantise(ee);
-    }
-#pragma unroll
-    for (int i = 0; i < kLive; ++i) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) acc[i] += __shfl_xor(acc[i], w, 64);
-    }
+    });
+    wave_totals(acc, part);
 #pragma unroll
     for (int w = 32; w >= 1; w >>= 1) bad |= __shfl_xor(bad, w, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kLive; ++i) part[tid >> 6][i] = acc[i];
-        part[tid >> 6][30] = 0, part[tid >> 6][31] = 0;
-        bad_part[tid >> 6] = bad;
-    }
+    if ((tid & 63) == 0) bad_part[tid >> 6] = bad;
     __syncthreads();
     if (tid < GPF_SUMS) {
-        long long covered = 0, v = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) covered += part[w][GPF_SUM_COVERED], v += part[w][tid];
-        // one wave instruction: 32 lanes, one int64 each, into the pair's 256-byte row; the result is not used
-        if (covered) atomicAdd(reinterpret_cast<u64*>(sums) + GPF_SUMS * (size_t)n + tid, (u64)v);
+        // one wave instruction: 32 lanes, one int64 each (lanes 30 and 31 add 0), into the pair's 256-byte row
+        if (workgroup_total(part, GPF_SUM_COVERED)) add_to_row(sums, GPF_SUMS, n, tid, tid < kLive ? workgroup_total(part, tid) : 0);
         if (tid == 0) {
 #pragma unroll
             for (int w = 1; w < kWaves; ++w) bad |= bad_part[w];

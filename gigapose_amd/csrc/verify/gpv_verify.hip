@@ -2,13 +2,13 @@
 // with the sensor's depth and with the detection's run-length mask -- what a caller chooses among a detection's hypotheses on.
 //   reference: the role of the multi-hypothesis refiners (n_pose_hypotheses: 5, src/megapose/utils/load_model.py:27-45); nothing
 //   of them is restated here, the header's definitions are the contract.
-// counts_kernel has the shape of accumulate_kernel (refine/gpf_refine.hip), which walks the same keys the same way: grid (chunk of
-// 4096 box pixels, pair); a workgroup whose chunk lies beyond the pair's clamped box returns before it reads a key.  The box is
-// walked row by row, 256 consecutive box pixels per step, so a wave's 8-byte key loads and 4-byte depth loads are contiguous
-// within a row.  A thread keeps the ten counters of its 16 pixels in registers (nine of them 32-bit: a wave's total is at most
-// 1024), then wave shuffles, LDS, and one atomic add of int64 per counter that is not 0 per workgroup that saw a covered or a
-// masked pixel.  The mask value of a pixel is the parity of its rank among the detection's prefix sums: a bisection of the
-// pair's slice per pixel (the lanes of a wave share the list but not the pixel index, which moves by H from lane to lane).
+// counts_kernel walks the pair's box as gp_key_walk.h states it: grid (chunk of 4096 box pixels, pair); the pair rules are judged
+// first (a bad frame or mask sets its bit even for an empty box), then a workgroup whose chunk lies beyond the pair's clamped box
+// returns before it reads a key.  A wave's 8-byte key loads and 4-byte depth loads are contiguous within a row.  A thread keeps
+// the ten counters of its 16 pixels in registers (nine of them 32-bit: a wave's total is at most 1024), then the header's wave
+// and workgroup sums, and one atomic add of int64 per counter that is not 0 per workgroup that saw a covered or a masked pixel.
+// The mask value of a pixel is the parity of its rank among the detection's prefix sums: a bisection of the pair's slice per BOX
+// pixel (the lanes of a wave share the list but not the pixel index, which moves by H from lane to lane).
 // Only integers are merged; no float atomics.  gigapose_testing/verify_ref.py restates the arithmetic in numpy; the two agree bit
 // for bit.  The host-side plumbing is gp_front.h's, list_range is gp_rle_scan.h's.  This library links no object of the other
 // libraries and exports only gpv_* names.
@@ -17,34 +17,14 @@
 #include "gigapose_verify.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpv
 #include "../gp_front.h"
-#include "../gp_rle_scan.h"
+#include "../gp_key_walk.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPix = 16;                      // box pixels of a thread
-constexpr int kChunk = kThreads * kPix;       // box pixels of a workgroup
 constexpr int kClasses = 9;                   // 2 x 4 classes of a covered pixel + uncovered in the mask
 constexpr int kLive = 10;                     // + the residual
-constexpr long long kMaxPixels = 1ll << 22;
-constexpr u64 kEmptyKey = ~0ull;
-constexpr double kInf = (double)INFINITY;
 static_assert(GPV_COUNTS == 16 && GPV_UNCOVERED_IN_MASK == kClasses - 1 && GPV_RESIDUAL == kLive - 1 && 2 * GPV_FRONT + 1 == 7,
               "the layout of a row of counts");
-
-// #{i in [lo, hi) : cum[i] <= p} for a non-decreasing cum; every index read lies in [lo, hi)
-__device__ __forceinline__ int rank_of(const int* __restrict__ cum, int lo, int hi, int p)
-{
-    int a = lo, b = hi;
-    while (a < b) {
-        const int mid = a + ((b - a) >> 1);
-        if (cum[mid] <= p) a = mid + 1;
-        else b = mid;
-    }
-    return a - lo;
-}
 
 // grid (ceil(H*W / 4096), N).  counts (N,16), status (N): zeroed by the caller
 __global__ __launch_bounds__(kThreads) void counts_kernel(const u64* __restrict__ vis, const float* __restrict__ depth, int M,
@@ -66,19 +46,15 @@ __global__ __launch_bounds__(kThreads) void counts_kernel(const u64* __restrict_
         const int d = det[n];
         if (d >= 0) {
             masked = true;
-            if (d >= D || !list_range(offsets, d, total, lo, hi) || cum[hi - 1] != H * W) bad |= GPV_BAD_MASK;
+            if (!mask_slice(offsets, d, D, total, cum, H, W, lo, hi)) bad |= GPV_BAD_MASK;
         }
     }
     if (bad) {
         if (tid == 0 && blockIdx.x == 0) atomicOr(status + n, bad);
         return;
     }
-    const int* bx = box + 4 * (size_t)n;
-    const int x0 = max(bx[0], 0), y0 = max(bx[1], 0), x1 = min(bx[2], W - 1), y1 = min(bx[3], H - 1);
-    if (x1 < x0 || y1 < y0) return;
-    const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);  // <= H*W <= 2^22
-    const int first = blockIdx.x * kChunk;                  // < 2^22 + 4096
-    if (first >= area) return;                              // beyond the box: no key has been read
+    BoxWalk walk;
+    if (!walk.open(box, n, H, W)) return;                   // no key has been read
     const double t = tol[n];
     const u64* keys = vis + (size_t)n * H * W;
     const float* dmap = depth ? depth + (size_t)fr * H * W : nullptr;
@@ -87,16 +63,12 @@ __global__ __launch_bounds__(kThreads) void counts_kernel(const u64* __restrict_
 #pragma unroll
     for (int i = 0; i < kClasses; ++i) acc[i] = 0;
     long long residual = 0;
-    for (int s = 0; s < kPix; ++s) {
-        const int idx = first + s * kThreads + tid;
-        if (idx >= area) break;
-        const int row = idx / bw, px = x0 + (idx - row * bw), py = y0 + row;
-        const size_t at = (size_t)py * W + px;
+    walk.for_each(W, [&](int px, int py, size_t at) {
         const u64 key = keys[at];
         const int in_mask = masked ? (rank_of(cum, lo, hi, px * H + py) & 1) : 0;   // px*H + py < H*W <= 2^22
         if (key == kEmptyKey) {
             acc[GPV_UNCOVERED_IN_MASK] += in_mask;
-            continue;
+            return;
         }
         int cls = GPV_UNMEASURED;
         if (dmap) {
@@ -115,26 +87,15 @@ __global__ __launch_bounds__(kThreads) void counts_kernel(const u64* __restrict_
         const int slot = 2 * cls + in_mask;
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] += (slot == i);
-    }
-#pragma unroll
-    for (int i = 0; i < kClasses; ++i) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) acc[i] += __shfl_xor(acc[i], w, 64);
-    }
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) residual += __shfl_xor(residual, w, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kClasses; ++i) part[tid >> 6][i] = acc[i];
-        part[tid >> 6][GPV_RESIDUAL] = residual;
-    }
+    });
+    long long last[1] = {residual};
+    wave_totals(acc, part);                                 // widened to 64 bits in LDS
+    wave_totals(last, part, GPV_RESIDUAL);
     __syncthreads();
     if (tid < kLive) {
-        long long v = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) v += part[w][tid];
-        // a counter that is not 0 belongs to a workgroup that saw a covered or a masked pixel; the result is not used
-        if (v) atomicAdd(reinterpret_cast<u64*>(counts) + GPV_COUNTS * (size_t)n + tid, (u64)v);
+        const long long v = workgroup_total(part, tid);
+        // a counter that is not 0 belongs to a workgroup that saw a covered or a masked pixel
+        if (v) add_to_row(counts, GPV_COUNTS, n, tid, v);
     }
 }
 

@@ -14,13 +14,13 @@ ADD, ADD-S and the model diameter are gigapose_amd/distances.py (libgigapose_dis
 depend on the summation order).  Out of scope: reading BOP json and depth PNG files (PoseScorer is handed their contents), the bop18 visibility mode, near-plane clipping (an estimate that puts a vertex
 behind the camera drops triangles: it is reported and scores VSD 1).  There is no CPU fallback: a missing library is an error.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from .hypotheses import CameraTable, pose_matrix  # noqa: F401  (pose_matrix is read from here too)
 from .render import MeshRenderer
 
 MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_eval.h: Limits)
@@ -32,10 +32,6 @@ CORRECT_THS = tuple(round(0.05 * i, 2) for i in range(1, 11))    # thresholds of
 MSPD_THS = tuple(float(5 * i) for i in range(1, 11))             # px at W = 640
 _eval = _lib.SideLibrary("libgigapose_eval.so", "gpe")
 EVAL_LIB_PATH, lib, _call = _eval.path, _eval.lib, _eval.call
-
-
-def _d(v):
-    return ctypes.c_double(float(v))
 
 
 # ------------------------------------------------------------------------------------------------ symmetries
@@ -115,7 +111,7 @@ def mssd_mspd(vertices, syms, est, gt, K, zmin=0.0, workspace=None):
     mssd2 = torch.empty(N, dtype=torch.float64, device=est.device)
     mspd2 = torch.empty(N, dtype=torch.float64, device=est.device)
     _call("gpe_mssd_mspd", _lib.ptr(vertices), _lib.i(V), _lib.ptr(syms), _lib.i(S), _lib.ptr(est), _lib.ptr(gt), _lib.ptr(K), _lib.i(N),
-          _d(zmin), _lib.ptr(mssd2), _lib.ptr(mspd2), _lib.ptr(workspace), _lib.stream_ptr())
+          _lib.d(zmin), _lib.ptr(mssd2), _lib.ptr(mspd2), _lib.ptr(workspace), _lib.stream_ptr())
     return mssd2, mspd2
 
 
@@ -160,7 +156,7 @@ def vsd_counts(depth_est, depth_gt, depth_test, frame, ray, ray_index, delta, th
     frame, ray_index = torch.from_numpy(frame).to(dev), torch.from_numpy(ray_index).to(dev)
     counts = torch.empty(N, 2 + T, dtype=torch.int64, device=dev)
     _call("gpe_vsd_counts", _lib.ptr(depth_est), _lib.ptr(depth_gt), _lib.i(N), _lib.ptr(depth_test), _lib.i(M), _lib.ptr(frame),
-          _lib.ptr(ray), _lib.i(R), _lib.ptr(ray_index), _lib.i(H), _lib.i(W), _d(delta), _lib.ptr(thr), _lib.i(T), _lib.ptr(counts),
+          _lib.ptr(ray), _lib.i(R), _lib.ptr(ray_index), _lib.i(H), _lib.i(W), _lib.d(delta), _lib.ptr(thr), _lib.i(T), _lib.ptr(counts),
           _lib.stream_ptr())
     return counts
 
@@ -307,12 +303,6 @@ def read_estimates(path):
     return out
 
 
-def pose_matrix(R, t):
-    P = np.eye(4)
-    P[:3, :3], P[:3, 3] = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
-    return P
-
-
 def group_estimates(targets, gts, estimates):
     """The grouping rule of the scorers (PoseScorer, distances.AddScorer): per target the inst_count highest-scored estimates of
     that object in that image (a tie in score: file order) and every ground truth of it there
@@ -343,20 +333,11 @@ class PoseScorer:
         self.models, self.targets, self.gts = models, list(targets), gts
         self.delta, self.taus, self.znear, self.device = float(delta), tuple(taus), float(znear), device
         self.syms = {o: symmetry_transforms(m, max_sym_disc_step) for o, m in models.items()}
-        self.frames = sorted(cameras)
-        if not self.frames:
-            raise ValueError("PoseScorer: no cameras")
-        depth = [np.asarray(cameras[k]["depth"], np.float32) for k in self.frames]
-        self.H, self.W = depth[0].shape
-        if any(d.shape != (self.H, self.W) for d in depth):
-            raise ValueError("PoseScorer: the depth images differ in size")
-        self._depth_host = np.stack(depth)
-        self._depth = None
-        self.K = {k: np.asarray(cameras[k]["cam_K"], np.float64).reshape(9) for k in self.frames}
-        self._frame_index = {k: i for i, k in enumerate(self.frames)}
+        self._table = CameraTable("PoseScorer", cameras, "required", max_pixels=None)
+        self.frames, self.H, self.W, self.K = self._table.frames, self._table.H, self._table.W, self._table.K
         for t in self.targets:
             key = (int(t["scene_id"]), int(t["im_id"]))
-            if key not in self._frame_index:
+            if key not in self._table.index:
                 raise ValueError(f"PoseScorer: target image {key} has no camera")
             if int(t["obj_id"]) not in models:
                 raise ValueError(f"PoseScorer: target object {t['obj_id']} has no model")
@@ -371,8 +352,7 @@ class PoseScorer:
     def errors(self, estimates):
         """-> [(target, {"mssd" (E,G), "mspd" (E,G), "vsd" (E,G,T), "clipped" (E,G)})] as numpy, E estimates kept x G ground truths."""
         groups = self.pairs(estimates)
-        if self._depth is None:
-            self._depth = torch.from_numpy(self._depth_host).to(self.device)
+        depth = self._table.depth_on(self.device)
         out = [None] * len(groups)
         for obj in sorted({int(t["obj_id"]) for t, _, _ in groups}):
             est, gt, K, frame, where = [], [], [], [], []
@@ -386,13 +366,13 @@ class PoseScorer:
                         est.append(pose_matrix(e["R"], e["t"]))
                         gt.append(pose_matrix(h["cam_R_m2c"], h["cam_t_m2c"]))
                         K.append(self.K[key])
-                        frame.append(self._frame_index[key])
+                        frame.append(self._table.index[key])
             T = len(self.taus)
             if est:
                 m = self.models[obj]
                 est, gt, K = np.stack(est), np.stack(gt), np.stack(K)
                 mssd, mspd = (a.numpy() for a in pose_errors(m["vertices"], self.syms[obj], est, gt, K, self.znear, self.device))
-                vsd = vsd_errors((m["vertices"], m["faces"]), est, gt, K, self._depth, np.asarray(frame), float(m["diameter"]), self.delta,
+                vsd = vsd_errors((m["vertices"], m["faces"]), est, gt, K, depth, np.asarray(frame), float(m["diameter"]), self.delta,
                                  self.taus, self.H, self.W, self.znear, self.device)
                 e_vsd, clipped = vsd["errors"].numpy(), vsd["clipped"].numpy()
             for gi, o, E, G in where:

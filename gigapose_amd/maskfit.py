@@ -23,12 +23,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ingest, refine, render
-from .evaluate import pose_matrix
-from .verify import HypothesisVerifier
+from . import _lib
+from .hypotheses import MAX_PAIRS_PER_CALL, MAX_PIXELS, HypothesisFlow, mask_lists, need_gpu, pack_masks, scan_masks  # (gigapose_maskfit.h: Limits)
 
-MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_maskfit.h: Limits)
-MAX_PIXELS = 1 << 22                                 # H*W
 MAX_SIDE = 16384                                     # H, W: a sum of x*x stays below 2^50
 ROW, MASK_ROW, INTER, EDGE = 16, 8, 6, 7
 BAD_MASK, NO_MASK, FEW, CLIPPED, ROUND, NOT_IMPROVED = 1, 2, 4, 8, 16, 32
@@ -41,10 +38,6 @@ _maskfit = _lib.SideLibrary("libgigapose_maskfit.so", "gpm")
 MASKFIT_LIB_PATH, lib, _call = _maskfit.path, _maskfit.lib, _maskfit.call
 
 
-def _d(v):
-    return ctypes.c_double(float(v))
-
-
 def pixels_per_workgroup():
     return int(lib().gpm_pixels_per_workgroup())
 
@@ -54,22 +47,12 @@ def _frame(who, H, W):
         raise ValueError(f"{who}: {H} x {W} frames (H, W in 1 .. 16384, H*W <= 2^22)")
 
 
-def _lists(who, masks):
-    if not (isinstance(masks, (tuple, list)) and len(masks) == 2):
-        raise ValueError(f"{who}: masks must be (cum, offsets)")
-    cum = _lib.arg(masks[0], torch.int32, (None,), who, "cum")
-    offsets = _lib.arg(masks[1], torch.int32, (None,), who, "offsets")
-    if offsets.shape[0] < 1:
-        raise ValueError(f"{who}: offsets holds D + 1 entries, got none")
-    return cum, offsets
-
-
 @torch.no_grad()
 def mask_moments(masks, H, W):
     """gpm_mask_moments: masks = (cum, offsets), int32 (total,) and (D+1,) on the device as ingest.RleDetectionPreprocessor.scan
     returns them -> mm int64 (D,8): n, sum x, y, xx, xy, yy of each mask, mstatus int32 (D,): BAD_MASK for a bad list."""
     who = "mask_moments"
-    cum, offsets = _lists(who, masks)
+    cum, offsets = mask_lists(who, masks)
     _frame(who, int(H), int(W))
     _lib.on_gpu(who, cum=cum, offsets=offsets)
     D = offsets.shape[0] - 1
@@ -88,7 +71,7 @@ def moments(vis, masks, det, box, out=None):
     who = "moments"
     vis = _lib.arg(vis, torch.int64, (None, None, None), who, "vis")
     N, H, W = vis.shape
-    cum, offsets = _lists(who, masks)
+    cum, offsets = mask_lists(who, masks)
     det = _lib.arg(det, torch.int32, (N,), who, "det")
     box = _lib.arg(box, torch.int32, (N, 4), who, "box")
     if N > MAX_PAIRS_PER_CALL:
@@ -150,13 +133,13 @@ def update(rows, status, mm, det, clipped, K, start, it, last, poses, poses32, b
     given = {} if clipped is None else dict(clipped=clipped)
     _lib.on_gpu(who, rows=rows, status=status, mm=mm, det=det, K=K, start=start, poses=poses, poses32=poses32, best=best, score=score, state=state, **given)
     _call("gpm_update", _lib.ptr(rows), _lib.ptr(status), _lib.ptr(mm), _lib.i(mm.shape[0]), _lib.ptr(det), _lib.ptr(clipped), _lib.ptr(K), _lib.ptr(start),
-          _lib.i(N), _lib.i(it), _lib.i(1 if last else 0), ctypes.c_longlong(int(min_points)), _d(min_elongation), _d(gain), _lib.ptr(poses),
+          _lib.i(N), _lib.i(it), _lib.i(1 if last else 0), ctypes.c_longlong(int(min_points)), _lib.d(min_elongation), _lib.d(gain), _lib.ptr(poses),
           _lib.ptr(poses32), _lib.ptr(best), _lib.ptr(score), _lib.ptr(state), _lib.stream_ptr())
     return poses, poses32, best, score, state
 
 
 # ------------------------------------------------------------------------------------------------ the fitter
-class MaskRefiner:
+class MaskRefiner(HypothesisFlow):
     """The silhouette fit of pose estimates to their detections' masks.
       models   {obj_id: {"vertices" (V,3), "faces" (F,3), "diameter"}}            (what HypothesisVerifier takes)
       cameras  {(scene_id, im_id): {"cam_K" 9, ["size" (H, W)]}}   no depth is needed; the frame size is "size" or the masks'
@@ -185,12 +168,9 @@ class MaskRefiner:
         if box not in ("projected", "frame"):
             raise ValueError(f"{who}: box must be 'projected' or 'frame'")
         _check_step(who, min_points, min_elongation, gain)
-        self.iters, self.box, self.margin, self.znear = int(iters), box, float(margin), float(znear)
+        self.iters = int(iters)
         self.step = dict(min_points=int(min_points), min_elongation=float(min_elongation), gain=float(gain))
-        rgb = {k: {f: v for f, v in c.items() if f != "depth"} for k, c in cameras.items()}
-        # the packing of masks, the cameras and the frame size are HypothesisVerifier's, as they are
-        self._packer = HypothesisVerifier(models, rgb, box=box, margin=margin, znear=znear, pairs_per_call=pairs_per_call, device=device)
-        self.models, self.device = models, device
+        super().__init__(who, models, cameras, "ignored", box, margin, znear, pairs_per_call, device)
 
     @torch.no_grad()
     def refine(self, estimates, masks):
@@ -198,19 +178,10 @@ class MaskRefiner:
         estimates = list(estimates)
         if masks is None:
             raise ValueError(f"{who}: masks are required")
-        pk = self._packer
-        groups = {}
-        for i, e in enumerate(estimates):
-            key, obj = (int(e["scene_id"]), int(e["im_id"])), int(e["obj_id"])
-            if key not in pk._frame_index:
-                raise ValueError(f"{who}: estimate {i}: image {key} has no camera")
-            if obj not in self.models:
-                raise ValueError(f"{who}: estimate {i}: object {obj} has no model")
-            groups.setdefault((obj, pk.K[key].tobytes()), []).append(i)
-        runs, offsets, det_h, _, mask_boxes = pk._masks(who, estimates, masks)
-        if torch.device(self.device).type != "cuda":
-            raise _lib.GigaPoseHipError(f"{who} needs a GPU device (no CPU fallback)")
-        dev, H, W = self.device, pk.H, pk.W
+        groups = self._groups(who, estimates)
+        runs, offsets, det_h, _, mask_boxes = pack_masks(who, estimates, masks, self.table)
+        need_gpu(who, self.device)
+        dev, H, W = self.device, self.H, self.W
         _frame(who, H, W)
         out = [dict(e) for e in estimates]
         if not len(runs):                              # no estimate has a mask
@@ -218,50 +189,22 @@ class MaskRefiner:
                 o.update(maskfit_status=NO_MASK | NOT_IMPROVED, iou_start=0.0, iou=0.0, best_iteration=0, moments=np.zeros(ROW, np.int64),
                          iou_counts=np.asarray([0, 1, 0, 1], np.int64))
             return out
-        offsets_d = torch.from_numpy(offsets).to(dev)      # pack_rle has checked the lists: the scan's error flag is not read
-        lists = (ingest.RleDetectionPreprocessor().scan(torch.from_numpy(runs).to(dev), offsets_d, H, W, torch.zeros(1, dtype=torch.int32, device=dev)), offsets_d)
+        lists = scan_masks(runs, offsets, H, W, dev)
         mm, _ = mask_moments(lists, H, W)
         results = []                                   # (indices, poses, score, state, rows) on the device: read once at the end
-        for (obj, _), idx in sorted(groups.items(), key=lambda kv: kv[1][0]):
-            m = self.models[obj]
-            vertices, faces = _lib.upload(who, dev, _lib.checked(m["vertices"], torch.float32, (None, 3), who, "vertices"),
-                                          _lib.checked(m["faces"], torch.int32, (None, 3), who, "faces"))
-            poses_h = np.stack([pose_matrix(estimates[i]["R"], estimates[i]["t"]) for i in idx])
-            K_h = np.stack([pk.K[(int(estimates[i]["scene_id"]), int(estimates[i]["im_id"]))] for i in idx])
-            if self.box == "frame":
-                box_h = np.tile(np.asarray([0, 0, W - 1, H - 1], np.int32), (len(idx), 1))
-            else:
-                box_h = refine.projected_boxes(m["vertices"], poses_h, K_h, H, W, self.margin)
-                for j, i in enumerate(idx):
-                    if det_h[i] >= 0:
-                        mb = mask_boxes[det_h[i]]
-                        if mb[2] >= mb[0]:              # the mask's box, padded like the projected one
-                            lo = np.clip(np.asarray(mb[:2]) - math.ceil(self.margin), -1, [W, H])
-                            hi = np.clip(np.asarray(mb[2:]) + math.ceil(self.margin), -1, [W, H])
-                            box_h[j] = (min(box_h[j, 0], lo[0]), min(box_h[j, 1], lo[1]), max(box_h[j, 2], hi[0]), max(box_h[j, 3], hi[1]))
-            K9 = render._k9(K_h[0])
-            V, F = vertices.shape[0], faces.shape[0]
-            n = min(len(idx), pk.pairs_per_call)
-            xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
-            vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
-            vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
-            work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
-            for _, a, b in _lib.chunked(len(idx), pk.pairs_per_call):
-                nb = b - a
-                poses = torch.from_numpy(poses_h[a:b]).to(dev)
-                start, poses32 = poses.clone(), poses.to(torch.float32)
-                Kd = torch.from_numpy(np.ascontiguousarray(K_h[a:b])).to(dev)
-                det = torch.from_numpy(np.ascontiguousarray(det_h[idx[a:b]])).to(dev)
-                box = torch.from_numpy(np.ascontiguousarray(box_h[a:b])).to(dev)
-                best, score, state = new_state(nb, dev)
-                clipped = torch.empty(nb, dtype=torch.int32, device=dev)
-                buffers = torch.empty(nb, ROW, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int32, device=dev)
-                for it in range(self.iters + 1):
-                    pxy, pz = render.project(vertices, poses32, K9, self.znear, out=(xy, vdepth))
-                    keys_d, _ = render.raster(pxy, pz, faces, H, W, out=(vis, clipped), workspace=work)
-                    rows, status = moments(keys_d, lists, det, box, out=buffers)
-                    update(rows, status, mm, det, clipped, Kd, start, it, it == self.iters, poses, poses32, best, score, state, **self.step)
-                results.append((idx[a:b], poses, score, state, rows))
+        # the mask's box joins padded like the projected one
+        for ch in self._chunks(who, estimates, groups, det=det_h, mask_boxes=mask_boxes, pad=math.ceil(self.margin)):
+            nb = len(ch.idx)
+            poses = torch.from_numpy(ch.poses).to(dev)
+            start, poses32 = poses.clone(), poses.to(torch.float32)
+            Kd = torch.from_numpy(ch.K).to(dev)
+            best, score, state = new_state(nb, dev)
+            clipped = torch.empty(nb, dtype=torch.int32, device=dev)
+            buffers = torch.empty(nb, ROW, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int32, device=dev)
+            for it in range(self.iters + 1):
+                rows, status = moments(ch.draw(poses32, clipped), lists, ch.det, ch.box, out=buffers)
+                update(rows, status, mm, ch.det, clipped, Kd, start, it, it == self.iters, poses, poses32, best, score, state, **self.step)
+            results.append((ch.idx, poses, score, state, rows))
         for idx, poses, score, state, rows in results:
             poses, score, state, rows = (t.cpu().numpy() for t in (poses, score, state, rows))
             for j, i in enumerate(idx):

@@ -23,11 +23,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, render
-from .evaluate import pose_matrix
+from . import _lib
+from .hypotheses import MAX_PAIRS_PER_CALL, MAX_PIXELS, HypothesisFlow, need_gpu, pose_matrix, projected_boxes  # noqa: F401  (gigapose_refine.h: Limits)
 
-MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_refine.h: Limits)
-MAX_PIXELS = 1 << 22                                 # H*W: the bound on an integer sum
 SUMS, SUM_RHS, SUM_EE, SUM_COVERED, SUM_COUNT = 32, 21, 27, 28, 29
 QUANTUM_BITS = 36
 RANGE, BAD_INDEX, FEW, DEGENERATE, CLIPPED, CONVERGED = 1, 2, 4, 8, 16, 32
@@ -37,10 +35,6 @@ STATUS_BITS = {RANGE: "a pixel was dropped: a term left the range", BAD_INDEX: "
                CLIPPED: "the view drops a triangle", CONVERGED: "the last step was below tol"}
 _refine = _lib.SideLibrary("libgigapose_refine.so", "gpf")
 REFINE_LIB_PATH, lib, _call = _refine.path, _refine.lib, _refine.call
-
-
-def _d(v):
-    return ctypes.c_double(float(v))
 
 
 def pixels_per_workgroup():
@@ -125,31 +119,11 @@ def update(sums, clipped, scale, start, poses, poses32, state, min_points=32, mi
     given = {k: v for k, v in dict(clipped=clipped, start=start).items() if v is not None}
     _lib.on_gpu(who, sums=sums, scale=scale, poses=poses, poses32=poses32, state=state, **given)
     _call("gpf_update", _lib.ptr(sums), _lib.ptr(clipped), _lib.ptr(scale), _lib.ptr(start), _lib.i(N), ctypes.c_longlong(int(min_points)),
-          _d(min_pivot), _d(damping), _d(tol2), _lib.ptr(poses), _lib.ptr(poses32), _lib.ptr(state), _lib.stream_ptr())
+          _lib.d(min_pivot), _lib.d(damping), _lib.d(tol2), _lib.ptr(poses), _lib.ptr(poses32), _lib.ptr(state), _lib.stream_ptr())
     return poses, poses32, state
 
 
-# ------------------------------------------------------------------------------------------------ boxes (host)
-def projected_boxes(vertices, poses, K, H, W, margin):
-    """The bounding box of the model's projected vertices at each pose, padded by `margin` pixels: float64 on the host, floor /
-    ceil, clamped to [-1, W] x [-1, H] (the kernel clamps to the frame).  A pose that puts a vertex at z <= 0 or gives a value
-    that is not finite takes the whole frame.  vertices (V,3), poses (N,4,4), K (N,9) -> int32 (N,4)."""
-    v = np.asarray(vertices, np.float32).astype(np.float64)
-    out = np.zeros((len(poses), 4), np.int32)
-    for n, (P, k) in enumerate(zip(np.asarray(poses, np.float64), np.asarray(K, np.float64).reshape(-1, 9))):
-        p = v @ P[:3, :3].T + P[:3, 3]
-        with np.errstate(all="ignore"):
-            u = (k[0] * p[:, 0] + k[1] * p[:, 1]) / p[:, 2] + k[2]
-            w = (k[4] * p[:, 1]) / p[:, 2] + k[5]
-        if not (np.isfinite(u).all() and np.isfinite(w).all() and (p[:, 2] > 0).all()):
-            out[n] = (0, 0, W - 1, H - 1)
-            continue
-        lo = np.clip(np.floor([u.min() - margin, w.min() - margin]), -1, [W, H])
-        hi = np.clip(np.ceil([u.max() + margin, w.max() + margin]), -1, [W, H])
-        out[n] = (lo[0], lo[1], hi[0], hi[1])
-    return out
-
-
+# ------------------------------------------------------------------------------------------------ the statistics (host)
 def rms_from_sums(sums, scale):
     """sums (N,32) int64 on the host, scale (N,) -> the root mean square point-to-plane distance of the associated pixels in
     model units, float64 (N,): scale * sqrt(sum 27 * 2^-36 / count), numpy's root; NaN where nothing is associated."""
@@ -159,7 +133,7 @@ def rms_from_sums(sums, scale):
 
 
 # ------------------------------------------------------------------------------------------------ the refiner
-class DepthRefiner:
+class DepthRefiner(HypothesisFlow):
     """Point-to-plane ICP of pose estimates against the sensor's depth.
       models   {obj_id: {"vertices" (V,3), "faces" (F,3), "diameter"}}            (what PoseScorer takes)
       cameras  {(scene_id, im_id): {"cam_K" 9, "depth" (H,W) z-depth in the units of the models, 0 = no measurement}}
@@ -188,26 +162,9 @@ class DepthRefiner:
         if box not in ("projected", "frame"):
             raise ValueError(f"{who}: box must be 'projected' or 'frame'")
         _check_step(who, min_points, min_pivot, damping, tol * tol)
-        self.models, self.device = models, device
-        self.iters, self.gate, self.box, self.margin, self.znear = int(iters), float(gate), box, float(margin), float(znear)
+        self.iters, self.gate = int(iters), float(gate)
         self.step = dict(min_points=int(min_points), min_pivot=float(min_pivot), damping=float(damping), tol2=float(tol) * float(tol))
-        self.frames = sorted(cameras)
-        if not self.frames:
-            raise ValueError(f"{who}: no cameras")
-        depth = [np.asarray(cameras[k]["depth"], np.float32) for k in self.frames]
-        self.H, self.W = depth[0].shape
-        if any(d.shape != (self.H, self.W) for d in depth):
-            raise ValueError(f"{who}: the depth images differ in size")
-        if self.H * self.W > MAX_PIXELS:
-            raise ValueError(f"{who}: {self.H} x {self.W} frames (at most 2^22 pixels)")
-        self._depth_host, self._depth = np.stack(depth), None
-        self.K = {k: np.asarray(cameras[k]["cam_K"], np.float64).reshape(9) for k in self.frames}
-        self._frame_index = {k: i for i, k in enumerate(self.frames)}
-        limit = max(1, render.VIS_BYTES_PER_CALL // (self.H * self.W * 8))
-        self.pairs_per_call = max(1, min(int(limit if pairs_per_call is None else pairs_per_call), MAX_PAIRS_PER_CALL))
-        for o, m in models.items():
-            if m.get("diameter") is None or not float(m["diameter"]) > 0:
-                raise ValueError(f"{who}: model {o} needs a positive diameter")
+        super().__init__(who, models, cameras, "required", box, margin, znear, pairs_per_call, device)
 
     @torch.no_grad()
     def refine(self, estimates, boxes=None):
@@ -218,61 +175,27 @@ class DepthRefiner:
             boxes = np.asarray(boxes)
             if boxes.shape != (E, 4) or boxes.dtype.kind not in "iu":
                 raise ValueError(f"{who}: expected boxes integers ({E}, 4), got {boxes.dtype} {boxes.shape}")
-        groups = {}
-        for i, e in enumerate(estimates):
-            key, obj = (int(e["scene_id"]), int(e["im_id"])), int(e["obj_id"])
-            if key not in self._frame_index:
-                raise ValueError(f"{who}: estimate {i}: image {key} has no camera")
-            if obj not in self.models:
-                raise ValueError(f"{who}: estimate {i}: object {obj} has no model")
-            groups.setdefault((obj, self.K[key].tobytes()), []).append(i)
-        if torch.device(self.device).type != "cuda":
-            raise _lib.GigaPoseHipError(f"{who} needs a GPU device (no CPU fallback)")
-        if self._depth is None:
-            self._depth = torch.from_numpy(self._depth_host).to(self.device)
-        dev, H, W = self.device, self.H, self.W
+        groups = self._groups(who, estimates)
+        need_gpu(who, self.device)
+        dev, depth = self.device, self.table.depth_on(self.device)
         results = []                                   # (indices, poses, state, status, sums) on the device: read once at the end
-        for (obj, _), idx in sorted(groups.items(), key=lambda kv: kv[1][0]):
-            m = self.models[obj]
-            vertices, faces = _lib.upload(who, dev, _lib.checked(m["vertices"], torch.float32, (None, 3), who, "vertices"),
-                                          _lib.checked(m["faces"], torch.int32, (None, 3), who, "faces"))
-            c = face_normals(vertices, faces)
-            d = float(m["diameter"])
-            poses_h = np.stack([pose_matrix(estimates[i]["R"], estimates[i]["t"]) for i in idx])
-            keys = [(int(estimates[i]["scene_id"]), int(estimates[i]["im_id"])) for i in idx]
-            K_h = np.stack([self.K[k] for k in keys])
-            if boxes is not None:
-                box_h = np.ascontiguousarray(boxes[idx], np.int32)
-            elif self.box == "frame":
-                box_h = np.tile(np.asarray([0, 0, W - 1, H - 1], np.int32), (len(idx), 1))
-            else:
-                box_h = projected_boxes(m["vertices"], poses_h, K_h, H, W, self.margin)
-            K9 = render._k9(K_h[0])
-            V, F = vertices.shape[0], faces.shape[0]
-            n = min(len(idx), self.pairs_per_call)
-            xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
-            vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
-            vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
-            work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
-            for _, a, b in _lib.chunked(len(idx), self.pairs_per_call):
-                nb = b - a
-                poses = torch.from_numpy(poses_h[a:b]).to(dev)
-                start, poses32 = poses.clone(), poses.to(torch.float32)
-                Kd = torch.from_numpy(np.ascontiguousarray(K_h[a:b])).to(dev)
-                frame = torch.tensor([self._frame_index[k] for k in keys[a:b]], dtype=torch.int32, device=dev)
-                box = torch.from_numpy(np.ascontiguousarray(box_h[a:b])).to(dev)
-                gate = torch.full((nb,), self.gate * d, dtype=torch.float64, device=dev)
-                scale = torch.full((nb,), d, dtype=torch.float64, device=dev)
-                state = torch.zeros(nb, dtype=torch.int32, device=dev)
-                clipped = torch.empty(nb, dtype=torch.int32, device=dev)
-                out = torch.empty(nb, SUMS, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int32, device=dev)
-                for it in range(self.iters + 1):
-                    pxy, pz = render.project(vertices, poses32, K9, self.znear, out=(xy, vdepth))
-                    keys_d, _ = render.raster(pxy, pz, faces, H, W, out=(vis, clipped), workspace=work)
-                    sums, status = accumulate(keys_d, c, poses, Kd, self._depth, frame, box, gate, scale, out=out)
-                    if it < self.iters:
-                        update(sums, clipped, scale, start, poses, poses32, state, **self.step)
-                results.append((idx[a:b], poses, state, status, sums, clipped, d))
+        for ch in self._chunks(who, estimates, groups, boxes):
+            if ch.first:
+                c, d = face_normals(ch.vertices, ch.faces), float(ch.model["diameter"])
+            nb = len(ch.idx)
+            poses = torch.from_numpy(ch.poses).to(dev)
+            start, poses32 = poses.clone(), poses.to(torch.float32)
+            Kd = torch.from_numpy(ch.K).to(dev)
+            gate = torch.full((nb,), self.gate * d, dtype=torch.float64, device=dev)
+            scale = torch.full((nb,), d, dtype=torch.float64, device=dev)
+            state = torch.zeros(nb, dtype=torch.int32, device=dev)
+            clipped = torch.empty(nb, dtype=torch.int32, device=dev)
+            out = torch.empty(nb, SUMS, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int32, device=dev)
+            for it in range(self.iters + 1):
+                sums, status = accumulate(ch.draw(poses32, clipped), c, poses, Kd, depth, ch.frame, ch.box, gate, scale, out=out)
+                if it < self.iters:
+                    update(sums, clipped, scale, start, poses, poses32, state, **self.step)
+            results.append((ch.idx, poses, state, status, sums, clipped, d))
         out = [dict(e) for e in estimates]
         for idx, poses, state, status, sums, clipped, d in results:
             poses, state, status, sums, clipped = (t.cpu().numpy() for t in (poses, state, status, sums, clipped))

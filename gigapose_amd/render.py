@@ -244,6 +244,40 @@ def resolve(vis, xy, vdepth, faces, colours, out=None):
     return rgba, depth
 
 
+class KeyBuffers:
+    """What drawing up to n views of a mesh of V vertices and F faces at H x W needs, allocated once and used chunk after chunk:
+    xy, vdepth, the keys `vis` and gpr_raster's workspace.  .draw(vertices, faces, poses32 (nb <= n, 4, 4), K9, znear, clipped
+    int32 (nb,), written) is project -> raster and returns (keys (nb,H,W), xy, vdepth), views of the buffers."""
+
+    def __init__(self, n, V, F, H, W, device):
+        self.H, self.W = H, W
+        self.xy = torch.empty(n, V, 2, dtype=torch.int32, device=device)
+        self.vdepth = torch.empty(n, V, dtype=torch.float32, device=device)
+        self.vis = torch.empty(n, H, W, dtype=torch.int64, device=device)
+        self.work = torch.empty(max(1, -(-int(lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=device)
+
+    def draw(self, vertices, faces, poses32, K9, znear, clipped):
+        pxy, pz = project(vertices, poses32, K9, znear, out=(self.xy, self.vdepth))
+        keys, _ = raster(pxy, pz, faces, self.H, self.W, out=(self.vis, clipped), workspace=self.work)
+        return keys, pxy, pz
+
+
+def views_step(views_per_call, H, W):
+    """The chunk size of the renderers: by default the keys of one call stay below VIS_BYTES_PER_CALL."""
+    if views_per_call is None:
+        views_per_call = max(1, VIS_BYTES_PER_CALL // (H * W * 8))
+    return max(1, min(int(views_per_call), MAX_VIEWS_PER_CALL))
+
+
+def raise_clipped(who, clipped, F, znear):
+    """The renderers' error for the first view that drops a triangle; one host synchronisation."""
+    bad = torch.nonzero(clipped).flatten().tolist()
+    if bad:
+        raise ValueError(f"{who}: view {bad[0]} drops {int(clipped[bad[0]])} of {F} triangles: a vertex lies behind znear = {znear}, "
+                         f"beyond 16384 px or is not finite (views {bad[:8]}{' ...' if len(bad) > 8 else ''}; there is no "
+                         "near-plane clipping -- on_clipped='ignore' renders what is left)")
+
+
 def template_object_poses(obj_poses, zoom=0.4):
     """A copy of the (N,4,4) object poses with the translation scaled: `template_poses[:, :3, 3] *= 0.4  # zoom to object`
     (src/scripts/render_bop_templates.py:69-70).  The poses themselves (obj_poses_level1.npy, 162 views) come from the caller."""
@@ -285,27 +319,16 @@ class MeshRenderer:
             colours = torch.tensor([colour], dtype=torch.uint8, device=dev).expand(V, 3)
         colours = _lib.on_device(colours, torch.uint8, (V, 3), who, "colours")
         H, W = self.H, self.W
-        if views_per_call is None:
-            views_per_call = max(1, VIS_BYTES_PER_CALL // (H * W * 8))
-        step = max(1, min(int(views_per_call), MAX_VIEWS_PER_CALL))
+        step = views_step(views_per_call, H, W)
         rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
         depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
         clipped = torch.empty(N, dtype=torch.int32, device=dev)
-        n = min(N, step)
-        xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
-        vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
-        vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
-        work = torch.empty(max(1, -(-int(lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
+        buffers = KeyBuffers(min(N, step), V, F, H, W, dev)
         for _, a, b in _lib.chunked(N, step):
-            pxy, pz = project(vertices, poses[a:b], self._K, self.znear, out=(xy, vdepth))
-            keys, _ = raster(pxy, pz, faces, H, W, out=(vis, clipped[a:b]), workspace=work)
+            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, clipped[a:b])
             resolve(keys, pxy, pz, faces, colours, out=(rgba[a:b], depth[a:b]))
         if on_clipped == "raise":
-            bad = torch.nonzero(clipped).flatten().tolist()
-            if bad:
-                raise ValueError(f"{who}: view {bad[0]} drops {int(clipped[bad[0]])} of {F} triangles: a vertex lies behind znear = {self.znear}, "
-                                 f"beyond 16384 px or is not finite (views {bad[:8]}{' ...' if len(bad) > 8 else ''}; there is no "
-                                 "near-plane clipping -- on_clipped='ignore' renders what is left)")
+            raise_clipped(who, clipped, F, self.znear)
         return {"rgba": rgba, "depth": depth, "clipped": clipped}
 
 

@@ -253,29 +253,18 @@ class ShadedMeshRenderer:
             normals = vertex_normals(vertices, faces) if normals is None else _lib.on_device(normals, torch.float64, (V, 3), who, "normals")
         decode, encode = self._on(dev)
         H, W = self.H, self.W
-        if views_per_call is None:
-            views_per_call = max(1, render.VIS_BYTES_PER_CALL // (H * W * 8))
-        step = max(1, min(int(views_per_call), render.MAX_VIEWS_PER_CALL))
+        step = render.views_step(views_per_call, H, W)
         rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
         depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
         clipped = torch.empty(N, dtype=torch.int32, device=dev)
         unlit = torch.empty(N, dtype=torch.int32, device=dev)
-        n = min(N, step)
-        xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
-        vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
-        vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
-        work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
+        buffers = render.KeyBuffers(min(N, step), V, F, H, W, dev)
         for _, a, b in _lib.chunked(N, step):
-            pxy, pz = render.project(vertices, poses[a:b], self._K, self.znear, out=(xy, vdepth))
-            keys, _ = render.raster(pxy, pz, faces, H, W, out=(vis, clipped[a:b]), workspace=work)
+            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, clipped[a:b])
             shade(keys, pxy, pz, faces, colours, vertices, normals, poses[a:b], self._K, self.lights, self.ambient, decode, encode, self.mode,
                   out=(rgba[a:b], depth[a:b], unlit[a:b]))
         if on_clipped == "raise":
-            bad = torch.nonzero(clipped).flatten().tolist()
-            if bad:
-                raise ValueError(f"{who}: view {bad[0]} drops {int(clipped[bad[0]])} of {F} triangles: a vertex lies behind znear = {self.znear}, "
-                                 f"beyond 16384 px or is not finite (views {bad[:8]}{' ...' if len(bad) > 8 else ''}; there is no "
-                                 "near-plane clipping -- on_clipped='ignore' renders what is left)")
+            render.raise_clipped(who, clipped, F, self.znear)
         return {"rgba": rgba, "depth": depth, "clipped": clipped, "unlit": unlit}
 
 

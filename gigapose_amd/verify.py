@@ -22,11 +22,10 @@ error.
 import numpy as np
 import torch
 
-from . import _lib, ingest, refine, render
-from .evaluate import pose_matrix, read_estimates
+from . import _lib, refine
+from .evaluate import read_estimates
+from .hypotheses import MAX_PAIRS_PER_CALL, MAX_PIXELS, HypothesisFlow, mask_lists, need_gpu, pack_masks, scan_masks  # (gigapose_verify.h: Limits)
 
-MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_verify.h: Limits)
-MAX_PIXELS = 1 << 22                                 # H*W
 COUNTS = 16
 UNMEASURED, AGREE, BEHIND, FRONT = 0, 1, 2, 3        # a covered pixel's class: counts[2*class + in_mask]
 UNCOVERED_IN_MASK, RESIDUAL = 8, 9
@@ -59,12 +58,7 @@ def counts(vis, depth, frame, masks, det, box, tol, out=None):
         frame = None
     cum = offsets = None
     if masks is not None:
-        if not (isinstance(masks, (tuple, list)) and len(masks) == 2):
-            raise ValueError(f"{who}: masks must be None or (cum, offsets)")
-        given["cum"] = cum = _lib.arg(masks[0], torch.int32, (None,), who, "cum")
-        given["offsets"] = offsets = _lib.arg(masks[1], torch.int32, (None,), who, "offsets")
-        if offsets.shape[0] < 1:
-            raise ValueError(f"{who}: offsets holds D + 1 entries, got none")
+        given["cum"], given["offsets"] = cum, offsets = mask_lists(who, masks, "None or ")
         given["det"] = det = _lib.arg(det, torch.int32, (N,), who, "det")
     else:
         det = None
@@ -143,7 +137,7 @@ def _instance_key(e, i):
 
 
 # ------------------------------------------------------------------------------------------------ the verifier
-class HypothesisVerifier:
+class HypothesisVerifier(HypothesisFlow):
     """Verification scores of pose hypotheses, and the choice among the hypotheses of each detection.
       models   {obj_id: {"vertices" (V,3), "faces" (F,3), "diameter"}}            (what DepthRefiner and PoseScorer take)
       cameras  {(scene_id, im_id): {"cam_K" 9, ["depth" (H,W) z-depth in the units of the models, 0 = no measurement], ["size" (H, W)]}}
@@ -171,160 +165,33 @@ class HypothesisVerifier:
             raise ValueError(f"{who}: occlusion_weight must lie in [0, 1]")
         if box not in ("projected", "frame"):
             raise ValueError(f"{who}: box must be 'projected' or 'frame'")
-        self.models, self.device = models, device
         self.tol, self.min_points, self.occlusion_weight = float(tol), int(min_points), float(occlusion_weight)
-        self.box, self.margin, self.znear = box, float(margin), float(znear)
-        self.frames = sorted(cameras)
-        if not self.frames:
-            raise ValueError(f"{who}: no cameras")
-        with_depth = [k for k in self.frames if cameras[k].get("depth") is not None]
-        if with_depth and len(with_depth) != len(self.frames):
-            raise ValueError(f"{who}: some cameras have a depth image and some have none (give it for every frame or for none)")
-        self.H = self.W = self._depth_host = self._depth = None
-        if with_depth:
-            depth = [np.asarray(cameras[k]["depth"], np.float32) for k in self.frames]
-            self._set_size(who, *depth[0].shape)
-            if any(d.shape != (self.H, self.W) for d in depth):
-                raise ValueError(f"{who}: the depth images differ in size")
-            self._depth_host = np.stack(depth)
-        for k in self.frames:
-            if cameras[k].get("size") is not None:
-                self._set_size(who, *cameras[k]["size"])
-        self.K = {k: np.asarray(cameras[k]["cam_K"], np.float64).reshape(9) for k in self.frames}
-        self._frame_index = {k: i for i, k in enumerate(self.frames)}
-        self._pairs_per_call = pairs_per_call
-        for o, m in models.items():
-            if m.get("diameter") is None or not float(m["diameter"]) > 0:
-                raise ValueError(f"{who}: model {o} needs a positive diameter")
-
-    def _set_size(self, who, H, W):
-        H, W = int(H), int(W)
-        if self.H is not None and (H, W) != (self.H, self.W):
-            raise ValueError(f"{who}: frame sizes differ: {H} x {W} and {self.H} x {self.W}")
-        if H < 1 or W < 1 or H * W > MAX_PIXELS:
-            raise ValueError(f"{who}: {H} x {W} frames (1 to 2^22 pixels)")
-        self.H, self.W = H, W
-
-    @property
-    def pairs_per_call(self):
-        if self._pairs_per_call is not None:
-            return max(1, min(int(self._pairs_per_call), MAX_PAIRS_PER_CALL))
-        return max(1, min(render.VIS_BYTES_PER_CALL // (self.H * self.W * 8), MAX_PAIRS_PER_CALL))
-
-    def _masks(self, who, estimates, masks):
-        """-> (run lengths int32, offsets int32 (D+1), det int32 (E,), area f64 (E,) NaN = none, boxes of the masks int (D,4))."""
-        E = len(estimates)
-        if isinstance(masks, dict):
-            keys, segs = list(masks), list(masks.values())
-            index = {k: d for d, k in enumerate(keys)}
-            if any("instance_id" not in e for e in estimates):
-                raise ValueError(f"{who}: masks keyed by instance_id need estimates with an instance_id (read_hypotheses)")
-            det = np.asarray([index.get(int(e["instance_id"]), index.get(e["instance_id"], -1)) for e in estimates], np.int32)
-        else:
-            masks = list(masks)
-            if len(masks) != E:
-                raise ValueError(f"{who}: {len(masks)} masks for {E} estimates")
-            segs, seen, det = [], {}, np.full(E, -1, np.int32)
-            for i, m in enumerate(masks):
-                if m is None:
-                    continue
-                if id(m) not in seen:                     # the k hypotheses of a detection usually share one dictionary
-                    seen[id(m)] = len(segs)
-                    segs.append(m)
-                det[i] = seen[id(m)]
-        plain = []
-        for d, seg in enumerate(segs):
-            if not (isinstance(seg, dict) and "counts" in seg and "size" in seg):
-                raise ValueError(f"{who}: mask {d} is not a run-length segmentation {{'size', 'counts'}} (polygons are out of scope)")
-            if self.H is None:
-                self._set_size(who, *seg["size"])
-            if isinstance(seg["counts"], (str, bytes, bytearray)):
-                from . import rle_strings
-
-                seg = dict(seg, counts=rle_strings.rle_counts_from_string(seg["counts"]))
-            plain.append(seg)
-        if self.H is None:
-            raise ValueError(f"{who}: the frame size is unknown (no depth image, no camera 'size', no mask)")
-        H, W = self.H, self.W
-        runs, offsets = ingest.pack_rle(plain, H, W)
-        areas, boxes = np.zeros(len(plain)), np.zeros((len(plain), 4), np.int64)
-        for d in range(len(plain)):
-            c = runs[offsets[d]:offsets[d + 1]].astype(np.int64)
-            ones, ends = c[1::2], np.cumsum(c)
-            areas[d] = ones.sum()
-            first, last = ends[0::2][:len(ones)][ones > 0], (ends[1::2] - 1)[ones > 0]   # the first and last pixel index of each run of ones
-            if not len(first):
-                boxes[d] = (W, H, -1, -1)
-                continue
-            wraps = (last // H > first // H).any()                           # a run that passes the end of a column: every row
-            boxes[d] = (first.min() // H, 0 if wraps else (first % H).min(), last.max() // H, H - 1 if wraps else (last % H).max())
-        area = np.where(det >= 0, areas[np.maximum(det, 0)] if len(plain) else np.nan, np.nan)
-        return runs, offsets, det, area, boxes
+        super().__init__(who, models, cameras, "all_or_none", box, margin, znear, pairs_per_call, device)
 
     @torch.no_grad()
     def score(self, estimates, masks=None):
         who = "HypothesisVerifier.score"
         estimates = list(estimates)
         E = len(estimates)
-        has_depth = self._depth_host is not None
+        has_depth = self.table.depth_host is not None
         if masks is None and not has_depth:
             raise ValueError(f"{who}: no camera has a depth image: masks are required")
-        groups = {}
-        for i, e in enumerate(estimates):
-            key, obj = (int(e["scene_id"]), int(e["im_id"])), int(e["obj_id"])
-            if key not in self._frame_index:
-                raise ValueError(f"{who}: estimate {i}: image {key} has no camera")
-            if obj not in self.models:
-                raise ValueError(f"{who}: estimate {i}: object {obj} has no model")
-            groups.setdefault((obj, self.K[key].tobytes()), []).append(i)
-        lists = None if masks is None else self._masks(who, estimates, masks)
-        if torch.device(self.device).type != "cuda":
-            raise _lib.GigaPoseHipError(f"{who} needs a GPU device (no CPU fallback)")
-        dev, H, W = self.device, self.H, self.W
-        if has_depth and self._depth is None:
-            self._depth = torch.from_numpy(self._depth_host).to(dev)
-        area, cum_d = np.full(E, np.nan), None
-        if lists is not None and len(lists[0]):          # pack_rle has checked the lists: the scan's error flag is not read
+        groups = self._groups(who, estimates)
+        lists = None if masks is None else pack_masks(who, estimates, masks, self.table)
+        need_gpu(who, self.device)
+        dev, depth = self.device, self.table.depth_on(self.device)
+        area, cum_d, det_h, mask_boxes = np.full(E, np.nan), None, None, None
+        if lists is not None and len(lists[0]):
             runs, offsets, det_h, area, mask_boxes = lists
-            offsets_d = torch.from_numpy(offsets).to(dev)
-            cum_d = (ingest.RleDetectionPreprocessor().scan(torch.from_numpy(runs).to(dev), offsets_d, H, W, torch.zeros(1, dtype=torch.int32, device=dev)), offsets_d)
+            cum_d = scan_masks(runs, offsets, self.H, self.W, dev)
         results = []                                   # (indices, counts, status, clipped, tol) on the device: read once at the end
-        for (obj, _), idx in sorted(groups.items(), key=lambda kv: kv[1][0]):
-            m = self.models[obj]
-            vertices, faces = _lib.upload(who, dev, _lib.checked(m["vertices"], torch.float32, (None, 3), who, "vertices"),
-                                          _lib.checked(m["faces"], torch.int32, (None, 3), who, "faces"))
-            t = self.tol * float(m["diameter"])
-            poses_h = np.stack([pose_matrix(estimates[i]["R"], estimates[i]["t"]) for i in idx])
-            keys = [(int(estimates[i]["scene_id"]), int(estimates[i]["im_id"])) for i in idx]
-            K_h = np.stack([self.K[k] for k in keys])
-            if self.box == "frame":
-                box_h = np.tile(np.asarray([0, 0, W - 1, H - 1], np.int32), (len(idx), 1))
-            else:
-                box_h = refine.projected_boxes(m["vertices"], poses_h, K_h, H, W, self.margin)
-                if cum_d is not None:
-                    for j, i in enumerate(idx):
-                        if det_h[i] >= 0:
-                            mb = mask_boxes[det_h[i]]
-                            box_h[j] = (min(box_h[j, 0], mb[0]), min(box_h[j, 1], mb[1]), max(box_h[j, 2], mb[2]), max(box_h[j, 3], mb[3]))
-            K9 = render._k9(K_h[0])
-            V, F = vertices.shape[0], faces.shape[0]
-            n = min(len(idx), self.pairs_per_call)
-            xy = torch.empty(n, V, 2, dtype=torch.int32, device=dev)
-            vdepth = torch.empty(n, V, dtype=torch.float32, device=dev)
-            vis = torch.empty(n, H, W, dtype=torch.int64, device=dev)
-            work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=dev)
-            for _, a, b in _lib.chunked(len(idx), self.pairs_per_call):
-                nb = b - a
-                poses32 = torch.from_numpy(poses_h[a:b].astype(np.float32)).to(dev)
-                frame = torch.tensor([self._frame_index[k] for k in keys[a:b]], dtype=torch.int32, device=dev) if has_depth else None
-                det = torch.from_numpy(np.ascontiguousarray(det_h[idx[a:b]])).to(dev) if cum_d is not None else None
-                box = torch.from_numpy(np.ascontiguousarray(box_h[a:b])).to(dev)
-                tol = torch.full((nb,), t, dtype=torch.float64, device=dev)
-                clipped = torch.empty(nb, dtype=torch.int32, device=dev)
-                pxy, pz = render.project(vertices, poses32, K9, self.znear, out=(xy, vdepth))
-                keys_d, _ = render.raster(pxy, pz, faces, H, W, out=(vis, clipped), workspace=work)
-                rows, status = counts(keys_d, self._depth, frame, cum_d, det, box, tol)
-                results.append((idx[a:b], rows, status, clipped, t))
+        for ch in self._chunks(who, estimates, groups, det=det_h, mask_boxes=mask_boxes):      # the mask's box joins unpadded
+            nb, t = len(ch.idx), self.tol * float(ch.model["diameter"])
+            poses32 = torch.from_numpy(ch.poses.astype(np.float32)).to(dev)
+            tol = torch.full((nb,), t, dtype=torch.float64, device=dev)
+            clipped = torch.empty(nb, dtype=torch.int32, device=dev)
+            rows, status = counts(ch.draw(poses32, clipped), depth, ch.frame, cum_d, ch.det, ch.box, tol)
+            results.append((ch.idx, rows, status, clipped, t))
         out = [dict(e) for e in estimates]
         for idx, rows, status, clipped, t in results:
             rows, status, clipped = (x.cpu().numpy() for x in (rows, status, clipped))

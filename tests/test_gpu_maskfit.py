@@ -19,21 +19,12 @@ from gigapose_testing import raster_ref
 from gigapose_testing import refine_cases as rc
 from gigapose_testing import verify_cases as vc
 
+from gigapose_testing.gpu_cases import assert_bits, five_pairs
+from gigapose_testing.gpu_cases import on_gpu as _t
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H, W = mc.H, mc.W
-
-
-def _t(a):
-    a = np.array(a, copy=True)                                   # the shared cases are read-only arrays
-    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(DEV)
-
-
-def assert_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    want = np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
-    assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
 
 
 def scanned(lists, h, w):
@@ -68,14 +59,7 @@ def check_moments(what, vis, masks, det, box):
 @functools.lru_cache(maxsize=None)
 def rendered():
     """Five pairs: the three starts about GT, two about GT2; keys from render.raster; the masks of the two ground truths."""
-    from gigapose_amd import render
-
-    v, f = rc.mesh("boxes")
-    poses = np.concatenate([rc.starts(), np.stack([rc.moved(rc.GT2, [1, 1, 0], 5, (3, 2, -6)), rc.moved(rc.GT2, [0, 1, 2], 10, (-4, 5, 9))])])
-    xy, vd = render.project(_t(v), _t(poses.astype(np.float32)), mc.K, 1e-3)
-    vis, clipped = render.raster(xy, vd, _t(f), H, W)
-    vis = vis.cpu().numpy().view(np.uint64)
-    assert not clipped.any().item() and ((vis != raster_ref.EMPTY_KEY).sum(axis=(1, 2)) > 200).all()
+    _, vis = five_pairs()
     return dict(vis=vis, masks=scanned([vc.truth(0)["runs"], vc.truth(1)["runs"]], H, W), det=np.asarray([0, 0, 0, 1, 1], np.int32))
 
 

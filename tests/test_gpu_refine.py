@@ -15,21 +15,12 @@ import torch
 from gigapose_testing import dist_ref, raster_ref, refine_ref
 from gigapose_testing import refine_cases as cases
 
+from gigapose_testing.gpu_cases import assert_bits, five_pairs
+from gigapose_testing.gpu_cases import on_gpu as _t
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H, W = cases.H, cases.W
-
-
-def _t(a):
-    a = np.array(a, copy=True)                                   # the shared cases are read-only arrays
-    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(DEV)
-
-
-def assert_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    want = np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
-    assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
 
 
 def device_accumulate(vis, c, poses, K, depth, frame, box, gate, scale):
@@ -69,14 +60,8 @@ def test_face_normals():
 @functools.lru_cache(maxsize=None)
 def rendered():
     """Five pairs on two frames: the three starts about GT on frame 0, two about GT2 on frame 1; keys from render.raster."""
-    from gigapose_amd import render
-
     v, f = cases.mesh("boxes")
-    poses = np.concatenate([cases.starts(), np.stack([cases.moved(cases.GT2, [1, 1, 0], 5, (3, 2, -6)), cases.moved(cases.GT2, [0, 1, 2], 10, (-4, 5, 9))])])
-    xy, vd = render.project(_t(v), _t(poses.astype(np.float32)), cases.K, 1e-3)
-    vis, clipped = render.raster(xy, vd, _t(f), H, W)
-    vis = vis.cpu().numpy().view(np.uint64)
-    assert not clipped.any().item() and ((vis != raster_ref.EMPTY_KEY).sum(axis=(1, 2)) > 200).all()
+    poses, vis = five_pairs()
     depth = np.stack([cases.sensor_depth("boxes", 0), cases.sensor_depth("boxes", 1)])
     n = len(poses)
     return dict(vis=vis, c=refine_ref.face_normals(v, f), poses=poses, K=np.tile(cases.K, (n, 1)), depth=depth, frame=np.asarray([0, 0, 0, 1, 1], np.int32),

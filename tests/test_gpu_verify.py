@@ -16,21 +16,12 @@ from gigapose_testing import dist_ref, raster_ref, verify_ref
 from gigapose_testing import refine_cases as rc
 from gigapose_testing import verify_cases as cases
 
+from gigapose_testing.gpu_cases import assert_bits, five_pairs
+from gigapose_testing.gpu_cases import on_gpu as _t
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H, W = cases.H, cases.W
-
-
-def _t(a):
-    a = np.array(a, copy=True)                                   # the shared cases are read-only arrays
-    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(DEV)
-
-
-def assert_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    want = np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
-    assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
 
 
 def packed(lists):
@@ -77,14 +68,7 @@ def check_counts(what, vis, depth, frame, masks, det, box, tol):
 def rendered():
     """Five pairs on two frames: the three starts about GT on frame 0, two about GT2 on frame 1; keys from render.raster; the
     masks of the two ground truths."""
-    from gigapose_amd import render
-
-    v, f = rc.mesh("boxes")
-    poses = np.concatenate([rc.starts(), np.stack([rc.moved(rc.GT2, [1, 1, 0], 5, (3, 2, -6)), rc.moved(rc.GT2, [0, 1, 2], 10, (-4, 5, 9))])])
-    xy, vd = render.project(_t(v), _t(poses.astype(np.float32)), cases.K, 1e-3)
-    vis, clipped = render.raster(xy, vd, _t(f), H, W)
-    vis = vis.cpu().numpy().view(np.uint64)
-    assert not clipped.any().item() and ((vis != raster_ref.EMPTY_KEY).sum(axis=(1, 2)) > 200).all()
+    poses, vis = five_pairs()
     depth = np.stack([cases.truth(0)["depth"], cases.truth(1)["depth"]])
     n = len(poses)
     return dict(vis=vis, depth=depth, frame=np.asarray([0, 0, 0, 1, 1], np.int32), masks=scanned([cases.truth(0)["runs"], cases.truth(1)["runs"]], H, W),

@@ -98,12 +98,9 @@ def main():
     det = dev(det_h)
     step = max(1, min(render.VIS_BYTES_PER_CALL // (H * W * 8), maskfit.MAX_PAIRS_PER_CALL))
     chunks = [(a, b) for _, a, b in _lib.chunked(N, step)]
-    n = min(N, step)
     V, F = v.shape[0], f.shape[0]
     K9 = render._k9(K)
-    xy, vdepth = torch.empty(n, V, 2, dtype=torch.int32, device=DEV), torch.empty(n, V, dtype=torch.float32, device=DEV)
-    vis = torch.empty(n, H, W, dtype=torch.int64, device=DEV)
-    work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=DEV)
+    buffers = render.KeyBuffers(min(N, step), V, F, H, W, DEV)
     start, Kd, boxd = dev(starts), dev(Kn), dev(box)
     poses32 = start.to(torch.float32)
     frame = torch.zeros(N, dtype=torch.int32, device=DEV)
@@ -120,11 +117,7 @@ def main():
         kept["mm"] = stages["mask_moments"](lambda: maskfit.mask_moments(masks, H, W))
         moved.copy_(start), moved32.copy_(poses32)
         for a, b in chunks:
-            def draw():
-                pxy, pz = render.project(vd, poses32[a:b], K9, 1e-3, out=(xy, vdepth))
-                return render.raster(pxy, pz, fd, H, W, out=(vis, clipped[a:b]), workspace=work)[0]
-
-            keys = stages["render"](draw)
+            keys = stages["render"](lambda: buffers.draw(vd, fd, poses32[a:b], K9, 1e-3, clipped[a:b])[0])
             work_ = {"moments": lambda: maskfit.moments(keys, masks, det[a:b], boxd[a:b], out=(mrows[0][a:b], mrows[1][a:b])),
                      "masked": lambda: verify.counts(keys, None, None, masks, det[a:b], boxd[a:b], tol[a:b], out=(crows["masked"][0][a:b], crows["masked"][1][a:b])),
                      "masked_depth": lambda: verify.counts(keys, depth, frame[a:b], masks, det[a:b], boxd[a:b], tol[a:b],

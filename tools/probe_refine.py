@@ -89,12 +89,9 @@ def main():
     depth = torch.round(torch.where(truth > 0, truth, torch.full_like(truth, 900.0)))
     step = max(1, min(render.VIS_BYTES_PER_CALL // (H * W * 8), refine.MAX_PAIRS_PER_CALL))
     chunks = [(a, b) for _, a, b in _lib.chunked(N, step)]
-    n = min(N, step)
     V, F = v.shape[0], f.shape[0]
     K9 = render._k9(K)
-    xy, vdepth = torch.empty(n, V, 2, dtype=torch.int32, device=DEV), torch.empty(n, V, dtype=torch.float32, device=DEV)
-    vis = torch.empty(n, H, W, dtype=torch.int64, device=DEV)
-    work = torch.empty(max(1, -(-int(render.lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=DEV)
+    buffers = render.KeyBuffers(min(N, step), V, F, H, W, DEV)
     start_d, Kd, boxd = dev(starts), dev(Kn), dev(box)
     frame = torch.zeros(N, dtype=torch.int32, device=DEV)
     gate, scale = torch.full((N,), 0.25 * diameter, dtype=torch.float64, device=DEV), torch.full((N,), diameter, dtype=torch.float64, device=DEV)
@@ -108,11 +105,7 @@ def main():
         poses32 = poses.to(torch.float32)
         for it in range(iters):
             for a, b in chunks:
-                def draw():
-                    pxy, pz = render.project(vd, poses32[a:b], K9, 1e-3, out=(xy, vdepth))
-                    return render.raster(pxy, pz, fd, H, W, out=(vis, clipped[a:b]), workspace=work)[0]
-
-                keys = t_render(draw)
+                keys = t_render(lambda: buffers.draw(vd, fd, poses32[a:b], K9, 1e-3, clipped[a:b])[0])
                 t_acc(lambda: refine.accumulate(keys, c, poses[a:b], Kd[a:b], depth, frame[a:b], boxd[a:b], gate[a:b], scale[a:b],
                                                 out=(sums[a:b], status[a:b])))
                 if keep_first and it == 0 and a == 0:
