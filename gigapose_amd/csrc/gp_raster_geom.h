@@ -1,10 +1,13 @@
-// The triangle arithmetic of the compute rasteriser, shared by render/gpr_render.hip (raster + coloured resolve) and
-// texture/gpt_texture.hip (textured resolve).  Header only; written ONCE: the two libraries must never disagree on which
-// pixels a triangle owns, on the 1 <-> 2 vertex swap of a negative area, or on r_i = 1.0 / (double)depth_i.  The arithmetic is
-// spelled out in include/gigapose_render.h (gpr_raster) and restated in gigapose_testing/raster_ref.py.
+// The triangle and pixel arithmetic of the compute rasteriser, shared by render/gpr_render.hip (raster + coloured resolve),
+// texture/gpt_texture.hip (textured resolve) and shade/gpl_shade.hip (lit resolve).  Header only; written ONCE: the three
+// libraries must never disagree on which pixels a triangle owns, on the 1 <-> 2 vertex swap of a negative area, on
+// r_i = 1.0 / (double)depth_i, or -- in the resolve kernels -- on which keys are background, on the weights t_k = e_k * r_k
+// and their sum q, on the depth a key carries and on how a float64 colour becomes a byte.  The arithmetic is spelled out in
+// include/gigapose_render.h (gpr_raster, gpr_resolve) and restated in gigapose_testing/raster_ref.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace {
@@ -83,6 +86,52 @@ __device__ __forceinline__ bool edges(const Tri& t, int px, int py, i64& e0, i64
     e1 = dx1 * (Y - t.y2) - dy1 * (X - t.x2);
     e2 = dx2 * (Y - t.y0) - dy2 * (X - t.x0);
     return edge_in(e0, dx0, dy0) && edge_in(e1, dx1, dy1) && edge_in(e2, dx2, dy2);
+}
+
+// One pixel of a resolve kernel: what its key says, before any colour.
+struct Pixel {
+    Tri t;                 // the face the key names, set up in this view (no pixel box)
+    i64 e0, e1, e2;        // the edge values at the pixel's centre
+    double t0, t1, t2, q;  // t_k = (double)e_k * t.r_k, q = (t0 + t1) + t2: perspective-correct weights are t_k / q
+    int x, y;
+    unsigned f;            // the key's lower word
+    float z;               // the key's upper word as a float; 0 when the pixel is not drawn
+};
+
+// The key of pixel p (row-major in the H x W frame of a view whose projected vertices are xy_n, depth_n) -> whether the pixel is
+// drawn: the key is not the empty one, names a face < F and that face sets up.  Nothing but f and z is set otherwise.  A drawn
+// pixel is handed to colour(s) -- the kernel's own part, a lambda -- HERE and not after the return: code that follows a returned bool is
+// compiled as a region of its own, whose loads (colours, UVs, normals) wait for the set-up's depth loads instead of going
+// out beside them; that round trip to memory cost the three resolve kernels 2 to 5%.
+template <class Colour>
+__device__ __forceinline__ bool resolve_pixel(u64 key, unsigned p, const int* __restrict__ xy_n, const float* __restrict__ depth_n,
+                                              int V, const int* __restrict__ faces, int F, int H, int W, Pixel& s, Colour colour)
+{
+    s.f = (unsigned)(key & 0xffffffffu);
+    s.z = 0.0f;
+    if (key == ~0ull || s.f >= (unsigned)F || setup_triangle(xy_n, depth_n, V, faces, (int)s.f, H, W, false, s.t) != TRI_OK) return false;
+    s.y = (int)(p / (unsigned)W);
+    s.x = (int)(p - (unsigned)s.y * (unsigned)W);
+    edges(s.t, s.x, s.y, s.e0, s.e1, s.e2);
+    s.t0 = (double)s.e0 * s.t.r0, s.t1 = (double)s.e1 * s.t.r1, s.t2 = (double)s.e2 * s.t.r2;
+    s.q = (s.t0 + s.t1) + s.t2;
+    s.z = __uint_as_float((unsigned)(key >> 32));
+    colour(s);
+    return true;
+}
+
+// floor(x + 1/2) clamped to a byte; a NaN gives 0
+__device__ __forceinline__ unsigned to_byte(double x)
+{
+    const double v = floor(x + 0.5);
+    return v >= 255.0 ? 255u : (v > 0.0 ? (unsigned)v : 0u);
+}
+
+// channel c of the perspective-correct mix of the three vertex colours (u8 (V,3))
+__device__ __forceinline__ unsigned vertex_colour_byte(const uint8_t* __restrict__ colours, const Pixel& s, int c)
+{
+    const double c0 = colours[3 * (size_t)s.t.i0 + c], c1 = colours[3 * (size_t)s.t.i1 + c], c2 = colours[3 * (size_t)s.t.i2 + c];
+    return to_byte(((s.t0 * c0 + s.t1 * c1) + s.t2 * c2) / s.q);
 }
 
 }  // namespace

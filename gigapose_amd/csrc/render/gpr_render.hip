@@ -6,15 +6,16 @@
 // bounding box, a triangle with a large box goes to a list and a second launch gives it a whole workgroup.  gpr_resolve: one
 // thread per pixel turns the key into colour, alpha and depth.  The arithmetic (int64 edge functions, float64 interpolation in
 // a fixed order) is spelled out in the header and restated in gigapose_testing/raster_ref.py; the two agree bit for bit.
-// The host-side plumbing is gp_front.h's, the triangle set-up and the coverage rule gp_raster_geom.h's (shared with the
-// texture library).  This library links no object of the other libraries and exports only gpr_* names.
+// The host-side plumbing is gp_front.h's; the triangle set-up, the coverage rule, what a resolve kernel reads out of a pixel's
+// key and the vertex-colour byte are gp_raster_geom.h's (shared with the texture and shade libraries).  This library links no
+// object of the other libraries and exports only gpr_* names.
 #include <limits.h>
 #include <math.h>
 
 #include "gigapose_render.h"   // the C ABI these definitions are compiled against
 #define GP_FRONT_PREFIX gpr
 #include "../gp_front.h"
-#include "../gp_raster_geom.h"   // Tri, setup_triangle, edge_in, edges: shared with texture/gpt_texture.hip
+#include "../gp_raster_geom.h"   // Tri, setup_triangle, edges; Pixel, resolve_pixel, vertex_colour_byte
 
 namespace {
 
@@ -123,33 +124,16 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const u64* __restrict
     const int n = blockIdx.y;
     if (p >= (unsigned)H * (unsigned)W) return;
     const size_t o = (size_t)n * H * W + p;
-    const u64 key = vis[o];
-    const unsigned f = (unsigned)(key & 0xffffffffu);
     uint32_t px = 0u;
-    float z = 0.0f;
-    Tri t;
-    if (key != ~0ull && f < (unsigned)F &&
-        setup_triangle(xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, (int)f, H, W, false, t) == TRI_OK) {
-        const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
-        i64 e0, e1, e2;
-        edges(t, x, y, e0, e1, e2);
-        const double t0 = (double)e0 * t.r0, t1 = (double)e1 * t.r1, t2 = (double)e2 * t.r2;
-        const double q = (t0 + t1) + t2;
+    Pixel pixel;
+    resolve_pixel(vis[o], p, xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, F, H, W, pixel, [&](const Pixel& pix) {
         px = 0xff000000u;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double c0 = colours[3 * (size_t)t.i0 + c], c1 = colours[3 * (size_t)t.i1 + c],
-                         c2 = colours[3 * (size_t)t.i2 + c];
-            const double v = floor(((t0 * c0 + t1 * c1) + t2 * c2) / q + 0.5);
-            const unsigned b = v >= 255.0 ? 255u : (v > 0.0 ? (unsigned)v : 0u);
-            px |= b << (8 * c);
-        }
-        z = __uint_as_float((unsigned)(key >> 32));
-    }
+        for (int c = 0; c < 3; ++c) px |= vertex_colour_byte(colours, pix, c) << (8 * c);
+    });
     rgba[o] = px;
-    zdepth[o] = z;
+    zdepth[o] = pixel.z;
 }
-
 
 }  // namespace
 

@@ -7,9 +7,10 @@
 // colour byte of gpr_resolve, a normal (interpolated, or the face's), the camera-space position from the key's depth, and a
 // loop over at most 16 lights that sit in the kernel's arguments: per light 3 subtractions, two dot products, one root and one
 // division.  Background pixels leave after the key.  The arithmetic is spelled out in the header and restated in
-// gigapose_testing/shade_ref.py; the two agree bit for bit.  The host-side plumbing is gp_front.h's, the triangle set-up
-// gp_raster_geom.h's (shared with the render and texture libraries), the square root gp_root.h's (shared with the distance
-// library).  This library links no object of the other libraries and exports only gpl_* names.
+// gigapose_testing/shade_ref.py; the two agree bit for bit.  The host-side plumbing is gp_front.h's; the triangle set-up,
+// what the kernel reads out of a pixel's key (the gate, the weights, the depth) and the vertex-colour byte are gp_raster_geom.h's
+// (shared with the render and texture libraries), the square root gp_root.h's (shared with the distance library).  This
+// library links no object of the other libraries and exports only gpl_* names.
 #include <math.h>
 
 #include "gigapose_shade.h"   // the C ABI these definitions are compiled against
@@ -99,19 +100,11 @@ __global__ __launch_bounds__(kThreads) void shade_kernel(const u64* __restrict__
     const int n = blockIdx.y;
     if (p >= (unsigned)H * (unsigned)W) return;
     const size_t o = (size_t)n * H * W + p;
-    const u64 key = vis[o];
-    const unsigned f = (unsigned)(key & 0xffffffffu);
     uint32_t px = 0u;
-    float zf = 0.0f;
-    Tri t;
-    if (key != ~0ull && f < (unsigned)F &&
-        setup_triangle(xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, (int)f, H, W, false, t) == TRI_OK) {
-        const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
-        i64 e0, e1, e2;
-        edges(t, x, y, e0, e1, e2);
-        const double t0 = (double)e0 * t.r0, t1 = (double)e1 * t.r1, t2 = (double)e2 * t.r2;
-        const double q = (t0 + t1) + t2;
-        zf = __uint_as_float((unsigned)(key >> 32));
+    Pixel pixel;
+    resolve_pixel(vis[o], p, xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, F, H, W, pixel, [&](const Pixel& pix) {
+        const Tri& t = pix.t;
+        const double t0 = pix.t0, t1 = pix.t1, t2 = pix.t2;
         double g[3];
         if (kFlat) {
             const int i1 = t.swapped ? t.i2 : t.i1, i2 = t.swapped ? t.i1 : t.i2;   // the stored order
@@ -125,9 +118,9 @@ __global__ __launch_bounds__(kThreads) void shade_kernel(const u64* __restrict__
         double m[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) m[r] = ((double)P[4 * r] * g[0] + (double)P[4 * r + 1] * g[1]) + (double)P[4 * r + 2] * g[2];
-        const double z = (double)zf;
-        const double yn = ((double)y - S.K5) / S.K4;
-        const double xn = (((double)x - S.K2) - S.K1 * yn) / S.K0;
+        const double z = (double)pix.z;
+        const double yn = ((double)pix.y - S.K5) / S.K4;
+        const double xn = (((double)pix.x - S.K2) - S.K1 * yn) / S.K0;
         const double pos[3] = {xn * z, yn * z, z};
         const double s = (m[0] * pos[0] + m[1] * pos[1]) + m[2] * pos[2];
         if (s > 0.0) m[0] = -m[0], m[1] = -m[1], m[2] = -m[2];
@@ -147,16 +140,13 @@ __global__ __launch_bounds__(kThreads) void shade_kernel(const u64* __restrict__
         px = 0xff000000u;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const double c0 = colours[3 * (size_t)t.i0 + c], c1 = colours[3 * (size_t)t.i1 + c], c2 = colours[3 * (size_t)t.i2 + c];
-            const double v = floor(((t0 * c0 + t1 * c1) + t2 * c2) / q + 0.5);
-            const unsigned b = v >= 255.0 ? 255u : (v > 0.0 ? (unsigned)v : 0u);
-            const double w = floor((decode[b] * E) * top + 0.5);
+            const double w = floor((decode[vertex_colour_byte(colours, pix, c)] * E) * top + 0.5);
             const unsigned i = w >= top ? (unsigned)(T - 1) : (w > 0.0 ? (unsigned)w : 0u);   // a NaN fails both: 0
             px |= (uint32_t)encode[i] << (8 * c);
         }
-    }
+    });
     rgba[o] = px;
-    zdepth[o] = zf;
+    zdepth[o] = pixel.z;
 }
 
 bool finite_host(double x) { return x == x && x - x == 0.0; }

@@ -6,8 +6,9 @@
 // pixel; perspective-correct UV at the pixel and at its right and lower neighbour, a level of detail from the squared UV
 // steps (comparisons with powers of four: no logarithm), one or two bilinear samples with repeat wrapping: 4 or 8 texel loads
 // of 4 bytes.  The arithmetic is spelled out in the header and restated in gigapose_testing/texture_ref.py; the two agree bit
-// for bit.  The host-side plumbing is gp_front.h's, the triangle set-up gp_raster_geom.h's (shared with the render library).
-// This library links no object of the other libraries and exports only gpt_* names.
+// for bit.  The host-side plumbing is gp_front.h's; the triangle set-up, what the kernel reads out of a pixel's key (the gate,
+// the centre weights, the depth) and the rounding to a byte are gp_raster_geom.h's (shared with the render and shade
+// libraries).  This library links no object of the other libraries and exports only gpt_* names.
 #include <math.h>
 
 #include "gigapose_texture.h"   // the C ABI these definitions are compiled against
@@ -78,9 +79,9 @@ struct UV {
     double q, u, v;
 };
 
-__device__ __forceinline__ UV uv_at(i64 e0, i64 e1, i64 e2, const Tri& t, const double* cu, const double* cv)
+// from the weights t_k = (double)e_k * r_k: the pixel's own are resolve_pixel's, a neighbour's come from its edge values
+__device__ __forceinline__ UV uv_at(double t0, double t1, double t2, const double* cu, const double* cv)
 {
-    const double t0 = (double)e0 * t.r0, t1 = (double)e1 * t.r1, t2 = (double)e2 * t.r2;
     UV o;
     o.q = (t0 + t1) + t2;
     o.u = ((t0 * cu[0] + t1 * cu[1]) + t2 * cu[2]) / o.q;
@@ -112,12 +113,6 @@ __device__ __forceinline__ void bilinear(const uint32_t* __restrict__ pyramid, c
     }
 }
 
-__device__ __forceinline__ unsigned to_byte(double x)
-{
-    const double v = floor(x + 0.5);
-    return v >= 255.0 ? 255u : (v > 0.0 ? (unsigned)v : 0u);
-}
-
 // grid (ceil(H*W / 256), N): thread = pixel
 __global__ __launch_bounds__(kThreads) void resolve_kernel(const u64* __restrict__ vis, const int* __restrict__ xy,
                                                            const float* __restrict__ depth, int V, const int* __restrict__ faces, int F,
@@ -128,29 +123,22 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const u64* __restrict
     const int n = blockIdx.y;
     if (p >= (unsigned)H * (unsigned)W) return;
     const size_t o = (size_t)n * H * W + p;
-    const u64 key = vis[o];
-    const unsigned f = (unsigned)(key & 0xffffffffu);
     uint32_t px = 0u;
-    float z = 0.0f;
-    Tri t;
-    if (key != ~0ull && f < (unsigned)F &&
-        setup_triangle(xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, (int)f, H, W, false, t) == TRI_OK) {
+    Pixel pixel;
+    resolve_pixel(vis[o], p, xy + 2 * (size_t)n * V, depth + (size_t)n * V, V, faces, F, H, W, pixel, [&](const Pixel& pix) {
+        const Tri& t = pix.t;
         px = 0xff000000u;
-        z = __uint_as_float((unsigned)(key >> 32));
-        const float* c = corner_uv + 6 * (size_t)f;
+        const float* c = corner_uv + 6 * (size_t)pix.f;
         const int k1 = t.swapped ? 2 : 1, k2 = t.swapped ? 1 : 2;   // the corners go with the vertices
         const double cu[3] = {(double)c[0], (double)c[2 * k1], (double)c[2 * k2]};
         const double cv[3] = {(double)c[1], (double)c[2 * k1 + 1], (double)c[2 * k2 + 1]};
-        const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
-        i64 e0, e1, e2;
-        edges(t, x, y, e0, e1, e2);
-        const UV m = uv_at(e0, e1, e2, t, cu, cv);
+        const UV m = uv_at(pix.t0, pix.t1, pix.t2, cu, cv);
         const bool good = within(cu[0], kMaxUV) && within(cu[1], kMaxUV) && within(cu[2], kMaxUV) && within(cv[0], kMaxUV) &&
                           within(cv[1], kMaxUV) && within(cv[2], kMaxUV) && within(m.u, 2.0 * kMaxUV) && within(m.v, 2.0 * kMaxUV);
         if (good) {
             const i64 dx0 = t.x2 - t.x1, dy0 = t.y2 - t.y1, dx1 = t.x0 - t.x2, dy1 = t.y0 - t.y2, dx2 = t.x1 - t.x0, dy2 = t.y1 - t.y0;
-            const UV mx = uv_at(e0 - 256 * dy0, e1 - 256 * dy1, e2 - 256 * dy2, t, cu, cv);
-            const UV my = uv_at(e0 + 256 * dx0, e1 + 256 * dx1, e2 + 256 * dx2, t, cu, cv);
+            const UV mx = uv_at((double)(pix.e0 - 256 * dy0) * t.r0, (double)(pix.e1 - 256 * dy1) * t.r1, (double)(pix.e2 - 256 * dy2) * t.r2, cu, cv);
+            const UV my = uv_at((double)(pix.e0 + 256 * dx0) * t.r0, (double)(pix.e1 + 256 * dx1) * t.r1, (double)(pix.e2 + 256 * dx2) * t.r2, cu, cv);
             const int top = P.levels - 1;
             int l0 = top;
             bool two = false;
@@ -188,9 +176,9 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const u64* __restrict
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) px |= to_byte(A[ch]) << (8 * ch);
         }
-    }
+    });
     rgba[o] = px;
-    zdepth[o] = z;
+    zdepth[o] = pixel.z;
 }
 
 }  // namespace

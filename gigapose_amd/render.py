@@ -13,6 +13,9 @@ gigapose_testing/raster_ref.py; tests/test_gpu_render.py holds the kernels to it
   template_object_poses(poses, zoom)    a copy with the translation scaled (render_bop_templates.py:69-70)
   MeshTemplates                         drop-in for model.template_datasets[name], beside onboard.RenderedTemplates
   save_renders(out_dir, rgba, depth)    {view:06d}.png + {view:06d}_depth.png, the reference's layout; onboard.load_renders reads it
+What texture.py and shade.py share with this module lives here, once: read_ply (one pass over a PLY file), key_inputs / resolve_out
+(the checks of a resolve's key inputs and of its `out`), Renderer (the checks, the buffers, the chunk loop and the clipped-view
+error of the three renderers), TemplateSet (the three template datasets) and host.
 Textured models (YCB-V, HB) are drawn by texture.py (libgigapose_texture.so), which takes gpr_project's and gpr_raster's output and
 resolves it through a mip-mapped texture; models with neither colour nor texture (T-LESS, ITODD) by shade.py (libgigapose_shade.so),
 which lights them; this module stays with vertex colours.  Out of scope here: shading other than ambient, near-plane clipping (a triangle with a vertex behind znear is
@@ -137,21 +140,35 @@ def _read_element(fmt, props, count, data, pos, tokens, path, name):
     return out, pos
 
 
-def load_ply(path):
-    """-> vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3) or None when the file has no red / green / blue.  Reads
-    `ascii` and `binary_little_endian` with numpy alone; names and types come from the header, properties it does not need
-    (normals, alpha, texture_u / texture_v, ...) are skipped; the face list is `vertex_indices` or `vertex_index` of any integer
-    types.  ValueError: a face that is not a triangle, an index >= V, a truncated file, binary_big_endian."""
+def read_ply(path):
+    """One pass over the file -> (path as a string, the header's comment lines as written, {element: {property: array, or a list
+    of arrays for a list property whose rows differ in length}}).  Reads `ascii` and `binary_little_endian` with numpy alone;
+    names and types come from the header.  ValueError: no PLY file, a truncated one, binary_big_endian.  What load_ply,
+    shade.load_ply_with_normals and texture.load_textured_ply are built on."""
     path = os.fspath(path)
     with open(path, "rb") as fh:
         data = fh.read()
     fmt, elements, pos = _ply_header(data, path)
+    comments = [ln for ln in data[:pos].decode("ascii", "replace").splitlines() if ln.split()[:1] == ["comment"]]
     tokens = None
     if fmt == "ascii":
         tokens, pos = data[pos:].split(), 0
     got = {}
     for name, count, props in elements:
         got[name], pos = _read_element(fmt, props, count, data, pos, tokens, path, name)
+    return path, comments, got
+
+
+def load_ply(path):
+    """-> vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3) or None when the file has no red / green / blue.  Properties
+    it does not need (normals, alpha, texture_u / texture_v, ...) are skipped; the face list is `vertex_indices` or
+    `vertex_index` of any integer types.  ValueError: a face that is not a triangle, an index >= V, and what read_ply rejects."""
+    path, _, got = read_ply(path)
+    return ply_mesh(path, got)
+
+
+def ply_mesh(path, got):
+    """load_ply's result from read_ply's elements."""
     if "vertex" not in got or not all(k in got["vertex"] for k in "xyz"):
         raise ValueError(f"load_ply: {path}: no vertex element with x, y, z")
     vert = got["vertex"]
@@ -225,21 +242,35 @@ def raster(xy, vdepth, faces, H, W, out=None, workspace=None):
     return vis[:N], clipped[:N]
 
 
+def key_inputs(who, vis, xy, vdepth, faces):
+    """What every resolve takes beside its colour inputs, checked: -> vis int64 (N,H,W), xy int32 (N,V,2), vdepth f32 (N,V), faces
+    int32 (F,3) and N, H, W, V, F."""
+    vis = _lib.on_device(vis, torch.int64, (None, None, None), who, "vis")
+    N, H, W = vis.shape
+    xy = _lib.on_device(xy, torch.int32, (N, None, 2), who, "xy")
+    V = xy.shape[1]
+    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), who, "vdepth")
+    faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
+    return vis, xy, vdepth, faces, N, H, W, V, faces.shape[0]
+
+
+def resolve_out(who, out, N, H, W, device, unlit=False):
+    """`out` of a resolve, or new buffers: rgba u8 (N,H,W,4), depth f32 (N,H,W) [, unlit int32 (N,)], checked."""
+    if out is None:
+        out = (torch.empty(N, H, W, 4, dtype=torch.uint8, device=device), torch.empty(N, H, W, dtype=torch.float32, device=device))
+        out += (torch.empty(N, dtype=torch.int32, device=device),) if unlit else ()
+    if [tuple(t.shape) for t in out] != [(N, H, W, 4), (N, H, W)] + [(N,)] * unlit:
+        raise ValueError(f"{who}: out must be rgba (N,H,W,4)" + (", depth (N,H,W) and unlit (N,)" if unlit else " and depth (N,H,W)"))
+    return out
+
+
 @torch.no_grad()
 def resolve(vis, xy, vdepth, faces, colours, out=None):
     """gpr_resolve: the keys -> rgba u8 (N,H,W,4), depth f32 (N,H,W); `out` = (rgba, depth) are buffers to write into."""
-    vis = _lib.on_device(vis, torch.int64, (None, None, None), "resolve", "vis")
-    N, H, W = vis.shape
-    xy = _lib.on_device(xy, torch.int32, (N, None, 2), "resolve", "xy")
-    V = xy.shape[1]
-    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), "resolve", "vdepth")
-    faces = _lib.on_device(faces, torch.int32, (None, 3), "resolve", "faces")
+    vis, xy, vdepth, faces, N, H, W, V, F = key_inputs("resolve", vis, xy, vdepth, faces)
     colours = _lib.on_device(colours, torch.uint8, (V, 3), "resolve", "colours")
-    rgba, depth = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=vis.device),
-                                               torch.empty(N, H, W, dtype=torch.float32, device=vis.device))
-    if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W):
-        raise ValueError("resolve: out must be rgba (N,H,W,4) and depth (N,H,W)")
-    _call("gpr_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(faces.shape[0]), _lib.ptr(colours),
+    rgba, depth = resolve_out("resolve", out, N, H, W, vis.device)
+    _call("gpr_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(colours),
           _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.stream_ptr())
     return rgba, depth
 
@@ -289,23 +320,32 @@ def template_object_poses(obj_poses, zoom=0.4):
     return out
 
 
-class MeshRenderer:
-    """vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3), poses f32 (N,4,4), all on the device -> rgba u8 (N,H,W,4) in the
-    format gpo_alpha_boxes / gpo_crop_templates read, depth f32 (N,H,W) in model units (0 where nothing is drawn), clipped
-    int32 (N,).  Poses are object -> camera in the OpenCV convention (x right, y down, z forward), what the reference's load_pose
-    returns; pixel centres sit at integer coordinates.  znear is in model units."""
+class Renderer:
+    """What MeshRenderer, texture.TexturedMeshRenderer and shade.ShadedMeshRenderer share: the frame, the camera, znear, the checks
+    of the mesh and the poses, the result's buffers, the chunk loop over render.KeyBuffers and the clipped-view error.  A
+    subclass names itself in `who`, passes its own inputs through ._draw and supplies
+      ._prepare(vertices, faces, poses, **inputs) -> state    its inputs checked (colours / UVs and pyramid / normals and tables)
+      ._resolve_chunk(state, keys, xy, vdepth, a, b, out)     views a..b of the result `out` from the keys of one chunk
+    and, in `counters`, the names of the int32 (N,) counts its resolve writes beside "clipped"."""
+    who = None
+    no_colour = None                                # the wording of `colours=None` without `colour`
+    counters = ()
 
     def __init__(self, H=480, W=640, K=TEMPLATE_K, znear=1e-3):
         self.H, self.W, self.znear = int(H), int(W), float(znear)
         self._K = _k9(K)
 
+    def _colours(self, V, colours, colour, device):
+        if colours is None:
+            if colour is None:
+                raise ValueError(f"{self.who}: {self.no_colour}")
+            colours = torch.tensor([colour], dtype=torch.uint8, device=device).expand(V, 3)
+        return _lib.on_device(colours, torch.uint8, (V, 3), self.who, "colours")
+
     @torch.no_grad()
-    def __call__(self, vertices, faces, colours, poses, views_per_call=None, colour=None, on_clipped="raise"):
-        """`colours=None` needs `colour=(r, g, b)`, painted on every vertex (the reference paints T-LESS a uniform grey,
-        src/lib3d/pyrender.py:90-95).  A view with a dropped triangle (a vertex behind znear, beyond 16384 px or not finite, or a
-        face index outside the mesh) raises ValueError naming it unless on_clipped="ignore".  One host synchronisation: the
-        read of the clipped counts."""
-        who = "MeshRenderer"
+    def _draw(self, vertices, faces, poses, views_per_call, on_clipped, **inputs):
+        """-> {"rgba", "depth", "clipped"} + one entry per name in `counters`."""
+        who = self.who
         if on_clipped not in ("raise", "ignore"):
             raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
         vertices = _lib.on_device(vertices, torch.float32, (None, 3), who, "vertices")
@@ -313,23 +353,47 @@ class MeshRenderer:
         poses = _lib.on_device(poses, torch.float32, (None, 4, 4), who, "poses")
         V, F, N = vertices.shape[0], faces.shape[0], poses.shape[0]
         dev = vertices.device
-        if colours is None:
-            if colour is None:
-                raise ValueError(f"{who}: the mesh has no vertex colours and textures are out of scope: pass colour=(r, g, b)")
-            colours = torch.tensor([colour], dtype=torch.uint8, device=dev).expand(V, 3)
-        colours = _lib.on_device(colours, torch.uint8, (V, 3), who, "colours")
+        state = self._prepare(vertices, faces, poses, **inputs)
         H, W = self.H, self.W
         step = views_step(views_per_call, H, W)
-        rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
-        depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-        clipped = torch.empty(N, dtype=torch.int32, device=dev)
+        out = {"rgba": torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev), "depth": torch.empty(N, H, W, dtype=torch.float32, device=dev)}
+        out.update({k: torch.empty(N, dtype=torch.int32, device=dev) for k in ("clipped",) + tuple(self.counters)})
         buffers = KeyBuffers(min(N, step), V, F, H, W, dev)
         for _, a, b in _lib.chunked(N, step):
-            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, clipped[a:b])
-            resolve(keys, pxy, pz, faces, colours, out=(rgba[a:b], depth[a:b]))
+            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, out["clipped"][a:b])
+            self._resolve_chunk(state, keys, pxy, pz, a, b, out)
         if on_clipped == "raise":
-            raise_clipped(who, clipped, F, self.znear)
-        return {"rgba": rgba, "depth": depth, "clipped": clipped}
+            raise_clipped(who, out["clipped"], F, self.znear)
+        return out
+
+
+class MeshRenderer(Renderer):
+    """vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3), poses f32 (N,4,4), all on the device -> rgba u8 (N,H,W,4) in the
+    format gpo_alpha_boxes / gpo_crop_templates read, depth f32 (N,H,W) in model units (0 where nothing is drawn), clipped
+    int32 (N,).  Poses are object -> camera in the OpenCV convention (x right, y down, z forward), what the reference's load_pose
+    returns; pixel centres sit at integer coordinates.  znear is in model units."""
+    who = "MeshRenderer"
+    no_colour = "the mesh has no vertex colours and textures are out of scope: pass colour=(r, g, b)"
+
+    def __call__(self, vertices, faces, colours, poses, views_per_call=None, colour=None, on_clipped="raise"):
+        """`colours=None` needs `colour=(r, g, b)`, painted on every vertex (the reference paints T-LESS a uniform grey,
+        src/lib3d/pyrender.py:90-95).  A view with a dropped triangle (a vertex behind znear, beyond 16384 px or not finite, or a
+        face index outside the mesh) raises ValueError naming it unless on_clipped="ignore".  One host synchronisation: the
+        read of the clipped counts."""
+        return self._draw(vertices, faces, poses, views_per_call, on_clipped, colours=colours, colour=colour)
+
+    def _prepare(self, vertices, faces, poses, colours, colour):
+        return faces, self._colours(vertices.shape[0], colours, colour, vertices.device)
+
+    def _resolve_chunk(self, state, keys, pxy, pz, a, b, out):
+        resolve(keys, pxy, pz, *state, out=(out["rgba"][a:b], out["depth"][a:b]))
+
+
+def host(a, dtype=None):
+    """A tensor or anything numpy reads -> a host array; with `dtype`, a C-contiguous COPY of that type (PIL hands out read-only
+    arrays, and torch.from_numpy wants a writable one)."""
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a if dtype is None else np.array(a, dtype=dtype, order="C")
 
 
 def _host_mesh(mesh, who):
@@ -338,14 +402,8 @@ def _host_mesh(mesh, who):
     if isinstance(mesh, dict):
         mesh = (mesh["vertices"], mesh["faces"], mesh.get("colours"))
     v, f, c = mesh
-
-    def host(a, dtype):
-        if isinstance(a, torch.Tensor):
-            a = a.detach().cpu().numpy()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype)))
-
-    v, f = host(v, np.float32), host(f, np.int32)
-    c = None if c is None else host(c, np.uint8)
+    v, f = torch.from_numpy(host(v, np.float32)), torch.from_numpy(host(f, np.int32))
+    c = None if c is None else torch.from_numpy(host(c, np.uint8))
     if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or (c is not None and tuple(c.shape) != tuple(v.shape)):
         raise ValueError(f"{who}: expected vertices (V,3), faces (F,3), colours (V,3) or None")
     if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
@@ -353,33 +411,28 @@ def _host_mesh(mesh, who):
     return v, f, c
 
 
-class MeshTemplates:
-    """Drop-in for `model.template_datasets[name]`, beside onboard.RenderedTemplates: item i is a PandasTensorCollection with
-    .rgb (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3) .poses (N,4,4) on the device.
+class TemplateSet:
+    """What MeshTemplates, texture.TexturedMeshTemplates and shade.ShadedMeshTemplates share: a drop-in for
+    `model.template_datasets[name]` whose item i is a PandasTensorCollection with .rgb (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3)
+    .poses (N,4,4) on the device.  The objects stay on the HOST; every __getitem__ uploads one, renders its N views on the device
+    and hands the device renders to TemplateOnboarder: no render crosses PCIe.  A subclass names itself in `who` and supplies
+    ._host_object(o, obj) -> (host tensors of the mesh | None, poses) and ._render_object(mesh on the device, poses)."""
+    who = None
 
-    objects: list of (mesh, poses) -- mesh a PLY path, a (vertices, faces, colours) tuple or a dict with those keys; poses
-    (N,4,4) object -> camera as the reference's load_pose returns them (template_object_poses applies the reference's zoom), in
-    bank order.  `colour=(r, g, b)` paints meshes without vertex colours.  The meshes stay on the HOST; every __getitem__ uploads
-    the mesh, renders its N views on the device and hands the device renders to TemplateOnboarder: no render crosses PCIe."""
-
-    def __init__(self, objects, K=None, device="cuda", target_size=224, H=480, W=640, znear=1e-3, colour=None):
+    def __init__(self, objects, renderer, K, device, target_size):
+        """renderer: K (3,3) f32 -> the subclass's renderer."""
         self.device = torch.device(device)
-        self.colour = colour
         K = np.asarray(TEMPLATE_K if K is None else K, dtype=np.float32).reshape(3, 3)
         self.K = torch.as_tensor(K)
-        self.renderer = MeshRenderer(H, W, K, znear)
+        self.renderer = renderer(K)
         self.onboard = TemplateOnboarder(target_size)
         self._meshes, self._poses = [], []
-        for o, (mesh, poses) in enumerate(objects):
-            m = _host_mesh(mesh, f"MeshTemplates: object {o}")
-            if m[2] is None and colour is None:
-                raise ValueError(f"MeshTemplates: object {o} has no vertex colours and textures are out of scope: pass colour=(r, g, b)")
-            if isinstance(poses, torch.Tensor):
-                poses = poses.detach().cpu().numpy()
-            p = torch.as_tensor(np.asarray(poses, dtype=np.float32))
+        for o, obj in enumerate(objects):
+            mesh, poses = self._host_object(o, obj)
+            p = torch.from_numpy(host(poses, np.float32))
             if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
-                raise ValueError(f"MeshTemplates: object {o}: expected poses (N, 4, 4), got {tuple(p.shape)}")
-            self._meshes.append(m)
+                raise ValueError(f"{self.who}: object {o}: expected poses (N, 4, 4), got {tuple(p.shape)}")
+            self._meshes.append(mesh)
             self._poses.append(p)
 
     def __len__(self):
@@ -387,14 +440,14 @@ class MeshTemplates:
 
     @torch.no_grad()
     def render(self, i):
-        """The device renders of object i: {"rgba", "depth", "clipped"}."""
+        """The device renders of object i: the renderer's result."""
         if self.device.type != "cuda":
-            raise _lib.GigaPoseHipError("MeshTemplates needs a GPU device (no CPU fallback)")
-        v, f, c = (None if t is None else t.to(self.device) for t in self._meshes[i])
+            raise _lib.GigaPoseHipError(f"{self.who} needs a GPU device (no CPU fallback)")
+        mesh = tuple(None if t is None else t.to(self.device) for t in self._meshes[i])
         try:
-            return self.renderer(v, f, c, self._poses[i].to(self.device), colour=self.colour)
+            return self._render_object(mesh, self._poses[i].to(self.device))
         except ValueError as e:
-            raise ValueError(f"MeshTemplates: object {i}: {e}") from None
+            raise ValueError(f"{self.who}: object {i}: {e}") from None
 
     @torch.no_grad()
     def __getitem__(self, i):
@@ -402,9 +455,34 @@ class MeshTemplates:
         try:
             out = self.onboard(rgba)
         except ValueError as e:
-            raise ValueError(f"MeshTemplates: object {i}: {e}") from None
+            raise ValueError(f"{self.who}: object {i}: {e}") from None
         return PandasTensorCollection(infos=pd.DataFrame(), K=self.K.to(self.device), rgb=out["rgb"], mask=out["mask"], M=out["M"],
                                       poses=self._poses[i].to(self.device))
+
+
+class MeshTemplates(TemplateSet):
+    """Drop-in for `model.template_datasets[name]`, beside onboard.RenderedTemplates: item i is a PandasTensorCollection with
+    .rgb (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3) .poses (N,4,4) on the device.
+
+    objects: list of (mesh, poses) -- mesh a PLY path, a (vertices, faces, colours) tuple or a dict with those keys; poses
+    (N,4,4) object -> camera as the reference's load_pose returns them (template_object_poses applies the reference's zoom), in
+    bank order.  `colour=(r, g, b)` paints meshes without vertex colours.  The meshes stay on the HOST; every __getitem__ uploads
+    the mesh, renders its N views on the device and hands the device renders to TemplateOnboarder: no render crosses PCIe."""
+    who = "MeshTemplates"
+
+    def __init__(self, objects, K=None, device="cuda", target_size=224, H=480, W=640, znear=1e-3, colour=None):
+        self.colour = colour
+        super().__init__(objects, lambda K: MeshRenderer(H, W, K, znear), K, device, target_size)
+
+    def _host_object(self, o, obj):
+        mesh, poses = obj
+        m = _host_mesh(mesh, f"{self.who}: object {o}")
+        if m[2] is None and self.colour is None:
+            raise ValueError(f"{self.who}: object {o} has no vertex colours and textures are out of scope: pass colour=(r, g, b)")
+        return m, poses
+
+    def _render_object(self, mesh, poses):
+        return self.renderer(*mesh, poses, colour=self.colour)
 
 
 def save_renders(out_dir, rgba, depth=None, depth_scale=1.0):
@@ -412,9 +490,6 @@ def save_renders(out_dir, rgba, depth=None, depth_scale=1.0):
     rint(depth * depth_scale), saturated at 65535 -- the reference stores millimetres, so a model in metres takes
     depth_scale=1000.  onboard.load_renders(out_dir) returns the same rgba."""
     from PIL import Image
-
-    def host(a):
-        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
     rgba = host(rgba)
     if not (rgba.dtype == np.uint8 and rgba.ndim == 4 and rgba.shape[3] == 4):

@@ -25,12 +25,10 @@ import math
 import os
 
 import numpy as np
-import pandas as pd
 import torch
 
 from . import _lib, render
-from .onboard import TEMPLATE_K, TemplateOnboarder
-from .tensor_collection import PandasTensorCollection
+from .onboard import TEMPLATE_K
 
 RANGE, NO_NORMAL = 1, 2                             # gigapose_shade.h: GPL_RANGE, GPL_NO_NORMAL
 SMOOTH, FLAT = 0, 1                                 # gigapose_shade.h: GPL_SMOOTH, GPL_FLAT
@@ -133,22 +131,11 @@ def blenderproc_lights(units_per_metre, watts=50.0):
 def load_ply_with_normals(path):
     """-> vertices, faces, colours as render.load_ply returns them, + normals f64 (V,3) from the vertex properties nx, ny, nz, or
     None when the file has none (BOP's model files usually carry them; load_ply skips them)."""
-    path = os.fspath(path)
-    vertices, faces, colours = render.load_ply(path)
-    with open(path, "rb") as fh:
-        data = fh.read()
-    fmt, elements, pos = render._ply_header(data, path)
-    tokens = None
-    if fmt == "ascii":
-        tokens, pos = data[pos:].split(), 0
-    normals = None
-    for name, count, props in elements:
-        got, pos = render._read_element(fmt, props, count, data, pos, tokens, path, name)
-        if name == "vertex":
-            if all(k in got for k in ("nx", "ny", "nz")):
-                normals = np.ascontiguousarray(np.stack([np.asarray(got[k], np.float64) for k in ("nx", "ny", "nz")], axis=1).reshape(-1, 3))
-            break
-    return vertices, faces, colours, normals
+    path, _, got = render.read_ply(path)
+    vert, normals = got.get("vertex", {}), None
+    if all(k in vert for k in ("nx", "ny", "nz")):
+        normals = np.ascontiguousarray(np.stack([np.asarray(vert[k], np.float64) for k in ("nx", "ny", "nz")], axis=1).reshape(-1, 3))
+    return render.ply_mesh(path, got) + (normals,)
 
 
 def _tables(tables, who):
@@ -177,12 +164,7 @@ def shade(vis, xy, vdepth, faces, colours, vertices, normals, poses, K, lights, 
     if mode not in _MODES:
         raise ValueError(f"{who}: mode must be 'smooth' or 'flat'")
     mode = _MODES[mode]
-    vis = _lib.on_device(vis, torch.int64, (None, None, None), who, "vis")
-    N, H, W = vis.shape
-    xy = _lib.on_device(xy, torch.int32, (N, None, 2), who, "xy")
-    V = xy.shape[1]
-    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), who, "vdepth")
-    faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
+    vis, xy, vdepth, faces, N, H, W, V, F = render.key_inputs(who, vis, xy, vdepth, faces)
     colours = _lib.on_device(colours, torch.uint8, (V, 3), who, "colours")
     if mode == FLAT:
         vertices, normals = _lib.on_device(vertices, torch.float32, (V, 3), who, "vertices"), None
@@ -192,14 +174,9 @@ def shade(vis, xy, vdepth, faces, colours, vertices, normals, poses, K, lights, 
     decode = _lib.on_device(decode, torch.float64, (256,), who, "decode")
     encode = _lib.on_device(encode, torch.uint8, (None,), who, "encode")
     rows = _lights(lights, who)
-    dev = vis.device
-    rgba, depth, unlit = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev),
-                                                      torch.empty(N, H, W, dtype=torch.float32, device=dev),
-                                                      torch.empty(N, dtype=torch.int32, device=dev))
-    if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W) or tuple(unlit.shape) != (N,):
-        raise ValueError(f"{who}: out must be rgba (N,H,W,4), depth (N,H,W) and unlit (N,)")
+    rgba, depth, unlit = render.resolve_out(who, out, N, H, W, vis.device, unlit=True)
     host_lights = (ctypes.c_double * max(1, rows.size))(*rows.reshape(-1).tolist())
-    _call("gpl_shade", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(faces.shape[0]), _lib.ptr(colours),
+    _call("gpl_shade", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(colours),
           _lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(poses), K if isinstance(K, ctypes.Array) else render._k9(K), host_lights,
           _lib.i(len(rows)), ctypes.c_double(ambient), _lib.ptr(decode), _lib.ptr(encode), _lib.i(encode.shape[0]), _lib.i(mode), _lib.i(N),
           _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.ptr(unlit), _lib.stream_ptr())
@@ -207,23 +184,24 @@ def shade(vis, xy, vdepth, faces, colours, vertices, normals, poses, K, lights, 
 
 
 # ------------------------------------------------------------------------------------------------ the renderer
-class ShadedMeshRenderer:
+class ShadedMeshRenderer(render.Renderer):
     """vertices f32 (V,3), faces int32 (F,3), colours u8 (V,3), poses f32 (N,4,4), all on the device -> rgba u8 (N,H,W,4), depth f32
     (N,H,W), clipped int32 (N,) as render.MeshRenderer returns them (same poses, K, pixel centres, znear), + unlit int32 (N,):
     the covered pixels of a view that had no usable normal and show the ambient term alone.
     lights: (L,4) rows x, y, z, intensity in CAMERA coordinates (OpenCV) and model units, L <= 16; ambient: irradiance added
     everywhere; tables: (decode, encode) as srgb_tables / linear_tables return them; mode: "smooth" (vertex normals, interpolated
     perspective-correctly) or "flat" (the face's own normal)."""
+    who = "ShadedMeshRenderer"
+    no_colour = "the mesh has no vertex colours: pass colour=(r, g, b)"
+    counters = ("unlit",)
 
     def __init__(self, H=480, W=640, K=TEMPLATE_K, znear=1e-3, lights=None, ambient=0.0, tables=None, mode="smooth"):
-        who = "ShadedMeshRenderer"
-        self.H, self.W, self.znear = int(H), int(W), float(znear)
-        self._K = render._k9(K)
+        super().__init__(H, W, K, znear)
         if mode not in _MODES:
-            raise ValueError(f"{who}: mode must be 'smooth' or 'flat'")
+            raise ValueError(f"{self.who}: mode must be 'smooth' or 'flat'")
         self.mode = _MODES[mode]
-        self.lights, self.ambient = _lights(lights, who), float(ambient)
-        self._decode, self._encode = _tables(srgb_tables() if tables is None else tables, who)
+        self.lights, self.ambient = _lights(lights, self.who), float(ambient)
+        self._decode, self._encode = _tables(srgb_tables() if tables is None else tables, self.who)
         self._device_tables = {}
 
     def _on(self, dev):
@@ -231,41 +209,23 @@ class ShadedMeshRenderer:
             self._device_tables[dev] = (self._decode.to(dev), self._encode.to(dev))
         return self._device_tables[dev]
 
-    @torch.no_grad()
     def __call__(self, vertices, faces, colours, poses, normals=None, views_per_call=None, colour=None, on_clipped="raise"):
         """`colours=None` needs `colour=(r, g, b)`, painted on every vertex.  `normals` f64 (V,3) on the device (from the model
         file) are used in smooth mode; None computes them with vertex_normals.  Chunking, the clipped-view error and its host
         synchronisation are MeshRenderer's."""
-        who = "ShadedMeshRenderer"
-        if on_clipped not in ("raise", "ignore"):
-            raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
-        vertices = _lib.on_device(vertices, torch.float32, (None, 3), who, "vertices")
-        faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
-        poses = _lib.on_device(poses, torch.float32, (None, 4, 4), who, "poses")
-        V, F, N = vertices.shape[0], faces.shape[0], poses.shape[0]
-        dev = vertices.device
-        if colours is None:
-            if colour is None:
-                raise ValueError(f"{who}: the mesh has no vertex colours: pass colour=(r, g, b)")
-            colours = torch.tensor([colour], dtype=torch.uint8, device=dev).expand(V, 3)
-        colours = _lib.on_device(colours, torch.uint8, (V, 3), who, "colours")
+        return self._draw(vertices, faces, poses, views_per_call, on_clipped, colours=colours, colour=colour, normals=normals)
+
+    def _prepare(self, vertices, faces, poses, colours, colour, normals):
+        V, dev = vertices.shape[0], vertices.device
+        colours = self._colours(V, colours, colour, dev)
         if self.mode == SMOOTH:
-            normals = vertex_normals(vertices, faces) if normals is None else _lib.on_device(normals, torch.float64, (V, 3), who, "normals")
-        decode, encode = self._on(dev)
-        H, W = self.H, self.W
-        step = render.views_step(views_per_call, H, W)
-        rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
-        depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-        clipped = torch.empty(N, dtype=torch.int32, device=dev)
-        unlit = torch.empty(N, dtype=torch.int32, device=dev)
-        buffers = render.KeyBuffers(min(N, step), V, F, H, W, dev)
-        for _, a, b in _lib.chunked(N, step):
-            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, clipped[a:b])
-            shade(keys, pxy, pz, faces, colours, vertices, normals, poses[a:b], self._K, self.lights, self.ambient, decode, encode, self.mode,
-                  out=(rgba[a:b], depth[a:b], unlit[a:b]))
-        if on_clipped == "raise":
-            render.raise_clipped(who, clipped, F, self.znear)
-        return {"rgba": rgba, "depth": depth, "clipped": clipped, "unlit": unlit}
+            normals = vertex_normals(vertices, faces) if normals is None else _lib.on_device(normals, torch.float64, (V, 3), self.who, "normals")
+        return faces, colours, vertices, normals, poses, self._on(dev)
+
+    def _resolve_chunk(self, state, keys, pxy, pz, a, b, out):
+        faces, colours, vertices, normals, poses, tables = state
+        shade(keys, pxy, pz, faces, colours, vertices, normals, poses[a:b], self._K, self.lights, self.ambient, *tables, self.mode,
+              out=(out["rgba"][a:b], out["depth"][a:b], out["unlit"][a:b]))
 
 
 def _host_mesh(mesh, who):
@@ -279,15 +239,13 @@ def _host_mesh(mesh, who):
     v, f, c = render._host_mesh(mesh[:3], who)
     n = mesh[3]
     if n is not None:
-        if isinstance(n, torch.Tensor):
-            n = n.detach().cpu().numpy()
-        n = torch.from_numpy(np.ascontiguousarray(np.asarray(n, dtype=np.float64)))
+        n = torch.from_numpy(render.host(n, np.float64))
         if tuple(n.shape) != tuple(v.shape):
             raise ValueError(f"{who}: expected normals (V,3), got {tuple(n.shape)}")
     return v, f, c, n
 
 
-class ShadedMeshTemplates:
+class ShadedMeshTemplates(render.TemplateSet):
     """Drop-in for `model.template_datasets[name]`, beside render.MeshTemplates: item i is the same PandasTensorCollection, .rgb
     (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3) .poses (N,4,4) on the device.
 
@@ -300,53 +258,27 @@ class ShadedMeshTemplates:
     What the lighting model leaves out of Blender's render is listed in the module's docstring; no effect on pose accuracy has
     been measured."""
 
+    who = "ShadedMeshTemplates"
+
     def __init__(self, objects, K=None, device="cuda", target_size=224, H=480, W=640, znear=1e-3, colour=TLESS_GREY, lights=None,
                  ambient=0.0, tables=None, normals="smooth", units_per_metre=1000.0):
         if normals not in ("file", "smooth", "flat"):
             raise ValueError("ShadedMeshTemplates: normals must be 'file', 'smooth' or 'flat'")
-        self.device = torch.device(device)
         self.colour, self.normals = colour, normals
-        K = np.asarray(TEMPLATE_K if K is None else K, dtype=np.float32).reshape(3, 3)
-        self.K = torch.as_tensor(K)
         if lights is None:
             lights = blenderproc_lights(units_per_metre)
-        self.renderer = ShadedMeshRenderer(H, W, K, znear, lights, ambient, tables, "flat" if normals == "flat" else "smooth")
-        self.onboard = TemplateOnboarder(target_size)
-        self._meshes, self._poses = [], []
-        for o, (mesh, poses) in enumerate(objects):
-            m = _host_mesh(mesh, f"ShadedMeshTemplates: object {o}")
-            if m[2] is None and colour is None:
-                raise ValueError(f"ShadedMeshTemplates: object {o} has no vertex colours: pass colour=(r, g, b)")
-            if normals == "file" and m[3] is None:
-                raise ValueError(f"ShadedMeshTemplates: object {o} carries no normals (nx, ny, nz): use normals='smooth' or 'flat'")
-            if isinstance(poses, torch.Tensor):
-                poses = poses.detach().cpu().numpy()
-            p = torch.as_tensor(np.asarray(poses, dtype=np.float32))
-            if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
-                raise ValueError(f"ShadedMeshTemplates: object {o}: expected poses (N, 4, 4), got {tuple(p.shape)}")
-            self._meshes.append(m)
-            self._poses.append(p)
+        super().__init__(objects, lambda K: ShadedMeshRenderer(H, W, K, znear, lights, ambient, tables, "flat" if normals == "flat" else "smooth"),
+                         K, device, target_size)
 
-    def __len__(self):
-        return len(self._meshes)
+    def _host_object(self, o, obj):
+        mesh, poses = obj
+        m = _host_mesh(mesh, f"{self.who}: object {o}")
+        if m[2] is None and self.colour is None:
+            raise ValueError(f"{self.who}: object {o} has no vertex colours: pass colour=(r, g, b)")
+        if self.normals == "file" and m[3] is None:
+            raise ValueError(f"{self.who}: object {o} carries no normals (nx, ny, nz): use normals='smooth' or 'flat'")
+        return m, poses
 
-    @torch.no_grad()
-    def render(self, i):
-        """The device renders of object i: {"rgba", "depth", "clipped", "unlit"}."""
-        if self.device.type != "cuda":
-            raise _lib.GigaPoseHipError("ShadedMeshTemplates needs a GPU device (no CPU fallback)")
-        v, f, c, n = (None if t is None else t.to(self.device) for t in self._meshes[i])
-        try:
-            return self.renderer(v, f, c, self._poses[i].to(self.device), normals=n if self.normals == "file" else None, colour=self.colour)
-        except ValueError as e:
-            raise ValueError(f"ShadedMeshTemplates: object {i}: {e}") from None
-
-    @torch.no_grad()
-    def __getitem__(self, i):
-        rgba = self.render(i)["rgba"]
-        try:
-            out = self.onboard(rgba)
-        except ValueError as e:
-            raise ValueError(f"ShadedMeshTemplates: object {i}: {e}") from None
-        return PandasTensorCollection(infos=pd.DataFrame(), K=self.K.to(self.device), rgb=out["rgb"], mask=out["mask"], M=out["M"],
-                                      poses=self._poses[i].to(self.device))
+    def _render_object(self, mesh, poses):
+        v, f, c, n = mesh
+        return self.renderer(v, f, c, poses, normals=n if self.normals == "file" else None, colour=self.colour)

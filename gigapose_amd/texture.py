@@ -20,12 +20,9 @@ render.py near-plane clipping, shading other than ambient and anti-aliasing.  Th
 import os
 
 import numpy as np
-import pandas as pd
 import torch
 
 from . import _lib, render
-from .onboard import TEMPLATE_K, TemplateOnboarder
-from .tensor_collection import PandasTensorCollection
 
 MAX_TEXTURE = 16384                                 # gigapose_texture.h: GPT_MAX_TEXTURE
 MAX_UV = 32768.0                                    # gigapose_texture.h: GPT_MAX_UV
@@ -57,22 +54,13 @@ def load_textured_ply(path):
     list `texcoord` (six floats: u, v of the three corners) when the file has one, else from the per-vertex pair texture_u /
     texture_v (also u / v, s / t) gathered through the faces.  ValueError: no UVs at all, a texcoord list that does not hold six
     values, a `texnumber` other than 0 (several textures per model are out of scope), and whatever load_ply rejects."""
-    path = os.fspath(path)
-    vertices, faces, colours = render.load_ply(path)
-    with open(path, "rb") as fh:
-        data = fh.read()
-    fmt, elements, pos = render._ply_header(data, path)
+    path, comments, got = render.read_ply(path)
+    vertices, faces, colours = render.ply_mesh(path, got)
     texture_file = None
-    for ln in data[:pos].decode("ascii", "replace").splitlines():
+    for ln in comments:
         w = ln.split(None, 2)
-        if len(w) == 3 and w[0] == "comment" and w[1] == "TextureFile":
+        if len(w) == 3 and w[1] == "TextureFile":
             texture_file = w[2].strip()
-    tokens = None
-    if fmt == "ascii":
-        tokens, pos = data[pos:].split(), 0
-    got = {}
-    for name, count, props in elements:
-        got[name], pos = render._read_element(fmt, props, count, data, pos, tokens, path, name)
     face = got.get("face", {})
     if "texnumber" in face and len(faces) and np.any(np.asarray(face["texnumber"]) != 0):
         raise ValueError(f"load_textured_ply: {path}: a face has texnumber != 0: several textures per model are out of scope")
@@ -132,47 +120,32 @@ def resolve_textured(vis, xy, vdepth, faces, corner_uv, pyramid, size, out=None)
     """gpt_resolve: the keys of render.raster + corner_uv f32 (F,3,2) + the pyramid of a size = (Ht, Wt) texture -> rgba u8
     (N,H,W,4), depth f32 (N,H,W); `out` = (rgba, depth) are buffers to write into."""
     who = "resolve_textured"
-    vis = _lib.on_device(vis, torch.int64, (None, None, None), who, "vis")
-    N, H, W = vis.shape
-    xy = _lib.on_device(xy, torch.int32, (N, None, 2), who, "xy")
-    V = xy.shape[1]
-    vdepth = _lib.on_device(vdepth, torch.float32, (N, V), who, "vdepth")
-    faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
-    F = faces.shape[0]
+    vis, xy, vdepth, faces, N, H, W, V, F = render.key_inputs(who, vis, xy, vdepth, faces)
     corner_uv = _lib.on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
     Ht, Wt = int(size[0]), int(size[1])
     _check_texture_shape((Ht, Wt, 3), who)
     pyramid = _lib.on_device(pyramid, torch.int32, (mip_texels(Ht, Wt),), who, "pyramid")
-    rgba, depth = out if out is not None else (torch.empty(N, H, W, 4, dtype=torch.uint8, device=vis.device),
-                                               torch.empty(N, H, W, dtype=torch.float32, device=vis.device))
-    if tuple(rgba.shape) != (N, H, W, 4) or tuple(depth.shape) != (N, H, W):
-        raise ValueError(f"{who}: out must be rgba (N,H,W,4) and depth (N,H,W)")
+    rgba, depth = render.resolve_out(who, out, N, H, W, vis.device)
     _call("gpt_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(corner_uv),
           _lib.ptr(pyramid), _lib.i(Ht), _lib.i(Wt), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.stream_ptr())
     return rgba, depth
 
 
 # ------------------------------------------------------------------------------------------------ the renderer
-class TexturedMeshRenderer:
+class TexturedMeshRenderer(render.Renderer):
     """vertices f32 (V,3), faces int32 (F,3), corner_uv f32 (F,3,2), texture, poses f32 (N,4,4), all on the device -> rgba u8
     (N,H,W,4), depth f32 (N,H,W), clipped int32 (N,), as render.MeshRenderer returns them (same poses, K, pixel centres, znear).
     texture: rgb u8 (Ht,Wt,3), of which the pyramid is built once per call, or a pyramid built before, as (pyramid, (Ht, Wt)).
     The colour is the filtered texel alone: vertex colours are not an input."""
+    who = "TexturedMeshRenderer"
 
-    def __init__(self, H=480, W=640, K=TEMPLATE_K, znear=1e-3):
-        self.H, self.W, self.znear = int(H), int(W), float(znear)
-        self._K = render._k9(K)
-
-    @torch.no_grad()
     def __call__(self, vertices, faces, corner_uv, texture, poses, views_per_call=None, on_clipped="raise"):
         """Chunking, the clipped-view error and the one host synchronisation are MeshRenderer's."""
-        who = "TexturedMeshRenderer"
-        if on_clipped not in ("raise", "ignore"):
-            raise ValueError(f"{who}: on_clipped must be 'raise' or 'ignore'")
-        vertices = _lib.on_device(vertices, torch.float32, (None, 3), who, "vertices")
-        faces = _lib.on_device(faces, torch.int32, (None, 3), who, "faces")
-        V, F = vertices.shape[0], faces.shape[0]
-        corner_uv = _lib.on_device(corner_uv, torch.float32, (F, 3, 2), who, "corner_uv")
+        return self._draw(vertices, faces, poses, views_per_call, on_clipped, corner_uv=corner_uv, texture=texture)
+
+    def _prepare(self, vertices, faces, poses, corner_uv, texture):
+        who = self.who
+        corner_uv = _lib.on_device(corner_uv, torch.float32, (faces.shape[0], 3, 2), who, "corner_uv")
         if isinstance(texture, (tuple, list)):
             pyramid, size = texture
             size = (int(size[0]), int(size[1]))
@@ -181,29 +154,11 @@ class TexturedMeshRenderer:
         else:
             texture = _lib.on_device(texture, torch.uint8, (None, None, 3), who, "texture")
             _check_texture_shape(texture.shape, who)
-            pyramid, size = None, tuple(texture.shape[:2])
-        poses = _lib.on_device(poses, torch.float32, (None, 4, 4), who, "poses")
-        N, dev = poses.shape[0], vertices.device
-        if pyramid is None:
-            pyramid = build_mips(texture)
-        H, W = self.H, self.W
-        step = render.views_step(views_per_call, H, W)
-        rgba = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
-        depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
-        clipped = torch.empty(N, dtype=torch.int32, device=dev)
-        buffers = render.KeyBuffers(min(N, step), V, F, H, W, dev)
-        for _, a, b in _lib.chunked(N, step):
-            keys, pxy, pz = buffers.draw(vertices, faces, poses[a:b], self._K, self.znear, clipped[a:b])
-            resolve_textured(keys, pxy, pz, faces, corner_uv, pyramid, size, out=(rgba[a:b], depth[a:b]))
-        if on_clipped == "raise":
-            render.raise_clipped(who, clipped, F, self.znear)
-        return {"rgba": rgba, "depth": depth, "clipped": clipped}
+            pyramid, size = build_mips(texture), tuple(texture.shape[:2])
+        return faces, corner_uv, pyramid, size
 
-
-def _host(a, dtype):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return torch.from_numpy(np.array(a, dtype=dtype, order="C"))          # a copy: PIL hands out read-only arrays
+    def _resolve_chunk(self, state, keys, pxy, pz, a, b, out):
+        resolve_textured(keys, pxy, pz, *state, out=(out["rgba"][a:b], out["depth"][a:b]))
 
 
 def _host_textured_mesh(mesh, texture, who):
@@ -214,7 +169,7 @@ def _host_textured_mesh(mesh, texture, who):
         mesh = load_textured_ply(mesh)
     if not isinstance(mesh, dict) or not all(k in mesh for k in ("vertices", "faces", "corner_uv")):
         raise ValueError(f"{who}: the mesh must be a PLY path or a dict with vertices, faces and corner_uv")
-    v, f, uv = _host(mesh["vertices"], np.float32), _host(mesh["faces"], np.int32), _host(mesh["corner_uv"], np.float32)
+    v, f, uv = (torch.from_numpy(render.host(mesh[k], t)) for k, t in (("vertices", np.float32), ("faces", np.int32), ("corner_uv", np.float32)))
     if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or tuple(uv.shape) != (f.shape[0], 3, 2):
         raise ValueError(f"{who}: expected vertices (V,3), faces (F,3), corner_uv (F,3,2), got {tuple(v.shape)}, {tuple(f.shape)}, {tuple(uv.shape)}")
     if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
@@ -226,12 +181,12 @@ def _host_textured_mesh(mesh, texture, who):
         texture = name if base is None or os.path.isabs(name) else os.path.join(base, name)
     if isinstance(texture, (str, os.PathLike)):
         texture = load_texture(texture)
-    t = _host(texture, np.uint8)
+    t = torch.from_numpy(render.host(texture, np.uint8))
     _check_texture_shape(t.shape, who)
     return v, f, uv, t
 
 
-class TexturedMeshTemplates:
+class TexturedMeshTemplates(render.TemplateSet):
     """Drop-in for `model.template_datasets[name]`, beside render.MeshTemplates: item i is the same PandasTensorCollection, .rgb
     (N,3,T,T) .mask (N,T,T) .K (3,3) .M (N,3,3) .poses (N,4,4) on the device.
 
@@ -239,47 +194,16 @@ class TexturedMeshTemplates:
     rgb array (Ht,Wt,3) or None to take the mesh's `texture_file` next to the PLY; poses (N,4,4) as for MeshTemplates.  Meshes
     and textures stay on the HOST; every __getitem__ uploads them, builds the pyramid, renders the N views on the device and hands
     the device renders to TemplateOnboarder: no render crosses PCIe.  Vertex colours in the mesh are ignored."""
+    who = "TexturedMeshTemplates"
 
     def __init__(self, objects, K=None, device="cuda", target_size=224, H=480, W=640, znear=1e-3):
-        self.device = torch.device(device)
-        K = np.asarray(TEMPLATE_K if K is None else K, dtype=np.float32).reshape(3, 3)
-        self.K = torch.as_tensor(K)
-        self.renderer = TexturedMeshRenderer(H, W, K, znear)
-        self.onboard = TemplateOnboarder(target_size)
-        self._meshes, self._poses = [], []
-        for o, obj in enumerate(objects):
-            if len(obj) != 3:
-                raise ValueError(f"TexturedMeshTemplates: object {o}: expected (mesh, texture, poses)")
-            mesh, texture, poses = obj
-            m = _host_textured_mesh(mesh, texture, f"TexturedMeshTemplates: object {o}")
-            if isinstance(poses, torch.Tensor):
-                poses = poses.detach().cpu().numpy()
-            p = torch.as_tensor(np.asarray(poses, dtype=np.float32))
-            if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
-                raise ValueError(f"TexturedMeshTemplates: object {o}: expected poses (N, 4, 4), got {tuple(p.shape)}")
-            self._meshes.append(m)
-            self._poses.append(p)
+        super().__init__(objects, lambda K: TexturedMeshRenderer(H, W, K, znear), K, device, target_size)
 
-    def __len__(self):
-        return len(self._meshes)
+    def _host_object(self, o, obj):
+        if len(obj) != 3:
+            raise ValueError(f"{self.who}: object {o}: expected (mesh, texture, poses)")
+        mesh, texture, poses = obj
+        return _host_textured_mesh(mesh, texture, f"{self.who}: object {o}"), poses
 
-    @torch.no_grad()
-    def render(self, i):
-        """The device renders of object i: {"rgba", "depth", "clipped"}."""
-        if self.device.type != "cuda":
-            raise _lib.GigaPoseHipError("TexturedMeshTemplates needs a GPU device (no CPU fallback)")
-        v, f, uv, t = (a.to(self.device) for a in self._meshes[i])
-        try:
-            return self.renderer(v, f, uv, t, self._poses[i].to(self.device))
-        except ValueError as e:
-            raise ValueError(f"TexturedMeshTemplates: object {i}: {e}") from None
-
-    @torch.no_grad()
-    def __getitem__(self, i):
-        rgba = self.render(i)["rgba"]
-        try:
-            out = self.onboard(rgba)
-        except ValueError as e:
-            raise ValueError(f"TexturedMeshTemplates: object {i}: {e}") from None
-        return PandasTensorCollection(infos=pd.DataFrame(), K=self.K.to(self.device), rgb=out["rgb"], mask=out["mask"], M=out["M"],
-                                      poses=self._poses[i].to(self.device))
+    def _render_object(self, mesh, poses):
+        return self.renderer(*mesh, poses)

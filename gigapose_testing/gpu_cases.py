@@ -1,5 +1,7 @@
-"""What the GPU tests of the stages behind the matcher (tests/test_gpu_refine.py, test_gpu_verify.py, test_gpu_maskfit.py) share:
-the upload of a read-only case, the bit-for-bit comparison and the five drawn pairs."""
+"""What the GPU tests of the stages around the matcher share.  All of them (the renderers in front: tests/test_gpu_render.py,
+test_gpu_texture.py, test_gpu_shade.py, test_gpu_planted_keys.py; the stages behind: test_gpu_refine.py, test_gpu_verify.py,
+test_gpu_maskfit.py): the upload of a read-only case and the bit-for-bit comparison.  The renderers: a random rotation, a pose, a
+grey mesh and the camera of a 240 x 320 frame.  The stages behind: the five drawn pairs."""
 import functools
 
 import numpy as np
@@ -9,6 +11,8 @@ from . import raster_ref
 from . import refine_cases as rc
 
 DEV = "cuda"
+ZNEAR = 1e-3
+K_SMALL = np.asarray([[300.0, 0.0, 160.0], [0.0, 302.0, 120.0], [0.0, 0.0, 1.0]], np.float32)      # for 240 x 320 frames
 
 
 def on_gpu(a):
@@ -18,9 +22,24 @@ def on_gpu(a):
 
 def assert_bits(got, want, what):
     got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    want = np.asarray(want)
+    want = want.cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want)
     assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
     assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
+
+
+def rotation(rs):
+    q, _ = np.linalg.qr(rs.normal(size=(3, 3)))
+    return q * np.sign(np.linalg.det(q))
+
+
+def pose(R, t):
+    P = np.eye(4)
+    P[:3, :3], P[:3, 3] = R, t
+    return P
+
+
+def grey(v, value=102):
+    return np.full((len(v), 3), value, np.uint8)
 
 
 @functools.lru_cache(maxsize=None)

@@ -147,34 +147,52 @@ def raster(xy, depth, faces, H, W, rule="top_left"):
     return vis, clipped
 
 
-def resolve(vis, xy, depth, faces, colours):
-    """-> rgba (N,H,W,4) u8, zdepth (N,H,W) f32."""
-    vis, xy, depth, faces = np.asarray(vis), np.asarray(xy), np.asarray(depth, np.float32), np.asarray(faces)
-    colours = np.asarray(colours, np.uint8).astype(np.float64)
-    N, H, W = vis.shape
+def drawn(vis, xy, depth, faces, face_shift=0):
+    """What the three resolves (this file's, texture_ref's, shade_ref's) share: per view n and per face f that a covered key of
+    the view names, that is < F and that sets up, yields (n, f, tri, py, px, e, dirs, r, z) -- tri as `setup` returns it, the
+    pixels (int64) whose key names f, their edge values e[k] with the edges' directions, r[k] = 1 / depth of corner k (apart from
+    e, so that a caller can weight differently: the mutants), and the depth z (f32) the keys carry.  face_shift = 32 reads the
+    face from the wrong half of the key (a mutant).  vis: uint64, or int64 holding the same bits."""
+    vis, xy, depth, faces = np.asarray(vis).view(np.uint64), np.asarray(xy), np.asarray(depth, np.float32), np.asarray(faces)
     V = depth.shape[1]
-    rgba = np.zeros((N, H, W, 4), np.uint8)
-    zdepth = np.zeros((N, H, W), np.float32)
-    face_of = (vis & np.uint64(0xFFFFFFFF)).astype(np.int64)
-    for n in range(N):
+    face_of = ((vis >> np.uint64(face_shift)) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    for n in range(vis.shape[0]):
         covered = vis[n] != EMPTY_KEY
         for f in np.unique(face_of[n][covered]):
-            if f >= len(faces):
-                continue
-            tri, _ = setup(xy[n], faces, int(f), V)
+            tri = setup(xy[n], faces, int(f), V)[0] if f < len(faces) else None
             if tri is None:
                 continue
             py, px = np.nonzero(covered & (face_of[n] == f))
             py, px = py.astype(np.int64), px.astype(np.int64)
-            e, _ = edge_values(tri[1], px, py)
-            t = [e[k].astype(np.float64) * (1.0 / np.float64(depth[n, i])) for k, i in enumerate(tri[0])]
-            q = (t[0] + t[1]) + t[2]
-            for c in range(3):
-                c0, c1, c2 = (colours[i, c] for i in tri[0])
-                v = np.floor(((t[0] * c0 + t[1] * c1) + t[2] * c2) / q + 0.5)
-                rgba[n, py, px, c] = np.clip(v, 0.0, 255.0).astype(np.uint8)
-            rgba[n, py, px, 3] = 255
-            zdepth[n, py, px] = (vis[n, py, px] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+            e, dirs = edge_values(tri[1], px, py)
+            with np.errstate(all="ignore"):
+                r = [1.0 / np.float64(depth[n, i]) for i in tri[0]]
+            yield n, int(f), tri, py, px, e, dirs, r, (vis[n, py, px] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+
+
+def weights(e, r):
+    """-> [t_0, t_1, t_2], q: t_k = (float64)e_k * r_k, q = (t_0 + t_1) + t_2."""
+    t = [e[k].astype(np.float64) * r[k] for k in range(3)]
+    return t, (t[0] + t[1]) + t[2]
+
+
+def colour_bytes(t, q, c0, c1, c2):
+    """floor(((t_0 c_0 + t_1 c_1) + t_2 c_2) / q + 1/2), clamped to [0, 255]: float64, not yet a byte (a NaN stays one)."""
+    return np.clip(np.floor(((t[0] * c0 + t[1] * c1) + t[2] * c2) / q + 0.5), 0.0, 255.0)
+
+
+def resolve(vis, xy, depth, faces, colours):
+    """-> rgba (N,H,W,4) u8, zdepth (N,H,W) f32."""
+    colours = np.asarray(colours, np.uint8).astype(np.float64)
+    N, H, W = np.asarray(vis).shape
+    rgba = np.zeros((N, H, W, 4), np.uint8)
+    zdepth = np.zeros((N, H, W), np.float32)
+    for n, _, tri, py, px, e, _, r, z in drawn(vis, xy, depth, faces):
+        t, q = weights(e, r)
+        for c in range(3):
+            rgba[n, py, px, c] = colour_bytes(t, q, *(colours[i, c] for i in tri[0])).astype(np.uint8)
+        rgba[n, py, px, 3] = 255
+        zdepth[n, py, px] = z
     return rgba, zdepth
 
 

@@ -57,7 +57,7 @@ def vertex_normals(vertices, faces, unit, wrong=None):
 def shade(vis, xy, depth, faces, colours, vertices, normals, poses, K, lights, ambient, decode, encode, mode, wrong=None, with_E=False):
     """-> rgba (N,H,W,4) u8, zdepth (N,H,W) f32, unlit (N,) int32 [, E (N,H,W) float64, NaN where nothing is drawn]."""
     _check(wrong)
-    vis, xy, depth, faces = np.asarray(vis), np.asarray(xy), np.asarray(depth, np.float32), np.asarray(faces)
+    faces = np.asarray(faces)
     col = np.asarray(colours, np.uint8).astype(np.float64)
     P = np.asarray(poses, np.float32).astype(np.float64)
     k = np.asarray(K, np.float32).astype(np.float64).reshape(9)
@@ -66,70 +66,52 @@ def shade(vis, xy, depth, faces, colours, vertices, normals, poses, K, lights, a
     T = len(encode)
     assert len(lights) <= MAX_LIGHTS and decode.shape == (256,) and 256 <= T <= 65536 and mode in (SMOOTH, FLAT)
     ambient, top = np.float64(ambient), np.float64(T - 1)
-    N, H, W = vis.shape
-    V = depth.shape[1]
+    N, H, W = np.asarray(vis).shape
     rgba, zdepth, unlit = np.zeros((N, H, W, 4), np.uint8), np.zeros((N, H, W), np.float32), np.zeros(N, np.int32)
     Emap = np.full((N, H, W), np.nan)
-    shift = np.uint64(32 if wrong == "wrong_key_half" else 0)
-    face_of = ((vis >> shift) & np.uint64(0xFFFFFFFF)).astype(np.int64)
     with np.errstate(all="ignore"):
-        for n in range(N):
-            covered = vis[n] != raster_ref.EMPTY_KEY
+        for n, f, tri, py, px, e, _, r, z in raster_ref.drawn(vis, xy, depth, faces, 32 if wrong == "wrong_key_half" else 0):
             lit = lights.copy()
             if wrong == "object_lights":
                 lit[:, :3] = lights[:, :3] @ P[n, :3, :3].T + P[n, :3, 3]
-            for f in np.unique(face_of[n][covered]):
-                if f >= len(faces):
-                    continue
-                tri, _ = raster_ref.setup(xy[n], faces, int(f), V)
-                if tri is None:
-                    continue
-                py, px = np.nonzero(covered & (face_of[n] == f))
-                py, px = py.astype(np.int64), px.astype(np.int64)
-                e, _ = raster_ref.edge_values(tri[1], px, py)
-                if wrong == "screen_weights":
-                    t = [e[j].astype(np.float64) for j in range(3)]
+            t, q = raster_ref.weights(e, [1.0, 1.0, 1.0] if wrong == "screen_weights" else r)
+            if mode == FLAT:
+                g = [np.full(len(px), c) for c in face_cross(vertices, faces[f][None])[0]]
+            else:
+                n0, n1, n2 = (np.asarray(normals, np.float64)[i] for i in tri[0])
+                g = [(t[0] * n0[j] + t[1] * n1[j]) + t[2] * n2[j] for j in range(3)]
+            m = [(P[n, row, 0] * g[0] + P[n, row, 1] * g[1]) + P[n, row, 2] * g[2] for row in range(3)]
+            zd = z.astype(np.float64)
+            yn = (py.astype(np.float64) - k[5]) / k[4]
+            xn = ((px.astype(np.float64) - k[2]) - k[1] * yn) / k[0]
+            p = [xn * zd, yn * zd, zd]
+            s = (m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]
+            if wrong != "no_flip":
+                m = [np.where(s > 0, -mj, mj) for mj in m]
+            mm = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]
+            usable = (mm > 0) & (mm < np.inf)
+            unlit[n] += int((~usable).sum())
+            E = np.full(len(px), ambient)
+            for l in range(len(lit)):
+                d = [lit[l, j] - p[j] for j in range(3)]
+                dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+                md = (m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]
+                if wrong == "falloff_1_over_d":
+                    add = (lit[l, 3] * md) / (np.sqrt(mm * dd) * np.sqrt(dd))
                 else:
-                    t = [e[j].astype(np.float64) * (1.0 / np.float64(depth[n, i])) for j, i in enumerate(tri[0])]
-                q = (t[0] + t[1]) + t[2]
-                if mode == FLAT:
-                    g = [np.full(len(px), c) for c in face_cross(vertices, faces[f][None])[0]]
-                else:
-                    n0, n1, n2 = (np.asarray(normals, np.float64)[i] for i in tri[0])
-                    g = [(t[0] * n0[j] + t[1] * n1[j]) + t[2] * n2[j] for j in range(3)]
-                m = [(P[n, r, 0] * g[0] + P[n, r, 1] * g[1]) + P[n, r, 2] * g[2] for r in range(3)]
-                z = (vis[n, py, px] >> np.uint64(32)).astype(np.uint32).view(np.float32)
-                zd = z.astype(np.float64)
-                yn = (py.astype(np.float64) - k[5]) / k[4]
-                xn = ((px.astype(np.float64) - k[2]) - k[1] * yn) / k[0]
-                p = [xn * zd, yn * zd, zd]
-                s = (m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]
-                if wrong != "no_flip":
-                    m = [np.where(s > 0, -mj, mj) for mj in m]
-                mm = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]
-                usable = (mm > 0) & (mm < np.inf)
-                unlit[n] += int((~usable).sum())
-                E = np.full(len(px), ambient)
-                for l in range(len(lit)):
-                    d = [lit[l, j] - p[j] for j in range(3)]
-                    dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
-                    md = (m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]
-                    if wrong == "falloff_1_over_d":
-                        add = (lit[l, 3] * md) / (np.sqrt(mm * dd) * np.sqrt(dd))
-                    else:
-                        add = (lit[l, 3] * md) / (np.sqrt(mm * dd) * dd)
-                    E = np.where(usable & (md > 0) & (dd > 0), E + add, E)
-                Emap[n, py, px] = E
-                for c in range(3):
-                    c0, c1, c2 = (col[i, c] for i in tri[0])
-                    b = np.clip(np.floor(((t[0] * c0 + t[1] * c1) + t[2] * c2) / q + 0.5), 0.0, 255.0)
-                    b = np.where(np.isnan(b), 0.0, b).astype(np.int64)
-                    w = (decode[b] * E) * top
-                    w = np.floor(w if wrong == "truncate_encode" else w + 0.5)
-                    i = np.where(w >= top, top, np.where(w > 0, w, 0.0)).astype(np.int64)
-                    rgba[n, py, px, c] = encode[i]
-                rgba[n, py, px, 3] = 255
-                zdepth[n, py, px] = z
+                    add = (lit[l, 3] * md) / (np.sqrt(mm * dd) * dd)
+                E = np.where(usable & (md > 0) & (dd > 0), E + add, E)
+            Emap[n, py, px] = E
+            for c in range(3):
+                c0, c1, c2 = (col[i, c] for i in tri[0])
+                b = raster_ref.colour_bytes(t, q, c0, c1, c2)
+                b = np.where(np.isnan(b), 0.0, b).astype(np.int64)
+                w = (decode[b] * E) * top
+                w = np.floor(w if wrong == "truncate_encode" else w + 0.5)
+                i = np.where(w >= top, top, np.where(w > 0, w, 0.0)).astype(np.int64)
+                rgba[n, py, px, c] = encode[i]
+            rgba[n, py, px, 3] = 255
+            zdepth[n, py, px] = z
     return (rgba, zdepth, unlit, Emap) if with_E else (rgba, zdepth, unlit)
 
 

@@ -79,22 +79,18 @@ def _within(x, bound):
 
 
 def _uv_at(e, r, cu, cv):
-    t = [e[k].astype(np.float64) * r[k] for k in range(3)]
-    q = (t[0] + t[1]) + t[2]
+    t, q = raster_ref.weights(e, r)
     u = ((t[0] * cu[0] + t[1] * cu[1]) + t[2] * cu[2]) / q
     v = ((t[0] * cv[0] + t[1] * cv[1]) + t[2] * cv[2]) / q
     return q, u, v
 
 
-def _face_lod(tri, face_row, cuv, depth_n, px, py, sizes, interp, swap_uv, l0_shift):
-    """u, v, bad, rho2, l0, two, w of the pixels (px, py) that face `tri` owns."""
-    idx, pts, _ = tri
-    swapped = idx[1] != int(face_row[1])
+def _face_lod(tri, face_row, cuv, e, dirs, r, sizes, swap_uv, l0_shift):
+    """u, v, bad, rho2, l0, two, w of the pixels that face `tri` owns: e, dirs, r as raster_ref.drawn yields them."""
+    swapped = tri[0][1] != int(face_row[1])
     order = (0, 2, 1) if (swapped and swap_uv) else (0, 1, 2)
     cu = [np.float64(cuv[k, 0]) for k in order]
     cv = [np.float64(cuv[k, 1]) for k in order]
-    r = [1.0 / np.float64(depth_n[i]) if interp == "perspective" else np.float64(1.0) for i in idx]
-    e, dirs = raster_ref.edge_values(pts, px, py)
     q, u, v = _uv_at(e, r, cu, cv)
     corners_ok = all(bool(_within(c, MAX_UV)) for c in cu + cv)
     bad = ~(_within(u, 2 * MAX_UV) & _within(v, 2 * MAX_UV)) | (not corners_ok)
@@ -106,7 +102,7 @@ def _face_lod(tri, face_row, cuv, depth_n, px, py, sizes, interp, swap_uv, l0_sh
     ax, ay = dsdx * dsdx + dtdx * dtdx, dsdy * dsdy + dtdy * dtdy
     ok = ~((qx <= 0.0) | (qy <= 0.0)) & (ax == ax) & (ay == ay)
     rho2 = np.where(ay > ax, ay, ax)
-    lv, p4 = np.zeros(len(px), np.int64), np.ones(len(px))
+    lv, p4 = np.zeros(len(u), np.int64), np.ones(len(u))
     for k in range(top):
         adv = (lv == k) & (p4 * 4.0 <= rho2)
         p4 = np.where(adv, p4 * 4.0, p4)
@@ -154,24 +150,14 @@ def sample(levels, u, v, l0, two, w, flip_v=True, wrap="repeat"):
 
 
 def _walk(vis, xy, depth, faces, corner_uv, Ht, Wt, interp, swap_uv, l0_shift, rounding):
-    vis, xy, depth, faces = np.asarray(vis).view(np.uint64), np.asarray(xy), np.asarray(depth, np.float32), np.asarray(faces)
+    faces = np.asarray(faces)
     corner_uv = np.asarray(corner_uv, np.float32).reshape(len(faces), 3, 2)
     sizes = mip_sizes(Ht, Wt, rounding)
-    N = vis.shape[0]
-    V = depth.shape[1]
-    face_of = (vis & np.uint64(0xFFFFFFFF)).astype(np.int64)
     with np.errstate(all="ignore"):
-        for n in range(N):
-            covered = vis[n] != raster_ref.EMPTY_KEY
-            for f in np.unique(face_of[n][covered]):
-                if f >= len(faces):
-                    continue
-                tri, _ = raster_ref.setup(xy[n], faces, int(f), V)
-                if tri is None:
-                    continue
-                py, px = np.nonzero(covered & (face_of[n] == f))
-                py, px = py.astype(np.int64), px.astype(np.int64)
-                yield n, int(f), py, px, _face_lod(tri, faces[f], corner_uv[f], depth[n], px, py, sizes, interp, swap_uv, l0_shift)
+        for n, f, tri, py, px, e, dirs, r, z in raster_ref.drawn(vis, xy, depth, faces):
+            if interp != "perspective":                             # mutant: screen-space weights
+                r = [np.float64(1.0)] * 3
+            yield n, f, py, px, z, _face_lod(tri, faces[f], corner_uv[f], e, dirs, r, sizes, swap_uv, l0_shift)
 
 
 def inspect(vis, xy, depth, faces, corner_uv, Ht, Wt, interp="perspective", swap_uv=True, l0_shift=0, rounding="floor", **_):
@@ -181,7 +167,7 @@ def inspect(vis, xy, depth, faces, corner_uv, Ht, Wt, interp="perspective", swap
     out = {k: np.full(shape, np.nan) for k in ("u", "v", "rho2", "w")}
     out.update(l0=np.full(shape, -1, np.int64), two=np.zeros(shape, bool), bad=np.zeros(shape, bool), covered=np.zeros(shape, bool),
                face=np.full(shape, -1, np.int64))
-    for n, f, py, px, d in _walk(vis, xy, depth, faces, corner_uv, Ht, Wt, interp, swap_uv, l0_shift, rounding):
+    for n, f, py, px, _, d in _walk(vis, xy, depth, faces, corner_uv, Ht, Wt, interp, swap_uv, l0_shift, rounding):
         for k, a in d.items():
             out[k][n, py, px] = a
         out["covered"][n, py, px] = True
@@ -192,12 +178,11 @@ def inspect(vis, xy, depth, faces, corner_uv, Ht, Wt, interp="perspective", swap
 def resolve(vis, xy, depth, faces, corner_uv, pyramid, Ht, Wt, interp="perspective", swap_uv=True, flip_v=True, wrap="repeat",
             l0_shift=0, rounding="floor"):
     """-> rgba (N,H,W,4) u8, zdepth (N,H,W) f32.  The keyword defaults are the contract; anything else is a mutant."""
-    vis = np.asarray(vis).view(np.uint64)
     levels = split_levels(pyramid, Ht, Wt, rounding)
-    N, H, W = vis.shape
+    N, H, W = np.asarray(vis).shape
     rgba = np.zeros((N, H, W, 4), np.uint8)
     zdepth = np.zeros((N, H, W), np.float32)
-    for n, f, py, px, d in _walk(vis, xy, depth, faces, corner_uv, Ht, Wt, interp, swap_uv, l0_shift, rounding):
+    for n, f, py, px, z, d in _walk(vis, xy, depth, faces, corner_uv, Ht, Wt, interp, swap_uv, l0_shift, rounding):
         good = ~d["bad"]
         colour = np.zeros((len(px), 3))
         if good.any():
@@ -205,7 +190,7 @@ def resolve(vis, xy, depth, faces, corner_uv, pyramid, Ht, Wt, interp="perspecti
                 colour[good] = sample(levels, d["u"][good], d["v"][good], d["l0"][good], d["two"][good], d["w"][good], flip_v, wrap)
         rgba[n, py, px, :3] = np.clip(np.floor(colour + 0.5), 0.0, 255.0).astype(np.uint8)
         rgba[n, py, px, 3] = 255
-        zdepth[n, py, px] = (vis[n, py, px] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        zdepth[n, py, px] = z
     return rgba, zdepth
 
 

@@ -11,33 +11,10 @@ import torch
 from gigapose_testing import factory, meshes, raster_ref
 from gigapose_testing import synthetic as syn
 from gigapose_testing import texture_ref as tr
+from gigapose_testing.gpu_cases import DEV, K_SMALL, ZNEAR, assert_bits, pose, rotation
+from gigapose_testing.gpu_cases import on_gpu as _t
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-K_SMALL = np.asarray([[300.0, 0.0, 160.0], [0.0, 302.0, 120.0], [0.0, 0.0, 1.0]], np.float32)      # for 240 x 320 frames
-ZNEAR = 1e-3
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def assert_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
-    want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} vs {want.dtype} {want.shape}"
-    assert got.tobytes() == want.tobytes(), f"{what}: {int((got != want).sum())} of {got.size} values differ"
-
-
-def rotation(rs):
-    q, _ = np.linalg.qr(rs.normal(size=(3, 3)))
-    return q * np.sign(np.linalg.det(q))
-
-
-def pose(R, t):
-    P = np.eye(4)
-    P[:3, :3], P[:3, 3] = R, t
-    return P
 
 
 def frontal_K(H, W, focal=256.0, cx=None, cy=None):

@@ -22,33 +22,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gigapose_amd import onboard, render  # noqa: E402
 from gigapose_testing import meshes, raster_ref  # noqa: E402
+from gigapose_testing.probe_timing import measure  # noqa: E402
+from gigapose_testing.probe_timing import line as timing_line  # noqa: E402
 
 DEV = "cuda"
 H, W = 480, 640
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3   # us
-
-
-def measure(stages, reps, warmup):
-    times = {k: [] for k in stages}
-    for r in range(warmup + reps):
-        for k, fn in stages.items():      # alternating: every stage sees the same machine state
-            t = timed(fn)
-            if r >= warmup:
-                times[k].append(t)
-    return times
-
-
 def line(name, v, what):
-    v = np.sort(np.asarray(v))
-    return f"   {name:8s}: median {float(np.median(v)):9.1f} us   min {v[0]:9.1f}   max {v[-1]:9.1f}   {what}"
+    return timing_line(name, v, what, width=8)
 
 
 def main():

@@ -14,7 +14,6 @@ restatement bit for bit, and that check does fail the run).  Writes the figures 
 profiles/texture_templates.txt)."""
 import argparse
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -25,40 +24,16 @@ sys.path.insert(0, ROOT)
 from gigapose_amd import onboard, render, texture  # noqa: E402
 from gigapose_testing import meshes  # noqa: E402
 from gigapose_testing import texture_ref as tr  # noqa: E402
+from gigapose_testing.probe_timing import commit, measure  # noqa: E402
+from gigapose_testing.probe_timing import line as timing_line  # noqa: E402
 
 DEV = "cuda"
 H, W = 480, 640
 TEX = 2048
 
 
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3   # us
-
-
-def measure(stages, reps, warmup):
-    times = {k: [] for k in stages}
-    for r in range(warmup + reps):
-        for k, fn in stages.items():      # alternating: every stage sees the same machine state
-            t = timed(fn)
-            if r >= warmup:
-                times[k].append(t)
-    return times
-
-
 def line(name, v, what):
-    v = np.sort(np.asarray(v))
-    return f"   {name:11s}: median {float(np.median(v)):9.1f} us   min {v[0]:9.1f}   max {v[-1]:9.1f}   {what}"
-
-
-def commit():
-    r = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True)
-    dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain"], capture_output=True, text=True).stdout.strip()
-    return (r.stdout.strip() + (" + uncommitted changes" if dirty else "")) if r.returncode == 0 else "unknown (no git here)"
+    return timing_line(name, v, what, width=11)
 
 
 def main():
