@@ -1,7 +1,7 @@
 // The walk of a workgroup over a pair's box of the render library's 64-bit keys, shared by accumulate_kernel (refine/gpf_refine.hip),
 // counts_kernel (verify/gpv_verify.hip) and moments_kernel (maskfit/gpm_maskfit.hip): written ONCE, so the three visit the same
 // pixels in the same order, judge a detection's mask slice by the same rule and merge their integer sums the same way.  Header
-// only, compiled into each of the three libraries.
+// only, compiled into each of the three libraries (and, for rank_of's constants and the sums alone, into gtinfo/gpg_gtinfo.hip).
 // Grid (chunk of kChunk box pixels, pair).  The box is walked row by row, kThreads consecutive box pixels per step, so a wave's
 // 8-byte key loads are contiguous within a row; a thread visits kPix pixels.  What a kernel does per pixel, the order of its pair
 // rules and the box test, and which totals it adds to global memory stay in the kernel.

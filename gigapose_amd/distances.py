@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluate import group_estimates, match_greedy, pose_matrix, read_estimates
+from .evaluate import check_min_visib, counted, group_estimates, match_greedy, pose_matrix, read_estimates, visibilities
 
 MAX_PAIRS_PER_CALL = 65535                           # the grid's second dimension (gigapose_dist.h: Limits)
 MAX_VERTICES = 1 << 20
@@ -137,9 +137,10 @@ def is_symmetric(model_info):
     return bool(model_info.get("symmetries_discrete")) or bool(model_info.get("symmetries_continuous"))
 
 
-def recall_from_add_errors(per_target, diameters, symmetric, tau_max=100.0):
-    """[(target, {"add" (E,G), "adds" (E,G)})] -> the dict AddScorer.score returns.  `symmetric`: {obj_id: bool}."""
-    total = sum(e["add"].shape[1] for _, e in per_target)
+def recall_from_add_errors(per_target, diameters, symmetric, tau_max=100.0, min_visib=None):
+    """[(target, {"add" (E,G), "adds" (E,G)})] -> the dict AddScorer.score returns.  `symmetric`: {obj_id: bool}.  min_visib: only
+    the ground truths with errors["visib"] >= min_visib are counted (evaluate.recall_from_errors)."""
+    valid, total = counted(per_target, min_visib, "add")
     den = float(max(total, 1))
     taus = [tau_max * j / AUC_STEPS for j in range(1, AUC_STEPS + 1)]
 
@@ -150,8 +151,9 @@ def recall_from_add_errors(per_target, diameters, symmetric, tau_max=100.0):
 
     out = {"targets": total}
     for which in ("add", "adds", "add_s"):
-        out["recall_" + which] = sum(match_greedy(pick(t, e, which), 0.1 * diameters[int(t["obj_id"])]) for t, e in per_target) / den
-        curve = [sum(match_greedy(pick(t, e, which), tau) for t, e in per_target) / den for tau in taus]
+        out["recall_" + which] = sum(match_greedy(pick(t, e, which), 0.1 * diameters[int(t["obj_id"])], ok)
+                                     for (t, e), ok in zip(per_target, valid)) / den
+        curve = [sum(match_greedy(pick(t, e, which), tau, ok) for (t, e), ok in zip(per_target, valid)) / den for tau in taus]
         out["auc_" + which] = float(np.mean(curve))
     return out
 
@@ -160,7 +162,9 @@ class AddScorer:
     """ADD / ADD-S recall and AUC of a set of estimates.
       models   {obj_id: {"vertices" (V,3), ["diameter"], ["symmetries_discrete"], ["symmetries_continuous"]}}
       targets  [{"scene_id", "im_id", "obj_id", "inst_count"}]             (test_targets_bop19.json)
-      gts      {(scene_id, im_id): [{"obj_id", "cam_R_m2c" 9, "cam_t_m2c" 3}]}   (scene_gt.json; every listed instance counts)
+      gts      {(scene_id, im_id): [{"obj_id", "cam_R_m2c" 9, "cam_t_m2c" 3, ["visib_fract"]}]}   (scene_gt.json [+ scene_gt_info.json])
+      min_visib  None: every listed instance counts; a number: as PoseScorer's -- a ground truth whose "visib_fract" is below it
+               still absorbs an estimate but counts neither for nor against, one without the key raises
     No cameras are needed.  A model without "diameter" gets model_diameter(vertices).  Estimates are kept and matched as PoseScorer
     does (evaluate.group_estimates: the inst_count highest-scored estimates per target; evaluate.match_greedy per threshold).
     score() ->
@@ -173,8 +177,9 @@ class AddScorer:
                                     tables); no toolkit is consulted, other toolkits integrate differently
       "targets"                     ground truths counted."""
 
-    def __init__(self, models, targets, gts, k=20, tau_max=100.0, device="cuda"):
+    def __init__(self, models, targets, gts, k=20, tau_max=100.0, device="cuda", min_visib=None):
         self.models, self.targets, self.gts = models, list(targets), gts
+        self.min_visib = check_min_visib("AddScorer", min_visib)
         self.k, self.tau_max, self.device = _check_k("AddScorer", k), float(tau_max), device
         if not self.tau_max > 0:
             raise ValueError("AddScorer: tau_max must be positive")
@@ -199,6 +204,7 @@ class AddScorer:
     def errors(self, estimates):
         """-> [(target, {"add" (E,G), "adds" (E,G)})] as numpy, E estimates kept x G ground truths."""
         groups = self.pairs(estimates)
+        visib = None if self.min_visib is None else [visibilities("AddScorer", g) for _, _, g in groups]      # raises before any GPU work
         out = [None] * len(groups)
         for obj in sorted({int(t["obj_id"]) for t, _, _ in groups}):
             est, gt, where = [], [], []
@@ -221,7 +227,10 @@ class AddScorer:
                     out[gi] = (groups[gi][0], dict(add=add[sl].reshape(E, G), adds=adds[sl].reshape(E, G)))
                 else:
                     out[gi] = (groups[gi][0], dict(add=np.zeros((E, G)), adds=np.zeros((E, G))))
+        if visib is not None:
+            for (_, e), v in zip(out, visib):
+                e["visib"] = v
         return out
 
     def score(self, estimates):
-        return recall_from_add_errors(self.errors(estimates), self.diameters(), self.symmetric, self.tau_max)
+        return recall_from_add_errors(self.errors(estimates), self.diameters(), self.symmetric, self.tau_max, self.min_visib)

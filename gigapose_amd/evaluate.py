@@ -11,7 +11,8 @@ numpy and tests/test_gpu_eval.py holds the kernels to it bit for bit).
   vsd_errors(mesh, est, gt, K, depth_test, frame, diameter, ...)   renders both pose sets, -> {"errors", "counts", "clipped"}
   PoseScorer(models, targets, gts, cameras)          .score_csv(path) / .score(estimates) -> recalls, ar_mssd, ar_mspd, ar_vsd, ar
 ADD, ADD-S and the model diameter are gigapose_amd/distances.py (libgigapose_dist.so: means over integers, so their bits do not
-depend on the summation order).  Out of scope: reading BOP json and depth PNG files (PoseScorer is handed their contents), the bop18 visibility mode, near-plane clipping (an estimate that puts a vertex
+depend on the summation order).  The BOP-19 visibility filter of the ground truths is PoseScorer's min_visib over the "visib_fract" gigapose_amd/gtinfo.py computes.
+Out of scope: reading BOP json and depth PNG files (PoseScorer is handed their contents), the bop18 visibility mode, near-plane clipping (an estimate that puts a vertex
 behind the camera drops triangles: it is reported and scores VSD 1).  There is no CPU fallback: a missing library is an error.
 """
 import math
@@ -274,9 +275,11 @@ def vsd_errors(mesh, est, gt, K, depth_test, frame, diameter, delta=15.0, taus=T
 
 
 # ------------------------------------------------------------------------------------------------ matching and recall (host)
-def match_greedy(errors, threshold):
+def match_greedy(errors, threshold, valid=None):
     """errors (E,G): estimates in descending score x ground truths.  Each estimate in turn takes the still-unmatched ground truth
-    with the smallest error (the lowest index on a tie) if that error is below the threshold; -> the number of matched ground truths."""
+    with the smallest error (the lowest index on a tie) if that error is below the threshold; -> the number of matched ground truths.
+    valid (G,) bool: every ground truth takes part in the matching (one that is not valid still absorbs its estimate), only the
+    valid ones are counted."""
     errors = np.asarray(errors, np.float64)
     free = np.ones(errors.shape[1], bool)
     for e in errors:
@@ -286,6 +289,8 @@ def match_greedy(errors, threshold):
         g = int(np.argmin(cand))
         if free[g] and cand[g] < threshold:
             free[g] = False
+    if valid is not None:
+        return int((~free & np.asarray(valid, bool).reshape(-1)).sum())
     return int((~free).sum())
 
 
@@ -319,18 +324,39 @@ def group_estimates(targets, gts, estimates):
     return out
 
 
+def visibilities(who, ground_truths):
+    """The "visib_fract" of each ground truth of one target -> float64 (G,); a ground truth without the key raises (min_visib
+    needs gtinfo.with_visibility, or scene_gt_info.json's value)."""
+    for g in ground_truths:
+        if g.get("visib_fract") is None:
+            raise ValueError(f"{who}: min_visib is set and a ground truth of object {g['obj_id']} has no 'visib_fract' "
+                             "(gtinfo.with_visibility adds it)")
+    return np.asarray([float(g["visib_fract"]) for g in ground_truths], np.float64).reshape(-1)
+
+
+def check_min_visib(who, min_visib):
+    if min_visib is not None and not 0 <= float(min_visib) <= 1:
+        raise ValueError(f"{who}: min_visib must be None or lie in [0, 1], got {min_visib!r}")
+    return None if min_visib is None else float(min_visib)
+
+
 class PoseScorer:
     """BOP-19 recall of a set of estimates.
       models   {obj_id: {"vertices" (V,3), "faces" (F,3), "diameter", ["symmetries_discrete"], ["symmetries_continuous"]}}
       targets  [{"scene_id", "im_id", "obj_id", "inst_count"}]             (test_targets_bop19.json)
-      gts      {(scene_id, im_id): [{"obj_id", "cam_R_m2c" 9, "cam_t_m2c" 3}]}   (scene_gt.json; every listed instance counts)
+      gts      {(scene_id, im_id): [{"obj_id", "cam_R_m2c" 9, "cam_t_m2c" 3, ["visib_fract"]}]}   (scene_gt.json [+ scene_gt_info.json])
       cameras  {(scene_id, im_id): {"cam_K" 9, "depth" (H,W) z-depth in the units of the models, 0 = no measurement}}
+      min_visib  None: every listed instance counts.  A number (BOP-19: 0.1): a ground truth whose "visib_fract" is below it
+               still takes part in the greedy matching -- it absorbs the estimate that lands on it -- but is counted neither
+               among the matched nor in "targets"; a ground truth without the key raises (gtinfo.GroundTruthInfo computes it,
+               gtinfo.with_visibility adds it)
     Per target it keeps the inst_count highest-scored estimates, computes the three errors of every estimate x ground truth of that
     object in that image on the GPU, and matches greedily per threshold on the host (match_greedy).  Recall = matched ground
     truths / ground truths of all targets."""
 
-    def __init__(self, models, targets, gts, cameras, delta=15.0, taus=TAUS, max_sym_disc_step=0.01, znear=1e-3, device="cuda"):
+    def __init__(self, models, targets, gts, cameras, delta=15.0, taus=TAUS, max_sym_disc_step=0.01, znear=1e-3, device="cuda", min_visib=None):
         self.models, self.targets, self.gts = models, list(targets), gts
+        self.min_visib = check_min_visib("PoseScorer", min_visib)
         self.delta, self.taus, self.znear, self.device = float(delta), tuple(taus), float(znear), device
         self.syms = {o: symmetry_transforms(m, max_sym_disc_step) for o, m in models.items()}
         self._table = CameraTable("PoseScorer", cameras, "required", max_pixels=None)
@@ -350,8 +376,10 @@ class PoseScorer:
         return group_estimates(self.targets, self.gts, estimates)
 
     def errors(self, estimates):
-        """-> [(target, {"mssd" (E,G), "mspd" (E,G), "vsd" (E,G,T), "clipped" (E,G)})] as numpy, E estimates kept x G ground truths."""
+        """-> [(target, {"mssd" (E,G), "mspd" (E,G), "vsd" (E,G,T), "clipped" (E,G)})] as numpy, E estimates kept x G ground truths;
+        with min_visib also "visib" (G,), the ground truths' visib_fract."""
         groups = self.pairs(estimates)
+        visib = None if self.min_visib is None else [visibilities("PoseScorer", g) for _, _, g in groups]     # raises before any GPU work
         depth = self._table.depth_on(self.device)
         out = [None] * len(groups)
         for obj in sorted({int(t["obj_id"]) for t, _, _ in groups}):
@@ -383,28 +411,41 @@ class PoseScorer:
                 else:
                     out[gi] = (groups[gi][0], dict(mssd=np.zeros((E, G)), mspd=np.zeros((E, G)), vsd=np.zeros((E, G, T)),
                                                    clipped=np.zeros((E, G), bool)))
+        if visib is not None:
+            for (_, e), v in zip(out, visib):
+                e["visib"] = v
         return out
 
     def score(self, estimates):
-        return recall_from_errors(self.errors(estimates), {o: float(m["diameter"]) for o, m in self.models.items()}, self.W)
+        return recall_from_errors(self.errors(estimates), {o: float(m["diameter"]) for o, m in self.models.items()}, self.W, self.min_visib)
 
 
-def recall_from_errors(per_target, diameters, W):
+def counted(per_target, min_visib, table="mssd"):
+    """Per target the ground truths that count: None (all of them: the columns of errors[table]) without min_visib, else
+    errors["visib"] >= min_visib; and their number."""
+    if min_visib is None:
+        return [None] * len(per_target), sum(e[table].shape[1] for _, e in per_target)
+    valid = [np.asarray(e["visib"], np.float64) >= float(min_visib) for _, e in per_target]
+    return valid, int(sum(int(v.sum()) for v in valid))
+
+
+def recall_from_errors(per_target, diameters, W, min_visib=None):
     """[(target, errors)] as PoseScorer.errors returns them -> {"recall_mssd" [10], "recall_mspd" [10], "recall_vsd" [T][10],
-    "ar_mssd", "ar_mspd", "ar_vsd", "ar", "targets": ground truths counted, "clipped": estimates x ground truths reported clipped}."""
+    "ar_mssd", "ar_mspd", "ar_vsd", "ar", "targets": ground truths counted, "clipped": estimates x ground truths reported clipped}.
+    min_visib: only the ground truths with errors["visib"] >= min_visib are counted, in the matches and in "targets"."""
     r = W / 640.0
-    total = sum(e["mssd"].shape[1] for _, e in per_target)
+    valid, total = counted(per_target, min_visib)
     T = per_target[0][1]["vsd"].shape[2] if per_target else 0
     tp_mssd, tp_mspd = np.zeros(len(CORRECT_THS), np.int64), np.zeros(len(MSPD_THS), np.int64)
     tp_vsd = np.zeros((T, len(CORRECT_THS)), np.int64)
-    for t, e in per_target:
+    for (t, e), ok in zip(per_target, valid):
         d = diameters[int(t["obj_id"])]
         for i, th in enumerate(CORRECT_THS):
-            tp_mssd[i] += match_greedy(e["mssd"], th * d)
+            tp_mssd[i] += match_greedy(e["mssd"], th * d, ok)
             for k in range(T):
-                tp_vsd[k, i] += match_greedy(e["vsd"][:, :, k], th)
+                tp_vsd[k, i] += match_greedy(e["vsd"][:, :, k], th, ok)
         for i, th in enumerate(MSPD_THS):
-            tp_mspd[i] += match_greedy(e["mspd"], th * r)
+            tp_mspd[i] += match_greedy(e["mspd"], th * r, ok)
     den = float(max(total, 1))
     out = dict(recall_mssd=(tp_mssd / den).tolist(), recall_mspd=(tp_mspd / den).tolist(), recall_vsd=(tp_vsd / den).tolist(), targets=total,
                clipped=int(sum(int(e["clipped"].sum()) for _, e in per_target)))

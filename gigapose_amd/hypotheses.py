@@ -10,6 +10,7 @@ evaluate.PoseScorer takes its cameras through CameraTable.  No library of its ow
   pack_masks(who, estimates, masks, table)         the two mask forms -> run lengths, offsets, det, areas, boxes (host)
   scan_masks(runs, offsets, H, W, device)          -> (cum, offsets) on the device, what the kernels take as `masks`
   mask_lists(who, masks)                           the check of such a pair
+  DeviceMasks(lists, areas, boxes, size)           masks that are on the device already, with what pack_masks works out on the host
   HypothesisFlow                                   the constructor's common part, ._groups(), ._chunks(): the chunk loop
 """
 import types
@@ -188,6 +189,30 @@ def scan_masks(runs, offsets, H, W, device):
     offsets_d = torch.from_numpy(offsets).to(device)
     err = torch.zeros(1, dtype=torch.int32, device=device)
     return ingest.RleDetectionPreprocessor().scan(torch.from_numpy(runs).to(device), offsets_d, H, W, err), offsets_d
+
+
+class DeviceMasks:
+    """Run-length masks that are on the device already (gtinfo.GroundTruthInfo.compute(masks=True) makes them; nothing is packed,
+    uploaded or scanned again): .lists = (cum, offsets) as the kernels take them, and what pack_masks works out on the host --
+    .areas f64 (D,), .boxes int64 (D,4) x0 y0 x1 y1 inclusive (W, H, -1, -1 for an empty mask; a box may be larger than the mask's
+    own: it only has to hold it), .size (H, W).  An estimate names its mask by "instance_id": .index {instance_id: d}, by default
+    d itself.  HypothesisVerifier.score takes one as `masks`."""
+
+    def __init__(self, lists, areas, boxes, size, index=None):
+        self.lists = mask_lists("DeviceMasks", lists)
+        D = self.lists[1].shape[0] - 1
+        self.areas, self.boxes = np.asarray(areas, np.float64).reshape(D), np.asarray(boxes, np.int64).reshape(D, 4)
+        self.size = (int(size[0]), int(size[1]))
+        self.index = {d: d for d in range(D)} if index is None else dict(index)
+
+    def assign(self, who, estimates, table):
+        """-> det int32 (E,) -1 = none, area f64 (E,) NaN = none, the masks' boxes: what pack_masks returns after the lists."""
+        if any("instance_id" not in e for e in estimates):
+            raise ValueError(f"{who}: masks on the device need estimates with an instance_id")
+        table.set_size(who, *self.size)
+        det = np.asarray([self.index.get(e["instance_id"], -1) for e in estimates], np.int32).reshape(-1)
+        area = np.where(det >= 0, self.areas[np.maximum(det, 0)] if len(self.areas) else np.nan, np.nan)
+        return det, area, self.boxes
 
 
 def mask_lists(who, masks, or_none=""):

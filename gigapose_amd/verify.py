@@ -24,7 +24,7 @@ import torch
 
 from . import _lib, refine
 from .evaluate import read_estimates
-from .hypotheses import MAX_PAIRS_PER_CALL, MAX_PIXELS, HypothesisFlow, mask_lists, need_gpu, pack_masks, scan_masks  # (gigapose_verify.h: Limits)
+from .hypotheses import MAX_PAIRS_PER_CALL, MAX_PIXELS, DeviceMasks, HypothesisFlow, mask_lists, need_gpu, pack_masks, scan_masks  # (gigapose_verify.h: Limits)
 
 COUNTS = 16
 UNMEASURED, AGREE, BEHIND, FRONT = 0, 1, 2, 3        # a covered pixel's class: counts[2*class + in_mask]
@@ -151,7 +151,8 @@ class HypothesisVerifier(HypothesisFlow):
     .score(estimates, masks) takes the dictionaries read_hypotheses returns and gives back copies with "verify", "depth_fit",
     "iou", "residual", "verify_status" (STATUS_BITS, | refine.CLIPPED for a view that drops a triangle) and "counts" (the row of
     16) added.  masks: {instance_id: segmentation} or one segmentation per estimate (None = none for it), a COCO dict {"size":
-    [H, W], "counts": run lengths, or a compressed string (decoded on the host by rle_strings)}.  Per chunk: render.project ->
+    [H, W], "counts": run lengths, or a compressed string (decoded on the host by rle_strings)} -- or a hypotheses.DeviceMasks,
+    lists that are on the device already (gtinfo.GroundTruthInfo.compute makes them), named by "instance_id".  Per chunk: render.project ->
     render.raster -> counts; the host does not synchronise inside the loop and no depth map, key or mask crosses PCIe again."""
 
     def __init__(self, models, cameras, tol=0.05, min_points=32, occlusion_weight=0.0, box="projected", margin=8, znear=1e-3,
@@ -177,11 +178,15 @@ class HypothesisVerifier(HypothesisFlow):
         if masks is None and not has_depth:
             raise ValueError(f"{who}: no camera has a depth image: masks are required")
         groups = self._groups(who, estimates)
-        lists = None if masks is None else pack_masks(who, estimates, masks, self.table)
+        on_device = isinstance(masks, DeviceMasks)
+        lists = None if masks is None or on_device else pack_masks(who, estimates, masks, self.table)
         need_gpu(who, self.device)
         dev, depth = self.device, self.table.depth_on(self.device)
         area, cum_d, det_h, mask_boxes = np.full(E, np.nan), None, None, None
-        if lists is not None and len(lists[0]):
+        if on_device and len(masks.areas):
+            det_h, area, mask_boxes = masks.assign(who, estimates, self.table)
+            cum_d = masks.lists
+        elif lists is not None and len(lists[0]):
             runs, offsets, det_h, area, mask_boxes = lists
             cum_d = scan_masks(runs, offsets, self.H, self.W, dev)
         results = []                                   # (indices, counts, status, clipped, tol) on the device: read once at the end
