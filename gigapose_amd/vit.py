@@ -365,6 +365,29 @@ class Dinov2ViT(nn.Module):
         return out
 
     @torch.no_grad()
+    def cls_descriptors(self, images, chunk=64):
+        """images (B,3,224,224) f32 -> (q int32 (B, C), status int32 (B)): the class token AFTER the final LayerNorm (`self.norm`,
+        which nothing else here applies), L2-normalised and quantised as rint(d * 2^20) -- the crop descriptor of CNOS, as
+        libgigapose_label.so defines it (include/gigapose_label.h: gpa_descriptors; gigapose_amd/proposals.py).  The forward runs in
+        chunks of at most `chunk` <= 64 crops with normalize=False; the kernel reads the tokens from the workspace's channel-major
+        view, no copy in between.  status: 1 = a token value is not finite, 2 = zero norm; a flagged row is all zeros."""
+        from . import proposals
+
+        if not 1 <= int(chunk) <= 64:
+            raise ValueError(f"cls_descriptors: chunk = {chunk} (1 to 64)")
+        B, C = images.shape[0], self.dim
+        gamma = self.norm.weight.detach().to(device=images.device, dtype=torch.float32).contiguous()
+        beta = self.norm.bias.detach().to(device=images.device, dtype=torch.float32).contiguous()
+        q = torch.empty(B, C, dtype=torch.int32, device=images.device)
+        status = torch.empty(B, dtype=torch.int32, device=images.device)
+        for a in range(0, B, int(chunk)):
+            n = min(B, a + int(chunk)) - a
+            self.patch_features(images[a:a + n], normalize=False)
+            mpad = (n * T + 255) // 256 * 256
+            q[a:a + n], status[a:a + n] = proposals.descriptors(self._ws, T, mpad, gamma, beta, self.norm.eps, n, C)
+        return q, status
+
+    @torch.no_grad()
     def forward_features(self, images):
         """hub-API compatibility: {"x_prenorm": (B, 257, C)} (token-major view of the workspace)."""
         B = images.shape[0]
