@@ -15,8 +15,8 @@ the labels do not depend on launch geometry; gigapose_testing/label_ref.py resta
   nms(box, label, num, den, per_label) boxes in suppression order -> keep                                gpa_nms_matrix + gpa_nms_keep
   DescriptorBank                       the descriptors of the onboarded objects' templates, (O, T, C)
   ProposalLabeller                     frames + proposals -> per image the list of CNOS dicts FrameIngest takes
-Out of scope: the segmenter, CNOS's appearance and visibility scores, mask-IoU NMS, objects with different template counts.  There
-is no CPU fallback: the kernels need the GPU, a missing library is an error.
+Out of scope: the segmenter, CNOS's appearance and visibility scores, objects with different template counts.  (A mask-IoU NMS
+is detections.mask_nms; ProposalLabeller(nms_on="mask") routes through it.)  There is no CPU fallback: the kernels need the GPU, a missing library is an error.
 """
 import ctypes
 
@@ -124,7 +124,13 @@ def mask_boxes(counts, offsets, H, W, device="cuda"):
     """Uncompressed run-length masks (ingest.pack_rle's counts int32[total], offsets int32[D+1]; numpy or tensors) -> (box, area,
     status) on the device, through gpi_rle_scan + gpa_run_boxes.  A bad list (a negative run, a total other than H*W) raises a
     ValueError that names the mask; an empty mask is no error: status EMPTY_MASK, box 0, 0, 0, 0."""
-    who = "mask_boxes"
+    return mask_boxes_and_lists(counts, offsets, H, W, device)[0]
+
+
+@torch.no_grad()
+def scan_lists(who, counts, offsets, H, W, device="cuda"):
+    """counts, offsets as mask_boxes takes them -> (cum, offsets) on the device (gpi_rle_scan, chunked at 65535 masks) and `check`,
+    which raises the ValueError of a bad list when called (a host synchronisation)."""
     (counts, ct), (offsets, ot) = _lib.checked(counts, torch.int32, (None,), who, "counts"), _lib.checked(offsets, torch.int32, (None,), who, "offsets")
     dev = counts.device if counts.is_cuda else device
     counts, offsets = _lib.upload(who, dev, (counts, ct), (offsets, ot))
@@ -136,11 +142,22 @@ def mask_boxes(counts, offsets, H, W, device="cuda"):
     for c, a, b in _lib.chunked(D, MAX_MASKS_PER_CALL):
         _ingest_call("gpi_rle_scan", _lib.ptr(counts), _lib.ptr(offsets[a:b + 1]), _lib.i(counts.numel()), _lib.i(b - a), _lib.i(H), _lib.i(W),
                     _lib.ptr(cum), _lib.ptr(err[c:c + 1]), _lib.stream_ptr())
+
+    def check():
+        bad = _lib.first_bad(err.tolist(), MAX_MASKS_PER_CALL)
+        if bad is not None:
+            raise ValueError(f"{who}: mask {bad} has a bad run-length list (no run, a negative run or a total other than H*W = {H * W})")
+
+    return cum, offsets, check
+
+
+@torch.no_grad()
+def mask_boxes_and_lists(counts, offsets, H, W, device="cuda"):
+    """mask_boxes, and the scanned lists it was taken from: -> ((box, area, status), (cum, offsets))."""
+    cum, offsets, check = scan_lists("mask_boxes", counts, offsets, H, W, device)
     out = run_boxes(cum, offsets, H, W)
-    bad = _lib.first_bad(err.tolist(), MAX_MASKS_PER_CALL)
-    if bad is not None:
-        raise ValueError(f"{who}: mask {bad} has a bad run-length list (no run, a negative run or a total other than H*W = {H * W})")
-    return out
+    check()
+    return out, (cum, offsets)
 
 
 def _threshold(nms_iou):
@@ -166,9 +183,22 @@ def nms(box, label, num, den, per_label=False):
     _lib.on_gpu(who, box=box)
     words = (P + 63) // 64
     sup = torch.empty(P, words, dtype=torch.int64, device=box.device)
-    keep = torch.empty(P, dtype=torch.uint8, device=box.device)
     _call("gpa_nms_matrix", _lib.ptr(box), _lib.ptr(label if per_label else None), _lib.i(P), _lib.i(num), _lib.i(den), _lib.i(1 if per_label else 0),
           _lib.ptr(sup), _lib.stream_ptr())
+    return nms_keep(sup)
+
+
+@torch.no_grad()
+def nms_keep(sup):
+    """sup int64 (P, (P + 63) // 64) on the device, the suppression bits of gpa_nms_matrix (or of gpc_sup_bits, from mask IoUs) ->
+    keep u8 (P): the greedy pass, gpa_nms_keep."""
+    who = "nms_keep"
+    sup = _lib.arg(sup, torch.int64, (None, None), who, "sup")
+    P = sup.shape[0]
+    if P > MAX_NMS or sup.shape[1] != (P + 63) // 64:
+        raise ValueError(f"{who}: expected sup (P, (P + 63) // 64) with P <= {MAX_NMS}, got {tuple(sup.shape)}")
+    _lib.on_gpu(who, sup=sup)
+    keep = torch.empty(P, dtype=torch.uint8, device=sup.device)
     _call("gpa_nms_keep", _lib.ptr(sup), _lib.i(P), _lib.ptr(keep), _lib.stream_ptr())
     return keep
 
@@ -261,11 +291,13 @@ class ProposalLabeller:
     bank: a DescriptorBank made with the same vit.  top_k: the templates an object's score is the mean of (CNOS: 5).  min_score:
     proposals below it are dropped.  nms_iou = (num, den): a kept box suppresses a later one when IoU > num / den, on integers.
     per_label: only boxes of one label suppress each other.  max_dets: at most this many detections per image, best first.
+    nms_on: "box" (the default) compares the boxes; "mask" compares the masks themselves (detections.mask_nms: the same threshold,
+    the same greedy pass, the IoU of the run-length masks; at most 2048 proposals above min_score per image).
 
     label(frames_u8, proposals) -> per image the list of CNOS dicts {bbox xywh, category_id, score, segmentation, best_template}
     (+ proposal: the index in the image's input list), best first; ingest.FrameIngest.__call__ takes them unchanged.  `report` counts what the last call dropped and why."""
 
-    def __init__(self, vit, bank, top_k=5, min_score=0.5, nms_iou=(1, 4), per_label=False, max_dets=None, device="cuda"):
+    def __init__(self, vit, bank, top_k=5, min_score=0.5, nms_iou=(1, 4), per_label=False, max_dets=None, device="cuda", nms_on="box"):
         self.vit, self.bank = vit, bank
         self.top_k, self.min_score = int(top_k), float(min_score)
         if not 1 <= self.top_k <= MAX_K:
@@ -274,6 +306,9 @@ class ProposalLabeller:
             raise ValueError("ProposalLabeller: min_score is NaN")
         self.nms_iou = _threshold(nms_iou)
         self.per_label = bool(per_label)
+        if nms_on not in ("box", "mask"):
+            raise ValueError(f"ProposalLabeller: nms_on must be 'box' or 'mask', got {nms_on!r}")
+        self.nms_on = nms_on
         if max_dets is not None and int(max_dets) < 0:
             raise ValueError(f"ProposalLabeller: max_dets = {max_dets}")
         self.max_dets = None if max_dets is None else int(max_dets)
@@ -314,7 +349,7 @@ class ProposalLabeller:
         P, dev = len(segs), self.device
         frames = frames_u8.to(dev, non_blocking=True)
         counts_d, offsets_d = torch.from_numpy(counts).to(dev), torch.from_numpy(offsets).to(dev)
-        box_d, _, mstatus_d = mask_boxes(counts_d, offsets_d, H, W)
+        (box_d, _, mstatus_d), lists = mask_boxes_and_lists(counts_d, offsets_d, H, W)
         box, mstatus = box_d.cpu().numpy().astype(np.int64), mstatus_d.cpu().numpy()
         box[given] = given_xyxy[given]                                  # a proposal's own box stands
         crop_box = box.copy()
@@ -325,7 +360,7 @@ class ProposalLabeller:
                                                                best_template=torch.zeros(0, dtype=torch.int32), kk=min(self.top_k, self.bank.q.shape[1]))
         host = {k: sc[k].cpu().numpy() for k in ("label", "score", "best_template")}
         return dict(host, kk=sc["kk"], box=box, mstatus=mstatus, dstatus=dstatus.cpu().numpy(), image=im_id, segs=segs, crops=crops, q=q,
-                    score_dev=sc["score"], n_img=n_img, local=local)
+                    score_dev=sc["score"], n_img=n_img, local=local, lists=lists, HW=H * W)
 
     @torch.no_grad()
     def label(self, frames_u8, proposals):
@@ -339,6 +374,10 @@ class ProposalLabeller:
         alive = ~(empty | flagged | low)
         box32 = torch.from_numpy(s["box"].clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32)).to(dev) if P else None
         label32 = torch.from_numpy(s["label"]).to(dev) if P else None
+        if self.nms_on == "mask" and P:
+            from . import detections                                    # detections imports this module
+
+            fg = detections.foreground(s["lists"], s["HW"])
         out = []
         for im in range(s["n_img"]):
             idx = np.flatnonzero(alive & (s["image"] == im))
@@ -349,7 +388,10 @@ class ProposalLabeller:
                 idx_d = torch.from_numpy(idx).to(dev)
                 order = torch.sort(s["score_dev"][idx_d], descending=True, stable=True).indices      # ties: the lower proposal index first
                 idx_d = idx_d[order]
-                keep = nms(box32[idx_d].contiguous(), label32[idx_d].contiguous(), *self.nms_iou, per_label=self.per_label)
+                if self.nms_on == "mask":
+                    keep = detections.mask_nms(fg, idx_d, *self.nms_iou, label=label32 if self.per_label else None)
+                else:
+                    keep = nms(box32[idx_d].contiguous(), label32[idx_d].contiguous(), *self.nms_iou, per_label=self.per_label)
                 kept = idx_d[keep.bool()].cpu().tolist()
                 report["suppressed"] += len(idx) - len(kept)
                 if self.max_dets is not None and len(kept) > self.max_dets:
