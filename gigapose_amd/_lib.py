@@ -7,6 +7,7 @@ raises.  torch must be imported first so the library binds to the HIP runtime to
 loaded (same SONAME libamdhip64.so.7) and shares its streams and allocations.
 """
 import ctypes
+import operator
 import os
 import re
 
@@ -43,12 +44,13 @@ def default_numerics():
 
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t}
 _RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+_RANGES = {ctypes.c_int: ("int", -2 ** 31, 2 ** 31 - 1), ctypes.c_longlong: ("long long", -2 ** 63, 2 ** 63 - 1), ctypes.c_size_t: ("size_t", 0, 2 ** 64 - 1)}
+_REALS = {ctypes.c_float: "float", ctypes.c_double: "double"}
+_CTYPES = (ctypes.c_int.__mro__[-2], type(ctypes.byref(ctypes.c_int())))   # every ctypes instance, and what byref returns
 
 
-def parse_prototypes(text):
-    """The `ret name(params);` prototypes of a C header -> {name: (restype, [argtypes])}.  Reads what include/*.h use and is no C front end: comments,
-    preprocessor lines and the extern "C" braces are dropped; a parameter is a pointer (-> c_void_p: None, an integer, a ctypes array or byref) or a named
-    int, float, double, long long or size_t; a function returns int, size_t, void or const char*.  Anything else raises: a prototype is never skipped."""
+def _parse(text):
+    """parse_prototypes with the parameter names kept: {name: (restype, [argtypes], [parameter names])}."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
     protos = {}
@@ -60,37 +62,116 @@ def parse_prototypes(text):
         if not m or ret not in _RETURNS or m.group(2) in protos or any(k != "*" and k not in _SCALARS for k in kinds):
             raise GigaPoseHipError(f"cannot read the prototype `{stmt}`: expected `int|size_t|void|const char* name(params)`, each name once, "
                                    f"every parameter a pointer or a named {' | '.join(_SCALARS)}")
-        protos[m.group(2)] = (_RETURNS[ret], [ctypes.c_void_p if k == "*" else _SCALARS[k] for k in kinds])
+        protos[m.group(2)] = (_RETURNS[ret], [ctypes.c_void_p if k == "*" else _SCALARS[k] for k in kinds],
+                              [re.search(r"\w*$", p.strip()).group() for p in params])
     return protos
 
 
-def declared(*headers):
-    """The prototypes of include/<header>, ... together; a missing header is an error like a missing library."""
+def parse_prototypes(text):
+    """The `ret name(params);` prototypes of a C header -> {name: (restype, [argtypes])}.  Reads what include/*.h use and is no C front end: comments,
+    preprocessor lines and the extern "C" braces are dropped; a parameter is a pointer (-> c_void_p: None, an integer, a ctypes array or byref) or a named
+    int, float, double, long long or size_t; a function returns int, size_t, void or const char*.  Anything else raises: a prototype is never skipped."""
+    return {name: (restype, argtypes) for name, (restype, argtypes, _) in _parse(text).items()}
+
+
+def _declared(*headers):
     protos = {}
     for path in (os.path.join(INCLUDE_DIR, h) for h in headers):
         if not os.path.exists(path):
             raise GigaPoseHipError(f"{path} not found: the ctypes signatures are read from the C headers beside the package (INTEGRATION.md section 2)")
         with open(path) as fh:
-            protos.update(parse_prototypes(fh.read()))
+            protos.update(_parse(fh.read()))
     return protos
 
 
+def declared(*headers):
+    """The prototypes of include/<header>, ... together; a missing header is an error like a missing library."""
+    return {name: (restype, argtypes) for name, (restype, argtypes, _) in _declared(*headers).items()}
+
+
+def _address(t, where):
+    """Device address of a contiguous GPU tensor; `where` names the call and the parameter."""
+    if not t.is_cuda:
+        raise GigaPoseHipError(f"{where}: gigapose_amd kernels need tensors on the GPU (no CPU fallback)")
+    if not t.is_contiguous():
+        raise GigaPoseHipError(f"{where}: non-contiguous tensor passed to a HIP kernel")
+    return t.data_ptr()
+
+
+def _converter(name, pos, pname, ctype):
+    """What turns one argument of `name` into what ctypes takes for the declared kind.  A ctypes instance (c_void_p, an array, byref, c_int, ...) always
+    passes unchanged: ctypes holds it against the argtypes.  A tensor is read only where a pointer is declared, so that no scalar synchronises the stream."""
+    if ctype is ctypes.c_void_p:
+        where = f"{name}: argument {pos} (pointer {pname})"
+
+        def pointer(v):   # None is ctypes' NULL
+            return _address(v, where) if isinstance(v, torch.Tensor) else v
+        return pointer
+    if ctype in _RANGES:
+        kind, lo, hi = _RANGES[ctype]
+        where = f"{name}: argument {pos} ({kind} {pname})"
+
+        def integer(v):
+            if type(v) is not int:
+                if isinstance(v, _CTYPES):
+                    return v
+                if isinstance(v, torch.Tensor):
+                    raise TypeError(f"{where} takes an integer, not a tensor: reading one on the device would synchronise the stream")
+                try:
+                    v = operator.index(v)
+                except TypeError:
+                    raise TypeError(f"{where} takes an integer, got {type(v).__name__}") from None
+            if not lo <= v <= hi:
+                raise OverflowError(f"{where}: {v} is outside [{lo}, {hi}]")
+            return v
+        return integer
+    where = f"{name}: argument {pos} ({_REALS[ctype]} {pname})"
+
+    def real(v):
+        if type(v) is float or isinstance(v, _CTYPES):
+            return v
+        if isinstance(v, (torch.Tensor, str, bytes)):
+            raise TypeError(f"{where} takes a real number, got {type(v).__name__}")
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise TypeError(f"{where} takes a real number, got {type(v).__name__}") from None
+    return real
+
+
+def converters(name, argtypes, names):
+    """One converter per parameter of `name`: built once per function (_load), so that a call only applies them."""
+    return tuple(_converter(name, pos, pname, ctype) for pos, (pname, ctype) in enumerate(zip(names, argtypes), 1))
+
+
+def _convert(name, convs, args):
+    if len(args) != len(convs):   # ctypes itself rejects too few arguments but lets extra ones through
+        raise TypeError(f"{name} takes {len(convs)} arguments (include/), got {len(args)}")
+    return [c(a) for c, a in zip(convs, args)]
+
+
+def marshal(name, argtypes, names, args):
+    """The arguments of one call as ctypes takes them, converted by the declared kinds (see _converter): tensors and None for pointers, Python and numpy
+    integers in the declared range for int / long long / size_t, real numbers for float / double.  Needs no library: _load keeps the converters per function."""
+    return tuple(_convert(name, converters(name, argtypes, names), args))
+
+
 def _load(path, *headers, scope=" for the hot path"):
-    """CDLL(path) with restype and argtypes of every function the headers declare: a wrong argument kind is a ctypes.ArgumentError before the library is entered."""
+    """CDLL(path) with restype, argtypes and argument converters of every function the headers declare: a wrong argument kind is an error before the library is entered."""
     if not os.path.exists(path):
         raise GigaPoseHipError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                f"(there is deliberately no CPU / PyTorch fallback{scope})")
     h = ctypes.CDLL(path)
-    for name, (restype, argtypes) in declared(*headers).items():
+    h.gp_converters = {}
+    for name, (restype, argtypes, names) in _declared(*headers).items():
         getattr(h, name).restype, getattr(h, name).argtypes = restype, argtypes
+        h.gp_converters[name] = converters(name, argtypes, names)
     return h
 
 
 def _invoke(h, name, args):
     fn = getattr(h, name)
-    if len(args) != len(fn.argtypes):   # ctypes itself rejects too few arguments but lets extra ones through
-        raise TypeError(f"{name} takes {len(fn.argtypes)} arguments (include/), got {len(args)}")
-    return fn(*args)
+    return fn(*_convert(name, h.gp_converters[name], args))
 
 
 class SideLibrary:
@@ -112,13 +193,23 @@ class SideLibrary:
         if rc != 0:
             raise GigaPoseHipError(f"{name} failed (rc={rc}): {getattr(self.lib(), self.prefix + '_last_error')().decode()}")
 
+    def value(self, name, *args):
+        """A function that returns no status (a size, a count, or nothing): its result, the arguments converted as call() converts them."""
+        return _invoke(self.lib(), name, args)
+
+
+def _expect(t, dtype, shape, who, what):
+    """dtype (None: any), rank and fixed sizes of one tensor, or ValueError."""
+    if (dtype is not None and t.dtype != dtype) or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        want, got = tuple('*' if s is None else s for s in shape), tuple(t.shape)
+        raise ValueError(f"{who}: expected {what} {want}, got {got}" if dtype is None else f"{who}: expected {what} {dtype} {want}, got {t.dtype} {got}")
+
 
 def arg(t, dtype, shape, who, what):
     """Argument checks the front-end modules share.  Type, dtype, shape and layout of one argument (ValueError); on_gpu checks the devices once every argument has passed."""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{who}: {what} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+    _expect(t, dtype, shape, who, what)
     if not t.is_contiguous():
         raise ValueError(f"{who}: {what} is not contiguous")
     return t
@@ -133,8 +224,7 @@ def on_gpu(who, **tensors):
 def checked(a, dtype, shape, who, what):
     """A numpy array or a tensor anywhere -> a tensor whose shape and kind of dtype are checked; upload moves it."""
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {tuple('*' if s is None else s for s in shape)}, got {tuple(t.shape)}")
+    _expect(t, None, shape, who, what)
     if t.dtype.is_floating_point != dtype.is_floating_point:
         raise ValueError(f"{who}: {what} has dtype {t.dtype}, expected {dtype}")
     return t, dtype
@@ -149,8 +239,7 @@ def upload(who, device, *checked):
 def on_device(t, dtype, shape, who, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda):
         raise GigaPoseHipError(f"{who} needs {what} on the GPU (no CPU fallback)")
-    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{who}: expected {what} {dtype} {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+    _expect(t, dtype, shape, who, what)
     return t.contiguous()
 
 
@@ -237,7 +326,7 @@ def status_word(device=None):
         _status[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
     if idx not in _registered:
         with torch.cuda.device(idx):
-            call("gp_set_status_buffer", ctypes.c_void_p(_status[idx].data_ptr()))
+            call("gp_set_status_buffer", _status[idx])
         _registered.add(idx)
     return _status[idx]
 
@@ -270,20 +359,25 @@ def stream_ptr():
 
 
 def ptr(t):
-    """Device pointer of a contiguous CUDA tensor (None -> NULL)."""
-    if t is None:
-        return ctypes.c_void_p(0)
-    if not t.is_cuda:
-        raise GigaPoseHipError("gigapose_amd kernels need tensors on the GPU (no CPU fallback)")
-    if not t.is_contiguous():
-        raise GigaPoseHipError("non-contiguous tensor passed to a HIP kernel")
-    return ctypes.c_void_p(t.data_ptr())
+    """Device pointer of a contiguous CUDA tensor (None -> NULL).  call() does this by itself for a tensor; tests and old call sites spell it out."""
+    return ctypes.c_void_p(0 if t is None else _address(t, "ptr"))
+
+
+def ptr_table(tensors):
+    """A host array of the tensors' device pointers (a `const T* const*` parameter; one NULL entry when there is no tensor), each held to ptr()'s device and
+    layout check.  The caller keeps the tensors alive."""
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[_address(t, f"ptr_table: entry {n}") for n, t in enumerate(tensors)])
 
 
 def call(name, *args):
     rc = _invoke(lib(), name, args)
     if rc != 0:
         raise GigaPoseHipError(f"{name} failed (rc={rc}): {lib().gp_last_error().decode()}")
+
+
+def value(name, *args):
+    """A function that returns no status (a size, a count, or nothing): its result, the arguments converted as call() converts them."""
+    return _invoke(lib(), name, args)
 
 
 def i(v):

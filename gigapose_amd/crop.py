@@ -41,8 +41,7 @@ class CropResizePad:
         out = torch.empty(D, C, T, T, device=dev)
         M = torch.empty(D, 3, 3, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.call("gp_crop_resize_pad", _lib.ptr(images), _lib.ptr(boxes), _lib.i(D), _lib.i(C), _lib.i(H), _lib.i(W),
-                  _lib.i(T), _lib.ptr(out), _lib.ptr(M), _lib.ptr(err), _lib.stream_ptr())
+        _lib.call("gp_crop_resize_pad", images, boxes, D, C, H, W, T, out, M, err, _lib.stream_ptr())
         _check(err, "CropResizePad")
         return {"M": M, "images": out}
 
@@ -73,8 +72,7 @@ class DetectionPreprocessor:
         tar_mask = torch.empty(D, T, T, device=dev)
         M = torch.empty(D, 3, 3, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.call("gp_preprocess_detections", _lib.ptr(rgb_u8), _lib.ptr(masks), _lib.ptr(boxes), _lib.ptr(im_id),
-                  _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), self._mean, self._std, _lib.ptr(tar_img),
-                  _lib.ptr(tar_mask), _lib.ptr(M), _lib.ptr(err), _lib.stream_ptr())
+        _lib.call("gp_preprocess_detections", rgb_u8, masks, boxes, im_id, n_img, D, H, W, T, self._mean, self._std, tar_img, tar_mask, M, err,
+                  _lib.stream_ptr())
         _check(err, "DetectionPreprocessor")
         return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}

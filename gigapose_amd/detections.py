@@ -67,8 +67,7 @@ def foreground(masks, HW):
     fg = torch.zeros_like(cum)
     area, status = torch.empty(D, dtype=torch.int64, device=dev), torch.empty(D, dtype=torch.int32, device=dev)
     for _, a, b in _lib.chunked(D, MAX_ITEMS_PER_CALL):
-        _call("gpc_fg_scan", _lib.ptr(cum), _lib.ptr(offsets[a:b + 1]), _lib.i(cum.numel()), _lib.i(b - a), _lib.i(HW), _lib.ptr(fg),
-              _lib.ptr(area[a:b]), _lib.ptr(status[a:b]), _lib.stream_ptr())
+        _call("gpc_fg_scan", cum, offsets[a:b + 1], cum.numel(), b - a, HW, fg, area[a:b], status[a:b], _lib.stream_ptr())
     return Foreground(cum, offsets, fg, area, status, HW)
 
 
@@ -93,9 +92,8 @@ def mask_intersections(masks_a, masks_b, pair_a, pair_b):
     inter, status = torch.empty(P, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
     A, B = masks_a, masks_b
     for _, a, b in _lib.chunked(P, MAX_ITEMS_PER_CALL):
-        _call("gpc_mask_inter", _lib.ptr(A.cum), _lib.ptr(A.offsets), _lib.ptr(A.fg), _lib.i(A.cum.numel()), _lib.i(len(A)), _lib.ptr(B.cum),
-              _lib.ptr(B.offsets), _lib.ptr(B.fg), _lib.i(B.cum.numel()), _lib.i(len(B)), _lib.i(A.HW), _lib.ptr(pair_a[a:b]), _lib.ptr(pair_b[a:b]),
-              _lib.i(b - a), _lib.ptr(inter[a:b]), _lib.ptr(status[a:b]), _lib.stream_ptr())
+        _call("gpc_mask_inter", A.cum, A.offsets, A.fg, A.cum.numel(), len(A), B.cum, B.offsets, B.fg, B.cum.numel(), len(B), A.HW, pair_a[a:b], pair_b[a:b],
+              b - a, inter[a:b], status[a:b], _lib.stream_ptr())
     return inter, status
 
 
@@ -111,8 +109,7 @@ def box_intersections(box_a, box_b, pair_a, pair_b):
     inter, area_a, area_b = (torch.empty(P, dtype=torch.int64, device=dev) for _ in range(3))
     status = torch.empty(P, dtype=torch.int32, device=dev)
     for _, a, b in _lib.chunked(P, MAX_ITEMS_PER_CALL):
-        _call("gpc_box_inter", _lib.ptr(box_a), _lib.i(box_a.shape[0]), _lib.ptr(box_b), _lib.i(box_b.shape[0]), _lib.ptr(pair_a[a:b]),
-              _lib.ptr(pair_b[a:b]), _lib.i(b - a), _lib.ptr(inter[a:b]), _lib.ptr(area_a[a:b]), _lib.ptr(area_b[a:b]), _lib.ptr(status[a:b]),
+        _call("gpc_box_inter", box_a, box_a.shape[0], box_b, box_b.shape[0], pair_a[a:b], pair_b[a:b], b - a, inter[a:b], area_a[a:b], area_b[a:b], status[a:b],
               _lib.stream_ptr())
     return inter, area_a, area_b, status
 
@@ -151,9 +148,8 @@ def match(det_off, gt_off, pair_off, inter, area_det, area_gt, gt_ignore, thresh
     dt_ignore = torch.zeros((T, TD), dtype=torch.uint8, device=dev)
     status = torch.empty(Q, dtype=torch.int32, device=dev)
     for _, a, b in _lib.chunked(Q, MAX_ITEMS_PER_CALL):
-        _call("gpc_match", _lib.ptr(det_off[a:b + 1]), _lib.ptr(gt_off[a:b + 1]), _lib.ptr(pair_off[a:b]), _lib.i(b - a), _lib.ptr(inter),
-              _lib.i(inter.shape[0]), _lib.ptr(area_det), _lib.i(TD), _lib.ptr(area_gt), _lib.ptr(gt_ignore), _lib.i(area_gt.shape[0]),
-              _lib.ptr(thr), _lib.i(T), _lib.i(den), _lib.ptr(dt_match), _lib.ptr(dt_ignore), _lib.ptr(status[a:b]), _lib.stream_ptr())
+        _call("gpc_match", det_off[a:b + 1], gt_off[a:b + 1], pair_off[a:b], b - a, inter, inter.shape[0], area_det, TD, area_gt, gt_ignore, area_gt.shape[0],
+              thr, T, den, dt_match, dt_ignore, status[a:b], _lib.stream_ptr())
     return dt_match, dt_ignore, status
 
 
@@ -170,7 +166,7 @@ def sup_bits(inter, area, num, den):
         raise ValueError(f"{who}: {P} masks in one call (the limit is {MAX_NMS})")
     _lib.on_gpu(who, inter=inter, area=area)
     sup = torch.empty(P, (P + 63) // 64, dtype=torch.int64, device=area.device)
-    _call("gpc_sup_bits", _lib.ptr(inter), _lib.ptr(area), _lib.i(P), _lib.i(num), _lib.i(den), _lib.ptr(sup), _lib.stream_ptr())
+    _call("gpc_sup_bits", inter, area, P, num, den, sup, _lib.stream_ptr())
     return sup
 
 

@@ -16,8 +16,6 @@ Out of scope: a KD-tree for very large models (the all-pairs kernel is exact and
 transforms (MSSD of evaluate.py is the symmetry-aware error), the AUC variants of other toolkits (the definition is AddScorer's
 docstring).  There is no CPU fallback: a missing library is an error.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -60,8 +58,7 @@ def add_sums(vertices, est, gt, symmetric, k=20):
     _lib.on_gpu(who, vertices=vertices, est=est, gt=gt)
     sums = torch.empty(N, dtype=torch.int64, device=est.device)
     status = torch.empty(N, dtype=torch.int32, device=est.device)
-    _call("gpd_adds" if symmetric else "gpd_add", _lib.ptr(vertices), _lib.i(V), _lib.ptr(est), _lib.ptr(gt), _lib.i(N), _lib.i(k),
-          _lib.ptr(sums), _lib.ptr(status), _lib.stream_ptr())
+    _call("gpd_adds" if symmetric else "gpd_add", vertices, V, est, gt, N, k, sums, status, _lib.stream_ptr())
     return sums, status
 
 
@@ -104,7 +101,7 @@ def diameter2_key(vertices):
     _check_v(who, vertices.shape[0])
     _lib.on_gpu(who, vertices=vertices)
     key = torch.empty(1, dtype=torch.int64, device=vertices.device)
-    _call("gpd_diameter2", _lib.ptr(vertices), _lib.i(vertices.shape[0]), _lib.ptr(key), _lib.stream_ptr())
+    _call("gpd_diameter2", vertices, vertices.shape[0], key, _lib.stream_ptr())
     return key
 
 
@@ -128,7 +125,7 @@ def roots(x):
     x = _lib.arg(x, torch.float64, (None,), "roots", "x")
     _lib.on_gpu("roots", x=x)
     out = torch.empty_like(x)
-    _call("gpd_root", _lib.ptr(x), ctypes.c_longlong(x.shape[0]), _lib.ptr(out), _lib.stream_ptr())
+    _call("gpd_root", x, x.shape[0], out, _lib.stream_ptr())
     return out
 
 

@@ -81,7 +81,7 @@ def symmetry_transforms(model_info, max_sym_disc_step=0.01):
 
 # ------------------------------------------------------------------------------------------------ the two entry points
 def pose_workspace_bytes(N, S):
-    return int(lib().gpe_pose_workspace_bytes(_lib.i(N), _lib.i(S)))
+    return _eval.value("gpe_pose_workspace_bytes", N, S)
 
 
 @torch.no_grad()
@@ -111,8 +111,7 @@ def mssd_mspd(vertices, syms, est, gt, K, zmin=0.0, workspace=None):
     _lib.on_gpu(who, vertices=vertices, syms=syms, est=est, gt=gt, K=K, workspace=workspace)
     mssd2 = torch.empty(N, dtype=torch.float64, device=est.device)
     mspd2 = torch.empty(N, dtype=torch.float64, device=est.device)
-    _call("gpe_mssd_mspd", _lib.ptr(vertices), _lib.i(V), _lib.ptr(syms), _lib.i(S), _lib.ptr(est), _lib.ptr(gt), _lib.ptr(K), _lib.i(N),
-          _lib.d(zmin), _lib.ptr(mssd2), _lib.ptr(mspd2), _lib.ptr(workspace), _lib.stream_ptr())
+    _call("gpe_mssd_mspd", vertices, V, syms, S, est, gt, K, N, zmin, mssd2, mspd2, workspace, _lib.stream_ptr())
     return mssd2, mspd2
 
 
@@ -156,9 +155,7 @@ def vsd_counts(depth_est, depth_gt, depth_test, frame, ray, ray_index, delta, th
     dev = depth_est.device
     frame, ray_index = torch.from_numpy(frame).to(dev), torch.from_numpy(ray_index).to(dev)
     counts = torch.empty(N, 2 + T, dtype=torch.int64, device=dev)
-    _call("gpe_vsd_counts", _lib.ptr(depth_est), _lib.ptr(depth_gt), _lib.i(N), _lib.ptr(depth_test), _lib.i(M), _lib.ptr(frame),
-          _lib.ptr(ray), _lib.i(R), _lib.ptr(ray_index), _lib.i(H), _lib.i(W), _lib.d(delta), _lib.ptr(thr), _lib.i(T), _lib.ptr(counts),
-          _lib.stream_ptr())
+    _call("gpe_vsd_counts", depth_est, depth_gt, N, depth_test, M, frame, ray, R, ray_index, H, W, delta, thr, T, counts, _lib.stream_ptr())
     return counts
 
 

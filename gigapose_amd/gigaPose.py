@@ -69,11 +69,9 @@ def rank_hypotheses(pred, sort=True):
     for s0 in range(0, max(len(srcs), 1), 16):                                   # the launch takes <= 16 tensors
         a, b = srcs[s0:s0 + 16], dsts[s0:s0 + 16]
         n = len(a)
-        src_t = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in a])
-        dst_t = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in b])
+        src_t, dst_t = _lib.ptr_table(a), _lib.ptr_table(b)
         rb_t = (ctypes.c_int * max(n, 1))(*[v[0, 0].numel() * v.element_size() if B else 1 for v in a])
-        _lib.call("gp_rank_hypotheses", _lib.ptr(isc), _lib.i(B), _lib.i(k), _lib.i(num_patches), _lib.i(1 if sort else 0),
-                  _lib.ptr(score), _lib.ptr(order), _lib.i(n), src_t, dst_t, rb_t, _lib.stream_ptr())
+        _lib.call("gp_rank_hypotheses", isc, B, k, num_patches, 1 if sort else 0, score, order, n, src_t, dst_t, rb_t, _lib.stream_ptr())
     for name, v in zip(names, dsts):
         pred.register_tensor(name, v)
     pred.register_tensor("scores", score)

@@ -39,7 +39,7 @@ def pixels_per_workgroup():
 
 
 def runs_workspace_bytes(N, H, W):
-    return int(lib().gpg_runs_workspace_bytes(_lib.i(N), _lib.i(H), _lib.i(W)))
+    return _gtinfo.value("gpg_runs_workspace_bytes", N, H, W)
 
 
 @torch.no_grad()
@@ -80,9 +80,8 @@ def classify(vis, origin, depth, frame, ray, ray_index, delta):
     info = torch.empty(N, INFO, dtype=torch.int64, device=dev)
     box = torch.empty(N, BOX, dtype=torch.int32, device=dev)
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    _call("gpg_classify", _lib.ptr(vis), _lib.i(Hc), _lib.i(Wc), _lib.i(ox), _lib.i(oy), _lib.ptr(depth),
-          _lib.i(0 if depth is None else depth.shape[0]), _lib.ptr(frame), _lib.ptr(ray), _lib.i(R), _lib.ptr(ray_index), _lib.d(delta),
-          _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(cls), _lib.ptr(info), _lib.ptr(box), _lib.ptr(status), _lib.stream_ptr())
+    _call("gpg_classify", vis, Hc, Wc, ox, oy, depth, 0 if depth is None else depth.shape[0], frame, ray, R, ray_index, delta, N, H, W, cls, info, box, status,
+          _lib.stream_ptr())
     return cls, info, box, status
 
 
@@ -112,7 +111,7 @@ def count_runs(cls, which, workspace=None):
         raise ValueError(f"{who}: the workspace is too small ({workspace.numel() * 8} < {need * 8} bytes)")
     _lib.on_gpu(who, workspace=workspace)
     runs = torch.empty(N, dtype=torch.int32, device=cls.device)
-    _call("gpg_count_runs", _lib.ptr(cls), _lib.i(N), _lib.i(H), _lib.i(W), _lib.i(which), _lib.ptr(runs), _lib.ptr(workspace), _lib.stream_ptr())
+    _call("gpg_count_runs", cls, N, H, W, which, runs, workspace, _lib.stream_ptr())
     return runs, workspace
 
 
@@ -130,8 +129,7 @@ def write_runs(cls, which, workspace, offsets, out, err):
     if N > MAX_PAIRS_PER_CALL or workspace.numel() * 8 < runs_workspace_bytes(N, H, W):
         raise ValueError(f"{who}: more than {MAX_PAIRS_PER_CALL} instances, or the workspace is not count_runs'")
     _lib.on_gpu(who, cls=cls, workspace=workspace, offsets=offsets, counts=counts, cum=cum, err=err)
-    _call("gpg_write_runs", _lib.ptr(cls), _lib.i(N), _lib.i(H), _lib.i(W), _lib.i(which), _lib.ptr(workspace), _lib.ptr(offsets),
-          _lib.i(counts.shape[0]), _lib.ptr(counts), _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())
+    _call("gpg_write_runs", cls, N, H, W, which, workspace, offsets, counts.shape[0], counts, cum, err, _lib.stream_ptr())
     return counts, cum
 
 

@@ -138,8 +138,7 @@ class RleDetectionPreprocessor:
     def scan(self, counts, offsets, H, W, err):
         """counts int32[total], offsets int32[D+1] on the device -> cum int32[total] (gpi_rle_scan)."""
         cum = torch.empty_like(counts)
-        _call("gpi_rle_scan", _lib.ptr(counts), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.i(offsets.numel() - 1), _lib.i(H),
-              _lib.i(W), _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())
+        _call("gpi_rle_scan", counts, offsets, counts.numel(), offsets.numel() - 1, H, W, cum, err, _lib.stream_ptr())
         return cum
 
     def _inputs(self, counts, offsets, dev):
@@ -164,8 +163,7 @@ class RleDetectionPreprocessor:
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         cum = self._scan(lists, H, W, err)
         masks = torch.zeros(D, H, W, device=dev)
-        _call("gpi_rle_decode", _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.i(D), _lib.i(H), _lib.i(W),
-              _lib.ptr(masks), _lib.stream_ptr())
+        _call("gpi_rle_decode", cum, offsets, counts.numel(), D, H, W, masks, _lib.stream_ptr())
         bad = int(err.item())
         if bad:
             raise ValueError(f"{type(self).__name__}.decode: detection {bad - 1} has a bad run-length list (no run, a negative "
@@ -197,9 +195,8 @@ class RleDetectionPreprocessor:
             return {"tar_img": tar_img, "tar_mask": tar_mask, "tar_M": M}
         err = torch.zeros(2, dtype=torch.int32, device=dev)     # [0]: the scan's flag, [1]: the crop's
         cum = self._scan(lists, H, W, err[0:1])
-        _call("gpi_preprocess_detections_rle", _lib.ptr(rgb_u8), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()),
-              _lib.ptr(boxes), _lib.ptr(im_id), _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), self._mean, self._std,
-              _lib.ptr(tar_img), _lib.ptr(tar_mask), _lib.ptr(M), _lib.ptr(err[1:2]), _lib.stream_ptr())
+        _call("gpi_preprocess_detections_rle", rgb_u8, cum, offsets, counts.numel(), boxes, im_id, n_img, D, H, W, T, self._mean, self._std, tar_img, tar_mask,
+              M, err[1:2], _lib.stream_ptr())
         bad_list, bad_box = err.tolist()  # one host sync per batch, where DetectionPreprocessor has its own
         if bad_list:
             raise ValueError(f"{who}: detection {bad_list - 1} has a bad run-length list (no run, a negative run "

@@ -8,8 +8,6 @@ src/models/network/resnet.py:26-50, 318-381; Hydra targets in configs/model/ist_
 * `Regressor` / `ISTNet.inference*` -- gather + concat + two MLP heads run in libgigapose_hip.so
   (gp_ist_regress) for every (detection, hypothesis, patch) row at once.
 """
-import ctypes
-
 import torch
 from torch import nn
 
@@ -158,31 +156,23 @@ class ResNet(nn.Module):
         need = _lib.lib().gp_conv2d_planes_workspace_bytes()
         if self._conv_scratch is None or self._conv_scratch.device != dev:
             self._conv_scratch = torch.zeros((need + 3) // 4, dtype=torch.float32, device=dev)
-        _lib.call("gp_conv2d_planes", _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(w[0]), _lib.ptr(w[1]),
-                  _lib.ptr(cv["alpha"]), _lib.ptr(cv["beta"]), _lib.ptr(None if residual is None else residual[0]),
-                  _lib.ptr(None if residual is None else residual[1]), _lib.i(B), _lib.i(H), _lib.i(W), _lib.i(cv["cin"]),
-                  _lib.i(cv["cout"]), _lib.i(cv["k"]), _lib.i(cv["k"]), _lib.i(cv["stride"]), _lib.i(cv["pad"]),
-                  _lib.i(1 if relu else 0), _lib.ptr(None if y is None else y[0]), _lib.ptr(None if y is None else y[1]),
-                  _lib.ptr(out_f32), _lib.ptr(self._conv_scratch), ctypes.c_size_t(need), _lib.stream_ptr())
+        _lib.call("gp_conv2d_planes", x[0], x[1], w[0], w[1], cv["alpha"], cv["beta"], None if residual is None else residual[0],
+                  None if residual is None else residual[1], B, H, W, cv["cin"], cv["cout"], cv["k"], cv["k"], cv["stride"], cv["pad"], 1 if relu else 0,
+                  None if y is None else y[0], None if y is None else y[1], out_f32, self._conv_scratch, need, _lib.stream_ptr())
         oh = (H + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
         return oh, (W + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
 
     def _conv_split(self, cv, w, x, y, B, H, W, residual=None, relu=True, out_f32=None):
         """x, y, residual: (hi, lo) f16 plane pairs, channel-last."""
-        _lib.call("gp_conv2d_nhwc_split", _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(w[0]), _lib.ptr(w[1]),
-                  _lib.ptr(cv["alpha"]), _lib.ptr(cv["beta"]), _lib.ptr(None if residual is None else residual[0]),
-                  _lib.ptr(None if residual is None else residual[1]), _lib.i(B), _lib.i(H), _lib.i(W), _lib.i(cv["cin"]),
-                  _lib.i(cv["cout"]), _lib.i(cv["k"]), _lib.i(cv["k"]), _lib.i(cv["stride"]), _lib.i(cv["pad"]),
-                  _lib.i(1 if relu else 0), _lib.ptr(None if y is None else y[0]), _lib.ptr(None if y is None else y[1]),
-                  _lib.ptr(out_f32), _lib.stream_ptr())
+        _lib.call("gp_conv2d_nhwc_split", x[0], x[1], w[0], w[1], cv["alpha"], cv["beta"], None if residual is None else residual[0],
+                  None if residual is None else residual[1], B, H, W, cv["cin"], cv["cout"], cv["k"], cv["k"], cv["stride"], cv["pad"], 1 if relu else 0,
+                  None if y is None else y[0], None if y is None else y[1], out_f32, _lib.stream_ptr())
         oh = (H + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
         return oh, (W + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
 
     def _conv(self, cv, x, y, B, H, W, residual=None, relu=True, nchw_out=False):
-        _lib.call("gp_conv2d_cm", _lib.ptr(x), _lib.ptr(cv["wt"]), _lib.ptr(y), _lib.ptr(cv["alpha"]),
-                  _lib.ptr(cv["beta"]), _lib.ptr(residual), _lib.i(cv["cin"]), _lib.i(B), _lib.i(H), _lib.i(W),
-                  _lib.i(cv["cout"]), _lib.i(cv["k"]), _lib.i(cv["k"]), _lib.i(cv["stride"]), _lib.i(cv["pad"]),
-                  _lib.i(1 if relu else 0), _lib.i(1 if nchw_out else 0), _lib.stream_ptr())
+        _lib.call("gp_conv2d_cm", x, cv["wt"], y, cv["alpha"], cv["beta"], residual, cv["cin"], B, H, W, cv["cout"], cv["k"], cv["k"], cv["stride"], cv["pad"],
+                  1 if relu else 0, 1 if nchw_out else 0, _lib.stream_ptr())
         oh = (H + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
         return oh, (W + 2 * cv["pad"] - cv["k"]) // cv["stride"] + 1
 
@@ -211,8 +201,7 @@ class ResNet(nn.Module):
         cur, y1, sc, nxt = self._bufs
         if self.numerics == "split" and self.conv_kernel == "256" and self._stem_planes_ok(pk):
             return self._forward_split(pk, None, out, B, S // 2, S // 2, (y1, sc, nxt), images=xin)   # stem in split numerics too
-        _lib.call("gp_resize_bilinear_cm", _lib.ptr(xin), _lib.ptr(self._resized), _lib.i(B), _lib.i(3),
-                  _lib.i(x.shape[2]), _lib.i(x.shape[3]), _lib.i(S), _lib.stream_ptr())
+        _lib.call("gp_resize_bilinear_cm", xin, self._resized, B, 3, x.shape[2], x.shape[3], S, _lib.stream_ptr())
         H, W = self._conv(pk["stem"], self._resized, cur, B, S, S)
         if self.numerics == "split":
             return self._forward_split(pk, cur, out, B, H, W, (y1, sc, nxt))
@@ -266,20 +255,17 @@ class ResNet(nn.Module):
             if getattr(self, "_framed", None) is None or self._framed[0].shape[0] != B or self._framed[0].device != dev:
                 self._framed = (torch.zeros(B, S + 6, S + 8, 4, dtype=torch.float16, device=dev),
                                 torch.zeros(B, S + 6, S + 8, 4, dtype=torch.float16, device=dev))   # the frame stays zero
-            _lib.call("gp_resize_stem_planes", _lib.ptr(images), _lib.ptr(self._framed[0]), _lib.ptr(self._framed[1]), _lib.i(B),
-                      _lib.i(images.shape[2]), _lib.i(images.shape[3]), _lib.i(S), _lib.stream_ptr())
+            _lib.call("gp_resize_stem_planes", images, self._framed[0], self._framed[1], B, images.shape[2], images.shape[3], S, _lib.stream_ptr())
             need = _lib.lib().gp_conv2d_planes_workspace_bytes()
             if self._conv_scratch is None or self._conv_scratch.device != dev:
                 self._conv_scratch = torch.zeros((need + 3) // 4, dtype=torch.float32, device=dev)
             st, sw = pk["stem"], weights["stem"]
-            _lib.call("gp_conv2d_stem_planes", _lib.ptr(self._framed[0]), _lib.ptr(self._framed[1]), _lib.ptr(sw[0]), _lib.ptr(sw[1]),
-                      _lib.ptr(st["alpha"]), _lib.ptr(st["beta"]), _lib.i(B), _lib.i(S), _lib.i(c0), _lib.i(1), _lib.ptr(cur[0]), _lib.ptr(cur[1]),
-                      _lib.ptr(self._conv_scratch), ctypes.c_size_t(need), _lib.stream_ptr())
+            _lib.call("gp_conv2d_stem_planes", self._framed[0], self._framed[1], sw[0], sw[1], st["alpha"], st["beta"], B, S, c0, 1, cur[0], cur[1],
+                      self._conv_scratch, need, _lib.stream_ptr())
         elif use256:   # [C][npix] f32 -> [npix][C] planes of 8 x (single-accumulator convention)
-            _lib.call("gp_planes_from_cm", _lib.ptr(stem_out), _lib.i(c0), _lib.i(npix), _lib.ptr(cur[0]), _lib.ptr(cur[1]), _lib.stream_ptr())
+            _lib.call("gp_planes_from_cm", stem_out, c0, npix, cur[0], cur[1], _lib.stream_ptr())
         else:        # ... of x with the low half scaled by 2^11 (two-accumulator convention; |x| > 65504 raises status bit 16)
-            _lib.call("gp_split_weights", _lib.ptr(stem_out), _lib.i(c0), _lib.i(npix), _lib.i(npix), _lib.ptr(cur[0]),
-                      _lib.ptr(cur[1]), _lib.stream_ptr())
+            _lib.call("gp_split_weights", stem_out, c0, npix, npix, cur[0], cur[1], _lib.stream_ptr())
         for (c1, c2, ds), (w1, w2, wd) in zip(pk["blocks"], weights["blocks"]):
             oh, ow = conv(c1, w1, cur, y1, B, H, W)                             # relu(bn1(conv1(x)))
             short = cur
@@ -362,7 +348,7 @@ class ISTNet(nn.Module):
 
             for seq in (self.regressor.scale_predictor, self.regressor.inplane_predictor):
                 tensors += list(split_planes(seq[0].weight.to(device))) + list(split_planes(seq[2].weight.to(device)))
-        table = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        table = _lib.ptr_table(tensors)
         self._packed = (device, tensors, table, numerics)
 
     @torch.no_grad()
@@ -380,17 +366,15 @@ class ISTNet(nn.Module):
         cos_sin = torch.empty(B, k, P, 2, dtype=torch.float32, device=dev)
         if B == 0:
             return scales, cos_sin
-        need = _lib.lib().gp_ist_workspace_bytes(_lib.i(B), _lib.i(k), _lib.i(D), _lib.i(H))
+        need = _lib.value("gp_ist_workspace_bytes", B, k, D, H)
         if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != dev:
             # zeroed once: the regressor's GEMMs run over compacted rows and the last 128-column tile is only partly filled --
             # its stale columns (never read back) must at least be finite, whatever the allocator handed out
             self._ws = torch.zeros((need + 3) // 4, dtype=torch.float32, device=dev)
         _, tensors, table, _ = self._packed
-        _lib.call("gp_ist_regress", _lib.ptr(tar_feat.contiguous().float()), _lib.ptr(ist_bank.contiguous()),
-                  _lib.ptr(labels0.to(torch.int32).contiguous()), _lib.ptr(id_src.contiguous()),
-                  _lib.ptr(tar_pts.contiguous()), _lib.ptr(src_pts.contiguous()), _lib.i(B), _lib.i(O), _lib.i(N),
-                  _lib.i(k), _lib.i(D), _lib.i(H), table, _lib.i(len(tensors)), _lib.i(1 if self.regressor.use_tanh_act else 0),
-                  _lib.ptr(self._ws), ctypes.c_size_t(need), _lib.ptr(scales), _lib.ptr(cos_sin), _lib.stream_ptr())
+        _lib.call("gp_ist_regress", tar_feat.contiguous().float(), ist_bank.contiguous(), labels0.to(torch.int32).contiguous(), id_src.contiguous(),
+                  tar_pts.contiguous(), src_pts.contiguous(), B, O, N, k, D, H, table, len(tensors), 1 if self.regressor.use_tanh_act else 0, self._ws, need,
+                  scales, cos_sin, _lib.stream_ptr())
         return scales, cos_sin
 
     @torch.no_grad()

@@ -17,7 +17,6 @@ Out of scope: occlusion (the mask of a half-hidden object pulls the fit towards 
 second moments (turns beyond 45 degrees are not attempted), out-of-plane rotation, cameras whose fx and fy differ much or with
 skew, polygon masks.  There is no CPU fallback: a missing library is an error.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -58,8 +57,7 @@ def mask_moments(masks, H, W):
     D = offsets.shape[0] - 1
     mm = torch.empty(D, MASK_ROW, dtype=torch.int64, device=cum.device)
     mstatus = torch.empty(D, dtype=torch.int32, device=cum.device)
-    _call("gpm_mask_moments", _lib.ptr(cum), _lib.ptr(offsets), _lib.i(cum.shape[0]), _lib.i(D), _lib.i(H), _lib.i(W), _lib.ptr(mm), _lib.ptr(mstatus),
-          _lib.stream_ptr())
+    _call("gpm_mask_moments", cum, offsets, cum.shape[0], D, H, W, mm, mstatus, _lib.stream_ptr())
     return mm, mstatus
 
 
@@ -83,8 +81,7 @@ def moments(vis, masks, det, box, out=None):
     rows = _lib.arg(out[0], torch.int64, (N, ROW), who, "rows")
     status = _lib.arg(out[1], torch.int32, (N,), who, "status")
     _lib.on_gpu(who, rows=rows, status=status)
-    _call("gpm_moments", _lib.ptr(vis), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(cum.shape[0]), _lib.i(offsets.shape[0] - 1), _lib.ptr(det), _lib.ptr(box),
-          _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rows), _lib.ptr(status), _lib.stream_ptr())
+    _call("gpm_moments", vis, cum, offsets, cum.shape[0], offsets.shape[0] - 1, det, box, N, H, W, rows, status, _lib.stream_ptr())
     return rows, status
 
 
@@ -132,9 +129,8 @@ def update(rows, status, mm, det, clipped, K, start, it, last, poses, poses32, b
         raise ValueError(f"{who}: {N} pairs in one call (at most {MAX_PAIRS_PER_CALL}: MaskRefiner chunks)")
     given = {} if clipped is None else dict(clipped=clipped)
     _lib.on_gpu(who, rows=rows, status=status, mm=mm, det=det, K=K, start=start, poses=poses, poses32=poses32, best=best, score=score, state=state, **given)
-    _call("gpm_update", _lib.ptr(rows), _lib.ptr(status), _lib.ptr(mm), _lib.i(mm.shape[0]), _lib.ptr(det), _lib.ptr(clipped), _lib.ptr(K), _lib.ptr(start),
-          _lib.i(N), _lib.i(it), _lib.i(1 if last else 0), ctypes.c_longlong(int(min_points)), _lib.d(min_elongation), _lib.d(gain), _lib.ptr(poses),
-          _lib.ptr(poses32), _lib.ptr(best), _lib.ptr(score), _lib.ptr(state), _lib.stream_ptr())
+    _call("gpm_update", rows, status, mm, mm.shape[0], det, clipped, K, start, N, it, 1 if last else 0, int(min_points), min_elongation, gain, poses, poses32,
+          best, score, state, _lib.stream_ptr())
     return poses, poses32, best, score, state
 
 

@@ -35,8 +35,7 @@ default_numerics = _lib.default_numerics   # "split" unless GIGAPOSE_NUMERICS=ch
 
 def _l2norm_split(x, hi, lo, rows, C):
     """gp_l2norm_split_mask without a mask image: the split normalisation alone."""
-    _lib.call("gp_l2norm_split_mask", _lib.ptr(x), _lib.ptr(hi), _lib.ptr(lo), _lib.i(rows), _lib.i(C), _lib.ptr(None), _lib.i(0), _lib.i(0),
-              _lib.ptr(None), _lib.stream_ptr())
+    _lib.call("gp_l2norm_split_mask", x, hi, lo, rows, C, None, 0, 0, None, _lib.stream_ptr())
 
 
 def normalize_split(feats, mask224=None):
@@ -56,8 +55,7 @@ def normalize_split(feats, mask224=None):
         _l2norm_split(x, hi, lo, rows, C)
         return hi, lo, patch_grid_mask(mask224)
     qmask = torch.empty(rows, P, dtype=torch.float32, device=x.device)
-    _lib.call("gp_l2norm_split_mask", _lib.ptr(x), _lib.ptr(hi), _lib.ptr(lo), _lib.i(rows), _lib.i(C), _lib.ptr(mask224),
-              _lib.i(mask224.shape[1]), _lib.i(mask224.shape[2]), _lib.ptr(qmask), _lib.stream_ptr())
+    _lib.call("gp_l2norm_split_mask", x, hi, lo, rows, C, mask224, mask224.shape[1], mask224.shape[2], qmask, _lib.stream_ptr())
     return hi, lo, qmask
 
 
@@ -70,8 +68,7 @@ def patch_masks(mask224):
     if not fused:   # another dtype / layout: the strided copy
         return patch_grid_mask(mask224)
     qmask = torch.empty(rows, P, dtype=torch.float32, device=mask224.device)
-    _lib.call("gp_l2norm_split_mask", _lib.ptr(None), _lib.ptr(None), _lib.ptr(None), _lib.i(rows), _lib.i(32), _lib.ptr(mask224),
-              _lib.i(mask224.shape[1]), _lib.i(mask224.shape[2]), _lib.ptr(qmask), _lib.stream_ptr())
+    _lib.call("gp_l2norm_split_mask", None, None, None, rows, 32, mask224, mask224.shape[1], mask224.shape[2], qmask, _lib.stream_ptr())
     return qmask
 
 
@@ -98,8 +95,7 @@ class MatchBank:
             self.lo = lo.view(O, N, P, -1) if self.bank_dtype == "f32" else None
         else:
             self.features = torch.empty_like(feats)
-            _lib.call("gp_l2norm_cp", _lib.ptr(feats), _lib.ptr(self.features), _lib.i(O * N), _lib.i(C),
-                      _lib.stream_ptr())
+            _lib.call("gp_l2norm_cp", feats, self.features, O * N, C, _lib.stream_ptr())
             self.features = self.features.view(O, N, C, P)
         self.masks = patch_grid_mask(masks224)
         self.O, self.N, self.C = O, N, C
@@ -133,7 +129,7 @@ class LocalSimilarity(torch.nn.Module):
         rows, C = feats.shape[:2]
         x = feats.reshape(rows, C, P).contiguous().float()
         out = torch.empty_like(x)
-        _lib.call("gp_l2norm_cp", _lib.ptr(x), _lib.ptr(out), _lib.i(rows), _lib.i(C), _lib.stream_ptr())
+        _lib.call("gp_l2norm_cp", x, out, rows, C, _lib.stream_ptr())
         return out
 
     def match_tiles(self, query, qmask, bank, labels0, search_direction=None, out=None):
@@ -158,15 +154,11 @@ class LocalSimilarity(torch.nn.Module):
             avg = torch.empty(B, N, dtype=torch.float32, device=dev)
         direction = 1 if (search_direction or self.search_direction) == "src2tar" else 0   # reference matching.py:239-244
         if split:
-            _lib.call("gp_match_tiles_split_dir", _lib.ptr(query[0]), _lib.ptr(query[1]), _lib.ptr(bank.hi), _lib.ptr(bank.lo),
-                      _lib.ptr(qmask), _lib.ptr(bank.masks), _lib.ptr(labels0), _lib.i(B), _lib.i(bank.O), _lib.i(N),
-                      _lib.i(C), _lib.f(self.sim_threshold), _lib.f(self.patch_threshold), _lib.i(direction), _lib.ptr(idx),
-                      _lib.ptr(sc), _lib.ptr(ma), _lib.ptr(avg), _lib.stream_ptr())
+            _lib.call("gp_match_tiles_split_dir", query[0], query[1], bank.hi, bank.lo, qmask, bank.masks, labels0, B, bank.O, N, C, self.sim_threshold,
+                      self.patch_threshold, direction, idx, sc, ma, avg, _lib.stream_ptr())
             return idx, sc, ma, avg
-        _lib.call("gp_match_tiles_dir", _lib.ptr(query), _lib.ptr(bank.features), _lib.ptr(qmask),
-                  _lib.ptr(bank.masks), _lib.ptr(labels0), _lib.i(B), _lib.i(bank.O), _lib.i(N), _lib.i(C),
-                  _lib.f(self.sim_threshold), _lib.f(self.patch_threshold), _lib.i(direction), _lib.ptr(idx), _lib.ptr(sc),
-                  _lib.ptr(ma), _lib.ptr(avg), _lib.stream_ptr())
+        _lib.call("gp_match_tiles_dir", query, bank.features, qmask, bank.masks, labels0, B, bank.O, N, C, self.sim_threshold, self.patch_threshold, direction,
+                  idx, sc, ma, avg, _lib.stream_ptr())
         return idx, sc, ma, avg
 
     def topk(self, sim_avg, k=None):
@@ -176,8 +168,7 @@ class LocalSimilarity(torch.nn.Module):
             raise RuntimeError("selected index k out of range")  # torch.topk's error (matching.py:279)
         ids = torch.empty(B, k, dtype=torch.int32, device=sim_avg.device)
         scores = torch.empty(B, k, dtype=torch.float32, device=sim_avg.device)
-        _lib.call("gp_topk", _lib.ptr(sim_avg), _lib.i(B), _lib.i(N), _lib.i(k), _lib.ptr(ids),
-                  _lib.ptr(scores), _lib.stream_ptr())
+        _lib.call("gp_topk", sim_avg, B, N, k, ids, scores, _lib.stream_ptr())
         return ids, scores
 
     def gather_records(self, ids, idx, sc, ma):
@@ -187,17 +178,14 @@ class LocalSimilarity(torch.nn.Module):
         rec_idx = torch.empty(B, k, P, dtype=torch.uint8, device=dev)
         rec_score = torch.empty(B, k, P, dtype=torch.float32, device=dev)
         rec_mask = torch.empty(B, k, P, dtype=torch.float32, device=dev)
-        _lib.call("gp_gather_records", _lib.ptr(ids), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(ma), _lib.i(B),
-                  _lib.i(N), _lib.i(k), _lib.ptr(rec_idx), _lib.ptr(rec_score), _lib.ptr(rec_mask),
-                  _lib.stream_ptr())
+        _lib.call("gp_gather_records", ids, idx, sc, ma, B, N, k, rec_idx, rec_score, rec_mask, _lib.stream_ptr())
         return rec_idx, rec_score, rec_mask
 
     def format_points(self, rec_idx, rec_mask):
         B, k = rec_idx.shape[:2]
         tar_pts = torch.empty(B, k, P, 2, dtype=torch.int64, device=rec_idx.device)
         src_pts = torch.empty(B, k, P, 2, dtype=torch.int64, device=rec_idx.device)
-        _lib.call("gp_format_points", _lib.ptr(rec_idx), _lib.ptr(rec_mask), _lib.i(B * k), _lib.ptr(tar_pts),
-                  _lib.ptr(src_pts), _lib.stream_ptr())
+        _lib.call("gp_format_points", rec_idx, rec_mask, B * k, tar_pts, src_pts, _lib.stream_ptr())
         return tar_pts, src_pts
 
     def select_topk(self, sim_avg, idx, sc, ma, k=None):
@@ -213,8 +201,7 @@ class LocalSimilarity(torch.nn.Module):
         rec_score = torch.empty(B, k, P, dtype=torch.float32, device=dev)
         tar_pts = torch.empty(B, k, P, 2, dtype=torch.int64, device=dev)
         src_pts = torch.empty(B, k, P, 2, dtype=torch.int64, device=dev)
-        _lib.call("gp_select_topk", _lib.ptr(sim_avg), _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(ma), _lib.i(B), _lib.i(N), _lib.i(k), _lib.ptr(ids),
-                  _lib.ptr(scores), _lib.ptr(rec_score), _lib.ptr(tar_pts), _lib.ptr(src_pts), _lib.stream_ptr())
+        _lib.call("gp_select_topk", sim_avg, idx, sc, ma, B, N, k, ids, scores, rec_score, tar_pts, src_pts, _lib.stream_ptr())
         return ids, scores, rec_score, tar_pts, src_pts
 
     # ---- resident-bank entry point (what GigaPose.eval_retrieval uses) --------------------

@@ -40,7 +40,7 @@ def _device_renders(rgba_u8, who):
     if not (rgba_u8.dtype == torch.uint8 and rgba_u8.dim() == 4 and rgba_u8.shape[3] == 4):
         raise ValueError(f"{who}: expected u8 renders (N, H, W, 4), got {rgba_u8.dtype} {tuple(rgba_u8.shape)}")
     rgba_u8 = rgba_u8.contiguous()
-    if rgba_u8.data_ptr() % 4:                       # a byte view at an odd offset: one pixel must be one aligned word
+    if rgba_u8.storage_offset() % 4:                 # a byte view at an odd offset (allocations start aligned): one pixel must be one aligned word
         rgba_u8 = rgba_u8.clone()
     return rgba_u8
 
@@ -49,8 +49,7 @@ def _alpha_boxes(rgba_u8, boxes, err):
     """boxes (N,4) int64 and err (chunks,) int32 on the device; chunk c of 65535 renders reports into err[c]."""
     N, H, W, _ = rgba_u8.shape
     for c, a, b in _lib.chunked(N, MAX_TEMPLATES_PER_CALL):
-        _call("gpo_alpha_boxes", _lib.ptr(rgba_u8[a:b]), _lib.i(b - a), _lib.i(H), _lib.i(W), _lib.ptr(boxes[a:b]), _lib.ptr(err[c:c + 1]),
-              _lib.stream_ptr())
+        _call("gpo_alpha_boxes", rgba_u8[a:b], b - a, H, W, boxes[a:b], err[c:c + 1], _lib.stream_ptr())
 
 
 @torch.no_grad()
@@ -103,9 +102,8 @@ class TemplateOnboarder:
             boxes = torch.empty(N, 4, dtype=torch.int64, device=dev)
             _alpha_boxes(rgba_u8, boxes, err[0])
         for c, a, b in _lib.chunked(N, MAX_TEMPLATES_PER_CALL):
-            _call("gpo_crop_templates", _lib.ptr(rgba_u8[a:b]), _lib.ptr(boxes[a:b]), _lib.i(b - a), _lib.i(H), _lib.i(W), _lib.i(T),
-                  self._mean, self._std, _lib.ptr(out["rgb"][a:b]), _lib.ptr(out["mask"][a:b]), _lib.ptr(out["M"][a:b]),
-                  _lib.ptr(err[1, c:c + 1]), _lib.stream_ptr())
+            _call("gpo_crop_templates", rgba_u8[a:b], boxes[a:b], b - a, H, W, T, self._mean, self._std, out["rgb"][a:b], out["mask"][a:b], out["M"][a:b],
+                  err[1, c:c + 1], _lib.stream_ptr())
         no_alpha, no_crop = err.tolist()
         bad = _lib.first_bad(no_alpha, MAX_TEMPLATES_PER_CALL)
         if bad is not None:

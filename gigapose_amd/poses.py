@@ -35,10 +35,8 @@ class RANSAC(torch.nn.Module):
         weights = None if scores is None else scores.to(dev).float().contiguous()
         if weights is not None and tuple(weights.shape) != tuple(src_pts.shape[:-1]):
             raise ValueError(f"scores must have shape {tuple(src_pts.shape[:-1])}, got {tuple(weights.shape)}")
-        _lib.call("gp_ransac_scored", _lib.ptr(src_pts.contiguous()), _lib.ptr(tar_pts.contiguous()),
-                  _lib.ptr(rel_scale.contiguous().float()), _lib.ptr(rel_inplane.contiguous().float()), _lib.ptr(weights), _lib.i(R),
-                  _lib.f(self.patch_size), _lib.f(self.pixel_threshold), _lib.ptr(M), _lib.ptr(failed),
-                  _lib.ptr(isrc), _lib.ptr(itar), _lib.ptr(isc), _lib.stream_ptr())
+        _lib.call("gp_ransac_scored", src_pts.contiguous(), tar_pts.contiguous(), rel_scale.contiguous().float(), rel_inplane.contiguous().float(), weights, R,
+                  self.patch_size, self.pixel_threshold, M, failed, isrc, itar, isc, _lib.stream_ptr())
         return M, failed.view(torch.bool), isrc, itar, isc   # the kernel writes 0 / 1 bytes: a reinterpretation, not a conversion launch
 
     def forward(self, batch, scores=None, direction="src2tar"):
@@ -83,11 +81,8 @@ class ObjectPoseRecovery(torch.nn.Module):
         if self._flag is None or self._flag.device != dev:
             self._flag = torch.zeros(1, dtype=torch.int32, device=dev)
         flag = self._flag
-        _lib.call("gp_recover_poses", _lib.ptr(labels0), _lib.ptr(tar_K.contiguous().float()),
-                  _lib.ptr(tar_M.contiguous().float()), _lib.ptr(pred_src_views.contiguous().long()),
-                  _lib.ptr(pred_M.contiguous().float()), _lib.ptr(self.template_K), _lib.ptr(self.template_Ms),
-                  _lib.ptr(self.template_poses), _lib.i(B), _lib.i(O), _lib.i(N), _lib.i(k), _lib.ptr(poses),
-                  _lib.ptr(flag), _lib.stream_ptr())
+        _lib.call("gp_recover_poses", labels0, tar_K.contiguous().float(), tar_M.contiguous().float(), pred_src_views.contiguous().long(),
+                  pred_M.contiguous().float(), self.template_K, self.template_Ms, self.template_poses, B, O, N, k, poses, flag, _lib.stream_ptr())
         if self.check_asserts == "deferred":
             self.deferred_flag = flag
         elif self.check_asserts and B > 0:

@@ -18,8 +18,6 @@ the labels do not depend on launch geometry; gigapose_testing/label_ref.py resta
 Out of scope: the segmenter, CNOS's appearance and visibility scores, objects with different template counts.  (A mask-IoU NMS
 is detections.mask_nms; ProposalLabeller(nms_on="mask") routes through it.)  There is no CPU fallback: the kernels need the GPU, a missing library is an error.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -58,8 +56,7 @@ def descriptors(x, crop_stride, channel_stride, gamma, beta, eps, B, C):
         raise ValueError(f"{who}: x is not contiguous (the strides are passed, not taken from the tensor)")
     q = torch.empty(B, C, dtype=torch.int32, device=x.device)
     status = torch.empty(B, dtype=torch.int32, device=x.device)
-    _call("gpa_descriptors", _lib.ptr(x), ctypes.c_longlong(crop_stride), ctypes.c_longlong(channel_stride), _lib.ptr(gamma),
-          _lib.ptr(beta), _lib.d(eps), _lib.i(B), _lib.i(C), _lib.ptr(q), _lib.ptr(status), _lib.stream_ptr())
+    _call("gpa_descriptors", x, crop_stride, channel_stride, gamma, beta, eps, B, C, q, status, _lib.stream_ptr())
     return q, status
 
 
@@ -84,9 +81,8 @@ def scores(q, bank_q, k, want=()):
     dot = torch.empty(P if "dot" in want else min(P, step), O, T, dtype=torch.int64, device=dev)
     for a in range(0, P, step):
         b = min(P, a + step)
-        _call("gpa_scores", _lib.ptr(q[a:b]), _lib.ptr(bank_q), _lib.i(b - a), _lib.i(O), _lib.i(T), _lib.i(C), _lib.i(k),
-              _lib.ptr(dot[a:b] if "dot" in want else dot), _lib.ptr(None if obj is None else obj[a:b]), _lib.ptr(out["label"][a:b]),
-              _lib.ptr(out["score"][a:b]), _lib.ptr(out["best_template"][a:b]), _lib.stream_ptr())
+        _call("gpa_scores", q[a:b], bank_q, b - a, O, T, C, k, dot[a:b] if "dot" in want else dot, None if obj is None else obj[a:b], out["label"][a:b],
+              out["score"][a:b], out["best_template"][a:b], _lib.stream_ptr())
     if obj is not None:
         out["obj"] = obj
     if "dot" in want:
@@ -114,8 +110,7 @@ def run_boxes(cum, offsets, H, W):
     area = torch.empty(D, dtype=torch.int64, device=dev)
     status = torch.empty(D, dtype=torch.int32, device=dev)
     for _, a, b in _lib.chunked(D, MAX_MASKS_PER_CALL):
-        _call("gpa_run_boxes", _lib.ptr(cum), _lib.ptr(offsets[a:b + 1]), _lib.i(cum.numel()), _lib.i(b - a), _lib.i(H), _lib.i(W),
-              _lib.ptr(box[a:b]), _lib.ptr(area[a:b]), _lib.ptr(status[a:b]), _lib.stream_ptr())
+        _call("gpa_run_boxes", cum, offsets[a:b + 1], cum.numel(), b - a, H, W, box[a:b], area[a:b], status[a:b], _lib.stream_ptr())
     return box, area, status
 
 
@@ -140,8 +135,7 @@ def scan_lists(who, counts, offsets, H, W, device="cuda"):
     err = torch.zeros(max(1, -(-D // MAX_MASKS_PER_CALL)), dtype=torch.int32, device=counts.device)
     cum = torch.empty_like(counts)
     for c, a, b in _lib.chunked(D, MAX_MASKS_PER_CALL):
-        _ingest_call("gpi_rle_scan", _lib.ptr(counts), _lib.ptr(offsets[a:b + 1]), _lib.i(counts.numel()), _lib.i(b - a), _lib.i(H), _lib.i(W),
-                    _lib.ptr(cum), _lib.ptr(err[c:c + 1]), _lib.stream_ptr())
+        _ingest_call("gpi_rle_scan", counts, offsets[a:b + 1], counts.numel(), b - a, H, W, cum, err[c:c + 1], _lib.stream_ptr())
 
     def check():
         bad = _lib.first_bad(err.tolist(), MAX_MASKS_PER_CALL)
@@ -183,8 +177,7 @@ def nms(box, label, num, den, per_label=False):
     _lib.on_gpu(who, box=box)
     words = (P + 63) // 64
     sup = torch.empty(P, words, dtype=torch.int64, device=box.device)
-    _call("gpa_nms_matrix", _lib.ptr(box), _lib.ptr(label if per_label else None), _lib.i(P), _lib.i(num), _lib.i(den), _lib.i(1 if per_label else 0),
-          _lib.ptr(sup), _lib.stream_ptr())
+    _call("gpa_nms_matrix", box, label if per_label else None, P, num, den, 1 if per_label else 0, sup, _lib.stream_ptr())
     return nms_keep(sup)
 
 
@@ -199,7 +192,7 @@ def nms_keep(sup):
         raise ValueError(f"{who}: expected sup (P, (P + 63) // 64) with P <= {MAX_NMS}, got {tuple(sup.shape)}")
     _lib.on_gpu(who, sup=sup)
     keep = torch.empty(P, dtype=torch.uint8, device=sup.device)
-    _call("gpa_nms_keep", _lib.ptr(sup), _lib.i(P), _lib.ptr(keep), _lib.stream_ptr())
+    _call("gpa_nms_keep", sup, P, keep, _lib.stream_ptr())
     return keep
 
 

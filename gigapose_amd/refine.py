@@ -17,7 +17,6 @@ Out of scope: nearest-neighbour association (a point is compared with the measur
 the gate, the MegaPose network, colour; scores are left as they are (choosing among hypotheses: gigapose_amd/verify.py).  There is no CPU fallback: a
 missing library is an error.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -52,8 +51,7 @@ def face_normals(vertices, faces):
         raise ValueError(f"{who}: V = 0 vertices")
     _lib.on_gpu(who, vertices=vertices, faces=faces)
     c = torch.empty(faces.shape[0], 3, dtype=torch.float64, device=vertices.device)
-    _call("gpf_face_normals", _lib.ptr(vertices), _lib.i(vertices.shape[0]), _lib.ptr(faces), _lib.i(faces.shape[0]), _lib.ptr(c),
-          _lib.stream_ptr())
+    _call("gpf_face_normals", vertices, vertices.shape[0], faces, faces.shape[0], c, _lib.stream_ptr())
     return c
 
 
@@ -83,9 +81,7 @@ def accumulate(vis, c, poses, K, depth, frame, box, gate, scale, out=None):
     sums = _lib.arg(out[0], torch.int64, (N, SUMS), who, "sums")
     status = _lib.arg(out[1], torch.int32, (N,), who, "status")
     _lib.on_gpu(who, sums=sums, status=status)
-    _call("gpf_accumulate", _lib.ptr(vis), _lib.ptr(c), _lib.i(c.shape[0]), _lib.ptr(poses), _lib.ptr(K), _lib.ptr(depth), _lib.i(depth.shape[0]),
-          _lib.ptr(frame), _lib.ptr(box), _lib.ptr(gate), _lib.ptr(scale), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(sums), _lib.ptr(status),
-          _lib.stream_ptr())
+    _call("gpf_accumulate", vis, c, c.shape[0], poses, K, depth, depth.shape[0], frame, box, gate, scale, N, H, W, sums, status, _lib.stream_ptr())
     return sums, status
 
 
@@ -118,8 +114,7 @@ def update(sums, clipped, scale, start, poses, poses32, state, min_points=32, mi
         raise ValueError(f"{who}: {N} pairs in one call (at most {MAX_PAIRS_PER_CALL}: DepthRefiner chunks)")
     given = {k: v for k, v in dict(clipped=clipped, start=start).items() if v is not None}
     _lib.on_gpu(who, sums=sums, scale=scale, poses=poses, poses32=poses32, state=state, **given)
-    _call("gpf_update", _lib.ptr(sums), _lib.ptr(clipped), _lib.ptr(scale), _lib.ptr(start), _lib.i(N), ctypes.c_longlong(int(min_points)),
-          _lib.d(min_pivot), _lib.d(damping), _lib.d(tol2), _lib.ptr(poses), _lib.ptr(poses32), _lib.ptr(state), _lib.stream_ptr())
+    _call("gpf_update", sums, clipped, scale, start, N, int(min_points), min_pivot, damping, tol2, poses, poses32, state, _lib.stream_ptr())
     return poses, poses32, state
 
 

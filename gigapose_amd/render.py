@@ -215,8 +215,7 @@ def project(vertices, poses, K, znear, out=None):
     V, N = vertices.shape[0], poses.shape[0]
     xy, depth = out if out is not None else (torch.empty(N, V, 2, dtype=torch.int32, device=vertices.device),
                                              torch.empty(N, V, dtype=torch.float32, device=vertices.device))
-    _call("gpr_project", _lib.ptr(vertices), _lib.i(V), _lib.ptr(poses), _lib.i(N), K if isinstance(K, ctypes.Array) else _k9(K),
-          ctypes.c_float(znear), _lib.ptr(xy), _lib.ptr(depth), _lib.stream_ptr())
+    _call("gpr_project", vertices, V, poses, N, K if isinstance(K, ctypes.Array) else _k9(K), znear, xy, depth, _lib.stream_ptr())
     return xy[:N], depth[:N]
 
 
@@ -232,13 +231,12 @@ def raster(xy, vdepth, faces, H, W, out=None, workspace=None):
     F, dev = faces.shape[0], xy.device
     vis, clipped = out if out is not None else (torch.empty(N, H, W, dtype=torch.int64, device=dev),
                                                 torch.empty(N, dtype=torch.int32, device=dev))
-    need = int(lib().gpr_raster_workspace_bytes(_lib.i(N), _lib.i(F)))
+    need = _render.value("gpr_raster_workspace_bytes", N, F)
     if workspace is None:
         workspace = torch.empty(-(-need // 8), dtype=torch.int64, device=dev)
     if workspace.numel() * workspace.element_size() < need or vis.numel() < N * H * W or clipped.numel() < N:
         raise ValueError("raster: a buffer is too small")
-    _call("gpr_raster", _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.i(N), _lib.i(H), _lib.i(W),
-          _lib.ptr(vis), _lib.ptr(clipped), _lib.ptr(workspace), _lib.stream_ptr())
+    _call("gpr_raster", xy, vdepth, V, faces, F, N, H, W, vis, clipped, workspace, _lib.stream_ptr())
     return vis[:N], clipped[:N]
 
 
@@ -270,8 +268,7 @@ def resolve(vis, xy, vdepth, faces, colours, out=None):
     vis, xy, vdepth, faces, N, H, W, V, F = key_inputs("resolve", vis, xy, vdepth, faces)
     colours = _lib.on_device(colours, torch.uint8, (V, 3), "resolve", "colours")
     rgba, depth = resolve_out("resolve", out, N, H, W, vis.device)
-    _call("gpr_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(colours),
-          _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.stream_ptr())
+    _call("gpr_resolve", vis, xy, vdepth, V, faces, F, colours, N, H, W, rgba, depth, _lib.stream_ptr())
     return rgba, depth
 
 
@@ -285,7 +282,7 @@ class KeyBuffers:
         self.xy = torch.empty(n, V, 2, dtype=torch.int32, device=device)
         self.vdepth = torch.empty(n, V, dtype=torch.float32, device=device)
         self.vis = torch.empty(n, H, W, dtype=torch.int64, device=device)
-        self.work = torch.empty(max(1, -(-int(lib().gpr_raster_workspace_bytes(_lib.i(n), _lib.i(F))) // 8)), dtype=torch.int64, device=device)
+        self.work = torch.empty(max(1, -(-_render.value("gpr_raster_workspace_bytes", n, F) // 8)), dtype=torch.int64, device=device)
 
     def draw(self, vertices, faces, poses32, K9, znear, clipped):
         pxy, pz = project(vertices, poses32, K9, znear, out=(self.xy, self.vdepth))

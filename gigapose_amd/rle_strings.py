@@ -152,9 +152,7 @@ class StringRleDetectionPreprocessor(RleDetectionPreprocessor):
         """bytes uint8[n_bytes], byte_offsets / offsets int32[D+1], counts int32[total] on the device -> cum int32[total]; the
         string detections' slots of `counts` receive their decoded lists (gps_rle_string_scan)."""
         cum = torch.empty_like(counts)
-        _call("gps_rle_string_scan", _lib.ptr(data), _lib.ptr(byte_offsets), _lib.i(data.numel()), _lib.ptr(offsets),
-              _lib.i(counts.numel()), _lib.i(offsets.numel() - 1), _lib.i(H), _lib.i(W), _lib.ptr(counts), _lib.ptr(cum), _lib.ptr(err),
-              _lib.stream_ptr())
+        _call("gps_rle_string_scan", data, byte_offsets, data.numel(), offsets, counts.numel(), offsets.numel() - 1, H, W, counts, cum, err, _lib.stream_ptr())
         return cum
 
     def _scan(self, lists, H, W, err):

@@ -68,8 +68,7 @@ def vertex_normals_raw(vertices, faces, unit, out=None):
                                                        torch.empty(V, 3, dtype=torch.float64, device=dev))
     if tuple(acc.shape) != (V, 3) or tuple(flags.shape) != (V,) or tuple(normals.shape) != (V, 3):
         raise ValueError(f"{who}: out must be acc (V,3), flags (V,) and normals (V,3)")
-    _call("gpl_vertex_normals", _lib.ptr(vertices), _lib.i(V), _lib.ptr(faces), _lib.i(faces.shape[0]), ctypes.c_double(unit), _lib.ptr(acc),
-          _lib.ptr(flags), _lib.ptr(normals), _lib.stream_ptr())
+    _call("gpl_vertex_normals", vertices, V, faces, faces.shape[0], unit, acc, flags, normals, _lib.stream_ptr())
     return acc, flags, normals
 
 
@@ -176,10 +175,8 @@ def shade(vis, xy, vdepth, faces, colours, vertices, normals, poses, K, lights, 
     rows = _lights(lights, who)
     rgba, depth, unlit = render.resolve_out(who, out, N, H, W, vis.device, unlit=True)
     host_lights = (ctypes.c_double * max(1, rows.size))(*rows.reshape(-1).tolist())
-    _call("gpl_shade", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(colours),
-          _lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(poses), K if isinstance(K, ctypes.Array) else render._k9(K), host_lights,
-          _lib.i(len(rows)), ctypes.c_double(ambient), _lib.ptr(decode), _lib.ptr(encode), _lib.i(encode.shape[0]), _lib.i(mode), _lib.i(N),
-          _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.ptr(unlit), _lib.stream_ptr())
+    _call("gpl_shade", vis, xy, vdepth, V, faces, F, colours, vertices, normals, poses, K if isinstance(K, ctypes.Array) else render._k9(K), host_lights,
+          len(rows), ambient, decode, encode, encode.shape[0], mode, N, H, W, rgba, depth, unlit, _lib.stream_ptr())
     return rgba, depth, unlit
 
 

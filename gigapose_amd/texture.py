@@ -31,11 +31,11 @@ TEXTURE_LIB_PATH, lib, _call = _texture.path, _texture.lib, _texture.call
 
 
 def mip_levels(Ht, Wt):
-    return int(lib().gpt_mip_levels(_lib.i(Ht), _lib.i(Wt)))
+    return _texture.value("gpt_mip_levels", Ht, Wt)
 
 
 def mip_texels(Ht, Wt):
-    return int(lib().gpt_mip_texels(_lib.i(Ht), _lib.i(Wt)))
+    return _texture.value("gpt_mip_texels", Ht, Wt)
 
 
 # ------------------------------------------------------------------------------------------------ loaders
@@ -111,7 +111,7 @@ def build_mips(rgb):
     _check_texture_shape(rgb.shape, "build_mips")
     Ht, Wt = rgb.shape[:2]
     pyramid = torch.empty(mip_texels(Ht, Wt), dtype=torch.int32, device=rgb.device)
-    _call("gpt_build_mips", _lib.ptr(rgb), _lib.i(Ht), _lib.i(Wt), _lib.ptr(pyramid), _lib.stream_ptr())
+    _call("gpt_build_mips", rgb, Ht, Wt, pyramid, _lib.stream_ptr())
     return pyramid
 
 
@@ -126,8 +126,7 @@ def resolve_textured(vis, xy, vdepth, faces, corner_uv, pyramid, size, out=None)
     _check_texture_shape((Ht, Wt, 3), who)
     pyramid = _lib.on_device(pyramid, torch.int32, (mip_texels(Ht, Wt),), who, "pyramid")
     rgba, depth = render.resolve_out(who, out, N, H, W, vis.device)
-    _call("gpt_resolve", _lib.ptr(vis), _lib.ptr(xy), _lib.ptr(vdepth), _lib.i(V), _lib.ptr(faces), _lib.i(F), _lib.ptr(corner_uv),
-          _lib.ptr(pyramid), _lib.i(Ht), _lib.i(Wt), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rgba), _lib.ptr(depth), _lib.stream_ptr())
+    _call("gpt_resolve", vis, xy, vdepth, V, faces, F, corner_uv, pyramid, Ht, Wt, N, H, W, rgba, depth, _lib.stream_ptr())
     return rgba, depth
 
 

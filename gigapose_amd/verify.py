@@ -74,9 +74,8 @@ def counts(vis, depth, frame, masks, det, box, tol, out=None):
     rows = _lib.arg(out[0], torch.int64, (N, COUNTS), who, "counts")
     status = _lib.arg(out[1], torch.int32, (N,), who, "status")
     _lib.on_gpu(who, counts=rows, status=status)
-    _call("gpv_counts", _lib.ptr(vis), _lib.ptr(depth), _lib.i(0 if depth is None else depth.shape[0]), _lib.ptr(frame), _lib.ptr(cum),
-          _lib.ptr(offsets), _lib.i(0 if cum is None else cum.shape[0]), _lib.i(0 if cum is None else offsets.shape[0] - 1), _lib.ptr(det),
-          _lib.ptr(box), _lib.ptr(tol), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(rows), _lib.ptr(status), _lib.stream_ptr())
+    _call("gpv_counts", vis, depth, 0 if depth is None else depth.shape[0], frame, cum, offsets, 0 if cum is None else cum.shape[0],
+          0 if cum is None else offsets.shape[0] - 1, det, box, tol, N, H, W, rows, status, _lib.stream_ptr())
     return rows, status
 
 

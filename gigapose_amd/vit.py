@@ -43,7 +43,7 @@ def split_planes_x64(w):
     w = w.detach().float().contiguous()
     hi = torch.empty(w.shape, dtype=torch.float16, device=w.device)
     lo = torch.empty_like(hi)
-    _lib.call("gp_split256_weights", _lib.ptr(w), ctypes.c_size_t(w.numel()), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split256_weights", w, w.numel(), hi, lo, _lib.stream_ptr())
     return hi, lo
 
 
@@ -222,7 +222,7 @@ class Dinov2ViT(nn.Module):
                         dev(blk.norm2.weight), dev(blk.norm2.bias),
                         dev(blk.mlp.fc1.weight.t()), dev(blk.mlp.fc1.bias),
                         dev(blk.mlp.fc2.weight.t()), dev(blk.mlp.fc2.bias), dev(blk.ls2.gamma)]
-        table = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        table = _lib.ptr_table(tensors)
         split, split_table = [], None
         if self.numerics == "split":  # pre-split weight planes, PyTorch-native [out][in] (k contiguous)
             for blk in self.blocks:
@@ -239,11 +239,11 @@ class Dinov2ViT(nn.Module):
                     split += [qkv_hi[:2 * C], qkv_lo[:2 * C], qkv_hi[2 * C:], qkv_lo[2 * C:]]
                     for w in ws[2:]:
                         split += list(split_planes_x64(w))
-            split_table = (ctypes.c_void_p * len(split))(*[t.data_ptr() for t in split])
+            split_table = _lib.ptr_table(split)
         self._packed = (device, tensors, table, split, split_table)
 
     def _workspace(self, B, device):
-        need = _lib.lib().gp_vit_workspace_bytes(_lib.i(B), _lib.i(self.dim), _lib.i(self.mlp_dim))
+        need = _lib.value("gp_vit_workspace_bytes", B, self.dim, self.mlp_dim)
         if self._ws is None or self._ws.numel() * 4 < need or self._ws.device != device:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
         return self._ws, need
@@ -357,11 +357,8 @@ class Dinov2ViT(nn.Module):
         scales = None
         if self.plane_scales is not None and self.numerics == "split":
             scales = (ctypes.c_float * len(self.plane_scales))(*self.plane_scales)   # host array, read at launch time
-        _lib.call("gp_vit_forward_split2", _lib.ptr(x), _lib.i(B), _lib.i(self.dim), _lib.i(self.depth),
-                  _lib.i(self.heads), _lib.i(self.mlp_dim), _lib.f(1e-6), table, _lib.i(len(tensors)),
-                  split_table, _lib.i(len(split)), _lib.ptr(ws), ctypes.c_size_t(need), _lib.ptr(out),
-                  _lib.i(2 if matcher_planes else (1 if normalize else 0)), _lib.i(stop_after_layers), scales, _lib.ptr(plane_amax),
-                  _lib.stream_ptr())
+        _lib.call("gp_vit_forward_split2", x, B, self.dim, self.depth, self.heads, self.mlp_dim, 1e-6, table, len(tensors), split_table, len(split), ws, need,
+                  out, 2 if matcher_planes else (1 if normalize else 0), stop_after_layers, scales, plane_amax, _lib.stream_ptr())
         return out
 
     @torch.no_grad()

@@ -23,9 +23,9 @@ M = B * 257
 Mpad = (M + 255) // 256 * 256
 qkv = torch.randn(Mpad, 3 * C, device=dev)
 hi = torch.empty(Mpad, 3 * C, dtype=torch.float16, device=dev); lo = torch.empty_like(hi)
-_lib.call("gp_split_planes", _lib.ptr(qkv), ctypes.c_size_t(qkv.numel()), _lib.f(8.0), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+_lib.call("gp_split_planes", qkv, qkv.numel(), 8.0, hi, lo, _lib.stream_ptr())
 ohi = torch.zeros(Mpad, C, dtype=torch.float16, device=dev); olo = torch.zeros_like(ohi)
-run = lambda: _lib.call("gp_attention_split_scaled", _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(ohi), _lib.ptr(olo), _lib.i(B), _lib.i(H), _lib.i(C), _lib.i(Mpad), _lib.f(8.0), _lib.stream_ptr())
+run = lambda: _lib.call("gp_attention_split_scaled", hi, lo, ohi, olo, B, H, C, Mpad, 8.0, _lib.stream_ptr())
 ms = timeit(run)
 fl = 4.0 * B * H * 257 * 257 * 64
 print(f"attention_split_kernel B={B} H={H}: {ms*1e3:.1f} us isolated = {fl/ms/1e9:.1f} TF-equivalent (f32 kernel: 286 us in the bench)")

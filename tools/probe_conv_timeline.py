@@ -1,7 +1,6 @@
 """GPU probe: where conv_planes_kernel's time goes on the IST layer shapes at B = 64 -- per slot: tile prologue (gather
 state + first slab), k loop, tail (epilogue / hand-over), from the kernel's 100 MHz stamps (gp_conv2d_planes_set_trace);
 with and without a residual."""
-import ctypes
 import os
 import sys
 
@@ -38,9 +37,7 @@ def run(cin, cout, k, stride, pad, hw, B, res, tall):
     al, be = torch.ones(cout, device=dev), torch.zeros(cout, device=dev)
 
     def call():
-        _lib.call("gp_conv2d_planes", _lib.ptr(xh), _lib.ptr(xl), _lib.ptr(wh), _lib.ptr(wl), _lib.ptr(al), _lib.ptr(be), _lib.ptr(rh), _lib.ptr(rl),
-                  _lib.i(B), _lib.i(hw), _lib.i(hw), _lib.i(cin), _lib.i(cout), _lib.i(k), _lib.i(k), _lib.i(stride), _lib.i(pad), _lib.i(1),
-                  _lib.ptr(o1), _lib.ptr(o2), None, _lib.ptr(ws), ctypes.c_size_t(nb), _lib.stream_ptr())
+        _lib.call("gp_conv2d_planes", xh, xl, wh, wl, al, be, rh, rl, B, hw, hw, cin, cout, k, k, stride, pad, 1, o1, o2, None, ws, nb, _lib.stream_ptr())
 
     for _ in range(3):
         call()
@@ -52,11 +49,11 @@ def run(cin, cout, k, stride, pad, hw, B, res, tall):
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 5 * 1e3
-    lib.gp_conv2d_planes_set_trace(ctypes.c_void_p(trace.data_ptr()))
+    _lib.value("gp_conv2d_planes_set_trace", trace)
     trace.zero_()
     call()
     torch.cuda.synchronize()
-    lib.gp_conv2d_planes_set_trace(None)
+    _lib.value("gp_conv2d_planes_set_trace", None)
     t = trace.cpu().numpy().astype(np.float64)
     t = t[t[:, 0] > 0]
     seg, steps, pro, loop, tail, life = t[:, 0], t[:, 1], t[:, 2] / 100, t[:, 3] / 100, t[:, 4] / 100, (t[:, 6] - t[:, 5]) / 100

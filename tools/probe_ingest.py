@@ -44,19 +44,15 @@ def workload(seed=500, n_img=8, D=64, H=480, W=640):
 
 def dense_kernel(rgb, masks, boxes, im_id, out, err):
     n_img, _, H, W = rgb.shape
-    _lib.call("gp_preprocess_detections", _lib.ptr(rgb), _lib.ptr(masks), _lib.ptr(boxes), _lib.ptr(im_id), _lib.i(n_img),
-              _lib.i(masks.shape[0]), _lib.i(H), _lib.i(W), _lib.i(T), MEAN, STD, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
-              _lib.ptr(err), _lib.stream_ptr())
+    _lib.call("gp_preprocess_detections", rgb, masks, boxes, im_id, n_img, masks.shape[0], H, W, T, MEAN, STD, out[0], out[1], out[2], err, _lib.stream_ptr())
 
 
 def rle_kernels(rgb, counts, offsets, cum, boxes, im_id, out, err):
     n_img, _, H, W = rgb.shape
     D, total = offsets.numel() - 1, counts.numel()
-    ingest._call("gpi_rle_scan", _lib.ptr(counts), _lib.ptr(offsets), _lib.i(total), _lib.i(D), _lib.i(H), _lib.i(W), _lib.ptr(cum),
-                 _lib.ptr(err), _lib.stream_ptr())
-    ingest._call("gpi_preprocess_detections_rle", _lib.ptr(rgb), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(total), _lib.ptr(boxes),
-                 _lib.ptr(im_id), _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), MEAN, STD, _lib.ptr(out[0]), _lib.ptr(out[1]),
-                 _lib.ptr(out[2]), _lib.ptr(err), _lib.stream_ptr())
+    ingest._call("gpi_rle_scan", counts, offsets, total, D, H, W, cum, err, _lib.stream_ptr())
+    ingest._call("gpi_preprocess_detections_rle", rgb, cum, offsets, total, boxes, im_id, n_img, D, H, W, T, MEAN, STD, out[0], out[1], out[2], err,
+                 _lib.stream_ptr())
 
 
 def outputs(D):
@@ -157,8 +153,7 @@ def main():
     cum = torch.empty_like(c)
     t = measure({"dense": lambda: dense_kernel(rgb, masks, boxes, im, out_d, err),
                  "rle": lambda: rle_kernels(rgb, c, o, cum, boxes, im, out_r, err),
-                 "scan": lambda: ingest._call("gpi_rle_scan", _lib.ptr(c), _lib.ptr(o), _lib.i(c.numel()), _lib.i(D), _lib.i(H), _lib.i(W),
-                                              _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())}, args.reps, args.warmup)
+                 "scan": lambda: ingest._call("gpi_rle_scan", c, o, c.numel(), D, H, W, cum, err, _lib.stream_ptr())}, args.reps, args.warmup)
     say()
     say("2. kernels alone (inputs resident)")
     say(f"   dense kernel           : {stats(t['dense'])}")

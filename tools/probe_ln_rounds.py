@@ -2,14 +2,12 @@
 step at 64 crops has 16640 rows of which 16448 = 514 blocks carry tokens).  First column pairs: every row live (what the stage entry
 runs by itself); last lines: the forward's shape with its live-token count (probe library: gp_vit_set_ln_live) -- the six blocks of
 row padding do not run and the two blocks past the round ride on first-round blocks."""
-import ctypes
 
 import torch
 
 from gigapose_amd import _lib
 
 _lib.use_probe_library()
-lib = _lib.lib()
 dev = torch.device("cuda", 0)
 C = 1024
 g = torch.randn(C, device=dev)
@@ -22,10 +20,9 @@ def measure(Mpad, live):
     lo = torch.empty_like(hi)
 
     def run():
-        _lib.call("gp_layernorm_planes", _lib.ptr(X), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(g), _lib.ptr(b), _lib.i(C), _lib.i(Mpad),
-                  _lib.f(1e-6), _lib.stream_ptr())
+        _lib.call("gp_layernorm_planes", X, hi, lo, g, b, C, Mpad, 1e-6, _lib.stream_ptr())
 
-    lib.gp_vit_set_ln_live(ctypes.c_int(live))
+    _lib.value("gp_vit_set_ln_live", live)
     try:
         for _ in range(5):
             run()
@@ -39,7 +36,7 @@ def measure(Mpad, live):
             torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) / 40 * 1e3)
     finally:
-        lib.gp_vit_set_ln_live(ctypes.c_int(0))
+        _lib.value("gp_vit_set_ln_live", 0)
     return best
 
 

@@ -68,9 +68,8 @@ for C, make in ((32, setup), (1024, setup), (1024, setup_disc)):
     avg = torch.empty(B, N, device=dev)
     trace = torch.zeros(B * N, 8, dtype=torch.int64, device=dev)
     for _ in range(2):
-        _lib.call("gp_match_tiles_split_trace", _lib.ptr(q[0]), _lib.ptr(q[1]), _lib.ptr(bank.hi), _lib.ptr(bank.lo), _lib.ptr(qm),
-                  _lib.ptr(bank.masks), _lib.ptr(lab), _lib.i(B), _lib.i(1), _lib.i(N), _lib.i(C), _lib.f(0.5), _lib.f(3.0),
-                  _lib.ptr(idx), _lib.ptr(sc), _lib.ptr(ma), _lib.ptr(avg), _lib.ptr(trace), _lib.stream_ptr())
+        _lib.call("gp_match_tiles_split_trace", q[0], q[1], bank.hi, bank.lo, qm, bank.masks, lab, B, 1, N, C, 0.5, 3.0, idx, sc, ma, avg, trace,
+                  _lib.stream_ptr())
     torch.cuda.synchronize()
     tr = trace.cpu().numpy()
     st = tr[:, :7].astype(np.float64) / 100.0                       # us

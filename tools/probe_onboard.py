@@ -82,11 +82,10 @@ def main():
     say(f"workload: one object, {N} renders {H} x {W} RGBA u8 in pinned host memory ({in_bytes / 1e6:.1f} MB), target {T}")
 
     def alpha():
-        onboard._call("gpo_alpha_boxes", _lib.ptr(dev), _lib.i(N), _lib.i(H), _lib.i(W), _lib.ptr(boxes), _lib.ptr(err[0:1]), _lib.stream_ptr())
+        onboard._call("gpo_alpha_boxes", dev, N, H, W, boxes, err[0:1], _lib.stream_ptr())
 
     def crop():
-        onboard._call("gpo_crop_templates", _lib.ptr(dev), _lib.ptr(boxes), _lib.i(N), _lib.i(H), _lib.i(W), _lib.i(T), MEAN, STD,
-                      _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(err[1:2]), _lib.stream_ptr())
+        onboard._call("gpo_crop_templates", dev, boxes, N, H, W, T, MEAN, STD, out[0], out[1], out[2], err[1:2], _lib.stream_ptr())
 
     alpha()
     t = measure({"upload": lambda: host.to(DEV, non_blocking=True), "alpha": alpha, "crop": crop, "clone": lambda: dev.clone()},

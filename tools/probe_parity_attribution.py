@@ -16,7 +16,6 @@ reproduces the product's residual stream bit for bit (asserted) and a stage can 
 and, outside the ViT: the matcher and the IST network in chain numerics (f32 fmaf chains) next to a split ViT.
     python tools/probe_parity_attribution.py [variants ...]      (GPU box; ~1 min per variant)
 """
-import ctypes
 import os
 import sys
 import time
@@ -39,7 +38,7 @@ def planes_of(x, scale=8.0):
     x = x.float().contiguous()
     hi = torch.empty(x.shape, dtype=torch.float16, device=DEV)
     lo = torch.empty_like(hi)
-    _lib.call("gp_split_planes", _lib.ptr(x), ctypes.c_size_t(x.numel()), _lib.f(scale), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split_planes", x, x.numel(), scale, hi, lo, _lib.stream_ptr())
     return hi, lo
 
 
@@ -71,18 +70,15 @@ class HybridViT:
         if out_planes:
             ohi = torch.zeros(Mpad, I, dtype=torch.float16, device=DEV)
             olo = torch.zeros_like(ohi)
-        _lib.call("gp_gemm_planes256_scaled", _lib.ptr(wpl[0]), _lib.ptr(wpl[1]), _lib.ptr(bhi), _lib.ptr(blo), _lib.ptr(D), _lib.i(Mpad),
-                  _lib.ptr(ohi), _lib.ptr(olo), _lib.i(I), _lib.i(I), _lib.i(Mpad), _lib.i(Mtok), _lib.i(K), _lib.i(epi), _lib.ptr(bias),
-                  _lib.ptr(scale), _lib.ptr(D), _lib.i(Mpad if res is not None else 0), _lib.f(1.0 / 512.0), _lib.f(8.0), _lib.ptr(None), _lib.ptr(self.ws),
-                  ctypes.c_size_t(self.nb), _lib.stream_ptr())
+        _lib.call("gp_gemm_planes256_scaled", wpl[0], wpl[1], bhi, blo, D, Mpad, ohi, olo, I, I, Mpad, Mtok, K, epi, bias, scale, D,
+                  Mpad if res is not None else 0, 1.0 / 512.0, 8.0, None, self.ws, self.nb, _lib.stream_ptr())
         return (ohi, olo) if out_planes else D
 
     def ln(self, X, g, b, Mpad):
         C = X.shape[0]
         hi = torch.zeros(Mpad, C, dtype=torch.float16, device=DEV)
         lo = torch.zeros_like(hi)
-        _lib.call("gp_layernorm_planes", _lib.ptr(X), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(g), _lib.ptr(b), _lib.i(C), _lib.i(Mpad), _lib.f(1e-6),
-                  _lib.stream_ptr())
+        _lib.call("gp_layernorm_planes", X, hi, lo, g, b, C, Mpad, 1e-6, _lib.stream_ptr())
         return hi, lo
 
     @torch.no_grad()
@@ -124,8 +120,7 @@ class HybridViT:
                 o = planes_of(pad(attn64(val(*a)[:Mtok].view(B, T, 3, H, 64))))
             else:
                 o = (torch.zeros(Mpad, C, dtype=torch.float16, device=DEV), torch.zeros(Mpad, C, dtype=torch.float16, device=DEV))
-                _lib.call("gp_attention_split_scaled", _lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(o[0]), _lib.ptr(o[1]), _lib.i(B), _lib.i(H), _lib.i(C), _lib.i(Mpad),
-                          _lib.f(8.0), _lib.stream_ptr())
+                _lib.call("gp_attention_split_scaled", a[0], a[1], o[0], o[1], B, H, C, Mpad, 8.0, _lib.stream_ptr())
             # x += ls1 * proj(.)
             if ideal & {"proj", "gemms", "all"}:
                 X1 = X.clone()

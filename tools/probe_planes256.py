@@ -19,7 +19,7 @@ def timeit(fn, iters=8, warm=3):
     return e0.elapsed_time(e1) / iters
 def planes(W, scale):
     hi = torch.empty(W.shape, dtype=torch.float16, device=dev); lo = torch.empty_like(hi)
-    _lib.call("gp_split_planes", _lib.ptr(W), ctypes.c_size_t(W.numel()), _lib.f(scale), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split_planes", W, W.numel(), scale, hi, lo, _lib.stream_ptr())
     return hi, lo
 torch.manual_seed(0)
 M = 16640
@@ -39,17 +39,14 @@ for (nw, K, w_is_a, name, epi) in [(1024, 1024, 1, "proj", 3), (4096, 1024, 1, "
     ohi = torch.zeros(M, nw, dtype=torch.float16, device=dev); olo = torch.zeros_like(ohi)
     a_hi, a_lo, b_hi, b_lo = (whi, wlo, xhi, xlo) if w_is_a else (xhi, xlo, whi, wlo)
     def run_new():
-        _lib.call("gp_gemm_planes256_scaled", _lib.ptr(a_hi), _lib.ptr(a_lo), _lib.ptr(b_hi), _lib.ptr(b_lo), _lib.ptr(Dn), _lib.i(J),
-                  _lib.ptr(ohi), _lib.ptr(olo), _lib.i(nw), _lib.i(I), _lib.i(J), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc),
-                  _lib.ptr(Dn), _lib.i(J), _lib.f(1.0 / 512.0), _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(NB), _lib.stream_ptr())
+        _lib.call("gp_gemm_planes256_scaled", a_hi, a_lo, b_hi, b_lo, Dn, J, ohi, olo, nw, I, J, J, K, epi, bias, sc, Dn, J, 1.0 / 512.0, 8.0, None, ws, NB,
+                  _lib.stream_ptr())
     def run_old():
-        _lib.call("gp_gemm_split256", _lib.ptr(Xk), _lib.i(M), _lib.ptr(whi), _lib.ptr(wlo), _lib.ptr(Do), _lib.i(J), _lib.i(I), _lib.i(J),
-                  _lib.i(K), _lib.i(w_is_a), _lib.i(2 if epi == 6 else epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(Do), _lib.i(J), _lib.ptr(ws),
-                  ctypes.c_size_t(NB), _lib.stream_ptr())
+        _lib.call("gp_gemm_split256", Xk, M, whi, wlo, Do, J, I, J, K, w_is_a, 2 if epi == 6 else epi, bias, sc, Do, J, ws, NB, _lib.stream_ptr())
     run_new(); torch.cuda.synchronize()
-    err_n = lib.gp_gemm_split256_error(_lib.ptr(ws), _lib.stream_ptr())
+    err_n = _lib.value("gp_gemm_split256_error", ws, _lib.stream_ptr())
     run_old(); torch.cuda.synchronize()
-    err_o = lib.gp_gemm_split256_error(_lib.ptr(ws), _lib.stream_ptr())
+    err_o = _lib.value("gp_gemm_split256_error", ws, _lib.stream_ptr())
     if epi == 6:
         v = Do * 8.0
         h = v.half(); l = (v - h.float()).half()
@@ -79,11 +76,10 @@ I, J, K = 1024, M, 4096
 W = torch.randn(I, K, device=dev) * 0.03; Xt = torch.randn(J, K, device=dev)
 whi, wlo = planes(W, 64.0); xhi, xlo = planes(Xt, 8.0); D = torch.empty(I, J, device=dev)
 out = (ctypes.c_ulonglong * 8)()
-def timed(): lib.gp_gemm_planes256_timing(_lib.ptr(whi), _lib.ptr(wlo), _lib.ptr(xhi), _lib.ptr(xlo), _lib.ptr(D), J, I, J, K, _lib.ptr(ws), out, _lib.stream_ptr())
+def timed(): _lib.value("gp_gemm_planes256_timing", whi, wlo, xhi, xlo, D, J, I, J, K, ws, out, _lib.stream_ptr())
 def plain():
-    _lib.call("gp_gemm_planes256_scaled", _lib.ptr(whi), _lib.ptr(wlo), _lib.ptr(xhi), _lib.ptr(xlo), _lib.ptr(D), _lib.i(J), _lib.ptr(None), _lib.ptr(None),
-              _lib.i(0), _lib.i(I), _lib.i(J), _lib.i(J), _lib.i(K), _lib.i(0), _lib.ptr(None), _lib.ptr(None), _lib.ptr(None), _lib.i(0), _lib.f(1.0 / 512.0),
-              _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(NB), _lib.stream_ptr())
+    _lib.call("gp_gemm_planes256_scaled", whi, wlo, xhi, xlo, D, J, None, None, 0, I, J, J, K, 0, None, None, None, 0, 1.0 / 512.0, 8.0, None, ws, NB,
+              _lib.stream_ptr())
 for label, heat in (("cold (single launch)", 0), ("sustained (after 30 back-to-back launches)", 30)):
     torch.cuda.synchronize()
     for _ in range(heat): plain()

@@ -15,7 +15,7 @@ NB = lib.gp_gemm_split256_workspace_bytes()
 ws = torch.zeros(NB // 4, device=dev)
 def planes(W, scale):
     hi = torch.empty(W.shape, dtype=torch.float16, device=dev); lo = torch.empty_like(hi)
-    _lib.call("gp_split_planes", _lib.ptr(W), ctypes.c_size_t(W.numel()), _lib.f(scale), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split_planes", W, W.numel(), scale, hi, lo, _lib.stream_ptr())
     return hi, lo
 def timeit(fn, iters=10, warm=3):
     for _ in range(warm): fn()
@@ -50,10 +50,9 @@ for (nw, K, name, epi) in [(3072, 1024, "qkv", 7), (1024, 1024, "proj", 3), (409
     D = torch.randn(I, J, device=dev)
     ohi = torch.zeros(M, nw, dtype=torch.float16, device=dev); olo = torch.zeros_like(ohi)
     trace = torch.zeros(256 * 32, dtype=torch.int64, device=dev)
-    args = (_lib.ptr(whi), _lib.ptr(wlo), _lib.ptr(xhi), _lib.ptr(xlo), _lib.ptr(D), _lib.i(J), _lib.ptr(ohi), _lib.ptr(olo), _lib.i(nw),
-            _lib.i(I), _lib.i(J), _lib.i(MV), _lib.i(K), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(D), _lib.i(J), _lib.f(1.0 / 512.0), _lib.ptr(ws))
-    def plain(): _lib.call("gp_gemm_planes256_scaled", *args[:-1], _lib.f(8.0), _lib.ptr(None), args[-1], ctypes.c_size_t(NB), _lib.stream_ptr())
-    def traced(): _lib.call("gp_gemm_planes256_trace", *args, _lib.ptr(trace), _lib.stream_ptr())
+    args = (whi, wlo, xhi, xlo, D, J, ohi, olo, nw, I, J, MV, K, epi, bias, sc, D, J, 1.0 / 512.0, ws)
+    def plain(): _lib.call("gp_gemm_planes256_scaled", *args[:-1], 8.0, None, args[-1], NB, _lib.stream_ptr())
+    def traced(): _lib.call("gp_gemm_planes256_trace", *args, trace, _lib.stream_ptr())
     t_plain = timeit(plain)
     if os.environ.get("COLD"):
         t_one = timeit_cold(plain, 1) * 0 + sum(timeit(plain, 1, 0) for _ in range(10)) / 10   # one launch per event pair, caches warm

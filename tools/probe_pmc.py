@@ -11,8 +11,7 @@ for (I, K, epi) in [(1024, 1024, 3), (2048, 1024, 1), (4096, 1024, 2), (1024, 40
     A = torch.randn(K, I, device=dev); Bm = torch.randn(K, J, device=dev); D = torch.randn(I, J, device=dev)
     bias = torch.randn(I, device=dev); sc = torch.randn(I, device=dev)
     for _ in range(3):
-        _lib.call("gp_gemm_kmajor", _lib.ptr(A), _lib.i(I), _lib.ptr(Bm), _lib.i(J), _lib.ptr(D), _lib.i(J), _lib.i(I), _lib.i(J),
-                  _lib.i(K), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(D), _lib.i(J), _lib.stream_ptr())
+        _lib.call("gp_gemm_kmajor", A, I, Bm, J, D, J, I, J, K, epi, bias, sc, D, J, _lib.stream_ptr())
 B, N, C = 64, 162, 1024
 bank_np, q_np = syn.random_features(1, B, 1, N, C)
 metric = LocalSimilarity(5, 0.5, 3)

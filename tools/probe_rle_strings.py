@@ -29,22 +29,19 @@ from probe_ingest import DEV, MEAN, STD, T, measure, outputs, rle_kernels, stats
 
 
 def string_scan(data, byte_offsets, offsets, counts, cum, H, W, err):
-    rs._call("gps_rle_string_scan", _lib.ptr(data), _lib.ptr(byte_offsets), _lib.i(data.numel()), _lib.ptr(offsets), _lib.i(counts.numel()),
-             _lib.i(offsets.numel() - 1), _lib.i(H), _lib.i(W), _lib.ptr(counts), _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())
+    rs._call("gps_rle_string_scan", data, byte_offsets, data.numel(), offsets, counts.numel(), offsets.numel() - 1, H, W, counts, cum, err, _lib.stream_ptr())
 
 
 def list_scan(counts, offsets, cum, H, W, err):
-    ingest._call("gpi_rle_scan", _lib.ptr(counts), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.i(offsets.numel() - 1), _lib.i(H),
-                 _lib.i(W), _lib.ptr(cum), _lib.ptr(err), _lib.stream_ptr())
+    ingest._call("gpi_rle_scan", counts, offsets, counts.numel(), offsets.numel() - 1, H, W, cum, err, _lib.stream_ptr())
 
 
 def string_kernels(rgb, data, byte_offsets, counts, offsets, cum, boxes, im_id, out, err):
     n_img, _, H, W = rgb.shape
     D = offsets.numel() - 1
     string_scan(data, byte_offsets, offsets, counts, cum, H, W, err)
-    ingest._call("gpi_preprocess_detections_rle", _lib.ptr(rgb), _lib.ptr(cum), _lib.ptr(offsets), _lib.i(counts.numel()), _lib.ptr(boxes),
-                 _lib.ptr(im_id), _lib.i(n_img), _lib.i(D), _lib.i(H), _lib.i(W), _lib.i(T), MEAN, STD, _lib.ptr(out[0]), _lib.ptr(out[1]),
-                 _lib.ptr(out[2]), _lib.ptr(err), _lib.stream_ptr())
+    ingest._call("gpi_preprocess_detections_rle", rgb, cum, offsets, counts.numel(), boxes, im_id, n_img, D, H, W, T, MEAN, STD, out[0], out[1], out[2], err,
+                 _lib.stream_ptr())
 
 
 def main():

@@ -18,7 +18,7 @@ def timeit(fn, iters=8, warm=3):
 def split_w(Wt):  # Wt [K][n] f32 -> hi, lo [n][K] f16
     K, n = Wt.shape
     hi = torch.empty(n, K, dtype=torch.float16, device=dev); lo = torch.empty_like(hi)
-    _lib.call("gp_split_weights", _lib.ptr(Wt), _lib.i(K), _lib.i(n), _lib.i(n), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split_weights", Wt, K, n, n, hi, lo, _lib.stream_ptr())
     return hi, lo
 torch.manual_seed(0)
 # correctness on a small asymmetric case, both operand roles
@@ -32,12 +32,10 @@ for act_is_b in [1, 0]:
         ref = (X.double().T @ Wt.double())
     hi, lo = split_w(Wt)
     D = torch.empty(I, J, device=dev)
-    _lib.call("gp_gemm_split", _lib.ptr(X), _lib.i(X.shape[1]), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I), _lib.i(J),
-              _lib.i(K), _lib.i(act_is_b), _lib.i(0), None, None, None, _lib.i(J), _lib.stream_ptr())
+    _lib.call("gp_gemm_split", X, X.shape[1], hi, lo, D, J, I, J, K, act_is_b, 0, None, None, None, J, _lib.stream_ptr())
     A_, B_ = (Wt, X) if act_is_b else (X, Wt)
     De = torch.empty(I, J, device=dev)
-    _lib.call("gp_gemm_kmajor", _lib.ptr(A_), _lib.i(I), _lib.ptr(B_), _lib.i(J), _lib.ptr(De), _lib.i(J), _lib.i(I), _lib.i(J),
-              _lib.i(K), _lib.i(0), None, None, None, _lib.i(J), _lib.stream_ptr())
+    _lib.call("gp_gemm_kmajor", A_, I, B_, J, De, J, I, J, K, 0, None, None, None, J, _lib.stream_ptr())
     torch.cuda.synchronize()
     scale = (A_.double().abs().T @ B_.double().abs())
     es = ((D.double() - ref).abs() / scale).max().item(); ee = ((De.double() - ref).abs() / scale).max().item()
@@ -51,10 +49,8 @@ for (I, J, K, act_is_b, name) in [(1024, 16512, 1024, 1, "proj"), (4096, 16512, 
     hi, lo = split_w(Wt)
     A_, B_ = (Wt, X) if act_is_b else (X, Wt)
     D = torch.empty(I, J, device=dev); De = torch.empty(I, J, device=dev)
-    fs = lambda: _lib.call("gp_gemm_split", _lib.ptr(X), _lib.i(X.shape[1]), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I), _lib.i(J),
-                           _lib.i(K), _lib.i(act_is_b), _lib.i(0), None, None, None, _lib.i(J), _lib.stream_ptr())
-    fe = lambda: _lib.call("gp_gemm_kmajor", _lib.ptr(A_), _lib.i(I), _lib.ptr(B_), _lib.i(J), _lib.ptr(De), _lib.i(J), _lib.i(I), _lib.i(J),
-                           _lib.i(K), _lib.i(0), None, None, None, _lib.i(J), _lib.stream_ptr())
+    fs = lambda: _lib.call("gp_gemm_split", X, X.shape[1], hi, lo, D, J, I, J, K, act_is_b, 0, None, None, None, J, _lib.stream_ptr())
+    fe = lambda: _lib.call("gp_gemm_kmajor", A_, I, B_, J, De, J, I, J, K, 0, None, None, None, J, _lib.stream_ptr())
     ms_s, ms_e = timeit(fs), timeit(fe)
     rows = slice(0, 256)
     ref = (A_[:, rows].double().T @ B_.double())
@@ -69,7 +65,7 @@ Wt = torch.randn(K, I, device=dev) * 0.05; X = torch.randn(K, J, device=dev)
 hi, lo = split_w(Wt); D = torch.empty(I, J, device=dev)
 out = (ctypes.c_ulonglong * 23)()
 for rep in range(2):
-    lib.gp_gemm_split_timing(_lib.ptr(X), J, _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), J, I, J, K, out, _lib.stream_ptr())
+    _lib.value("gp_gemm_split_timing", X, J, hi, lo, D, J, I, J, K, out, _lib.stream_ptr())
 names = ["gload issue", "LDS read + MFMA issue", "MFMA drain", "convert + LDS write", "barrier"]
 for w in range(4):
     v = [out[w * 5 + p] for p in range(5)]
@@ -80,9 +76,9 @@ print(f"timed block: {out[20]} shader cycles in {out[21] * 10} ns -> {out[20] / 
 import numpy as np
 grid = 8 * ((32 * 129 + 7) // 8)
 trace = torch.zeros(grid * 3, dtype=torch.int64, device=dev)
-lib.gp_gemm_split_set_trace(ctypes.c_void_p(trace.data_ptr()))
-lib.gp_gemm_split_timing(_lib.ptr(X), J, _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), J, I, J, K, out, _lib.stream_ptr())
-lib.gp_gemm_split_set_trace(ctypes.c_void_p(0))
+_lib.value("gp_gemm_split_set_trace", trace)
+_lib.value("gp_gemm_split_timing", X, J, hi, lo, D, J, I, J, K, out, _lib.stream_ptr())
+_lib.value("gp_gemm_split_set_trace", None)
 t = trace.cpu().numpy().reshape(grid, 3)
 t = t[t[:, 1] > 0]
 start, end, hw = t[:, 0], t[:, 1], t[:, 2]

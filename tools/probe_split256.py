@@ -19,7 +19,7 @@ def timeit(fn, iters=8, warm=3):
     return e0.elapsed_time(e1) / iters
 def planes256(W):  # W [n][K] f32
     hi = torch.empty(W.shape, dtype=torch.float16, device=dev); lo = torch.empty_like(hi)
-    _lib.call("gp_split256_weights", _lib.ptr(W), ctypes.c_size_t(W.numel()), _lib.ptr(hi), _lib.ptr(lo), _lib.stream_ptr())
+    _lib.call("gp_split256_weights", W, W.numel(), hi, lo, _lib.stream_ptr())
     return hi, lo
 torch.manual_seed(0)
 M = 16640
@@ -31,11 +31,9 @@ for (I, J, K, act_is_b, name, epi) in [(1024, M, 1024, 1, "proj", 3), (4096, M, 
     bias = torch.randn(max(I, J), device=dev); sc = torch.randn(I, device=dev)
     D = torch.randn(I, J, device=dev); D0 = D.clone()
     def run():
-        _lib.call("gp_gemm_split256", _lib.ptr(X), _lib.i(na), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I), _lib.i(J),
-                  _lib.i(K), _lib.i(act_is_b), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(D), _lib.i(J), _lib.ptr(ws),
-                  ctypes.c_size_t(NB), _lib.stream_ptr())
+        _lib.call("gp_gemm_split256", X, na, hi, lo, D, J, I, J, K, act_is_b, epi, bias, sc, D, J, ws, NB, _lib.stream_ptr())
     D.copy_(D0); run(); torch.cuda.synchronize()
-    err = lib.gp_gemm_split256_error(_lib.ptr(ws), _lib.stream_ptr())
+    err = _lib.value("gp_gemm_split256_error", ws, _lib.stream_ptr())
     rows = slice(0, 128) if act_is_b else slice(0, 128)
     if act_is_b:
         ref = W[rows].double() @ X.double(); mag = W[rows].double().abs() @ X.double().abs()

@@ -11,16 +11,13 @@ W = torch.randn(I, K, device=dev) * 0.05; X = torch.randn(K, J, device=dev)
 hi, lo = split_planes(W)
 D = torch.empty(I, J, device=dev)
 for _ in range(3):
-    _lib.call("gp_gemm_split", _lib.ptr(X), _lib.i(J), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(D), _lib.i(J), _lib.i(I), _lib.i(J),
-              _lib.i(K), _lib.i(1), _lib.i(0), None, None, None, _lib.i(J), _lib.stream_ptr())
+    _lib.call("gp_gemm_split", X, J, hi, lo, D, J, I, J, K, 1, 0, None, None, None, J, _lib.stream_ptr())
 B, H, C = 32, 128, 128
 xh, xl = split_planes(torch.randn(B, H, H, C, device=dev))
 wh, wl = split_planes(torch.randn(128, 9 * C, device=dev) * 0.03)
 oh, ol = torch.empty(B, H, H, C, dtype=torch.float16, device=dev), torch.empty(B, H, H, C, dtype=torch.float16, device=dev)
 for _ in range(3):
-    _lib.call("gp_conv2d_nhwc_split", _lib.ptr(xh), _lib.ptr(xl), _lib.ptr(wh), _lib.ptr(wl), None, None, None, None, _lib.i(B),
-              _lib.i(H), _lib.i(H), _lib.i(C), _lib.i(C), _lib.i(3), _lib.i(3), _lib.i(1), _lib.i(1), _lib.i(1), _lib.ptr(oh), _lib.ptr(ol),
-              None, _lib.stream_ptr())
+    _lib.call("gp_conv2d_nhwc_split", xh, xl, wh, wl, None, None, None, None, B, H, H, C, C, 3, 3, 1, 1, 1, oh, ol, None, _lib.stream_ptr())
 Bq, N, Cf = 32, 64, 1024
 m = LocalSimilarity(5, 0.5, 3); m.numerics = "split"
 bank = MatchBank(torch.randn(1, N, Cf, 16, 16, device=dev), torch.ones(1, N, 224, 224, device=dev), "split")

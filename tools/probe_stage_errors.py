@@ -11,7 +11,6 @@ Errors are rms over the token rows, relative to the rms of the stage's float64 o
     python tools/probe_stage_errors.py [--batch 64] [--layer 12]
 """
 import argparse
-import ctypes
 import os
 import sys
 
@@ -66,16 +65,14 @@ def main():
         whi, wlo = split_planes_x64(W)
         D = res.clone() if res is not None else torch.zeros(1, device=DEV)
         ohi, olo = planes_empty(Mpad, I) if out_planes else (None, None)
-        _lib.call("gp_gemm_planes256_scaled", _lib.ptr(whi), _lib.ptr(wlo), _lib.ptr(bhi), _lib.ptr(blo), _lib.ptr(D if not out_planes else None),
-                  _lib.i(Mpad), _lib.ptr(ohi), _lib.ptr(olo), _lib.i(I), _lib.i(I), _lib.i(Mpad), _lib.i(Mtok), _lib.i(K), _lib.i(epi),
-                  _lib.ptr(bias), _lib.ptr(scale), _lib.ptr(D if res is not None else None), _lib.i(Mpad if res is not None else 0), _lib.f(os_),
-                  _lib.f(8.0), _lib.ptr(None), _lib.ptr(ws), ctypes.c_size_t(nb), st())
+        _lib.call("gp_gemm_planes256_scaled", whi, wlo, bhi, blo, D if not out_planes else None, Mpad, ohi, olo, I, I, Mpad, Mtok, K, epi, bias, scale,
+                  D if res is not None else None, Mpad if res is not None else 0, os_, 8.0, None, ws, nb, st())
         torch.cuda.synchronize()
         return (ohi, olo) if out_planes else D
 
     def ln(Xcm, g, b):
         hi, lo = planes_empty(Mpad, C)
-        _lib.call("gp_layernorm_planes", _lib.ptr(Xcm), _lib.ptr(hi), _lib.ptr(lo), _lib.ptr(g), _lib.ptr(b), _lib.i(C), _lib.i(Mpad), _lib.f(1e-6), st())
+        _lib.call("gp_layernorm_planes", Xcm, hi, lo, g, b, C, Mpad, 1e-6, st())
         torch.cuda.synchronize()
         return hi, lo
 
@@ -102,7 +99,7 @@ def main():
     # ---- attention
     qkv = val(ahi, alo)[:Mtok].view(B, 257, 3, vit.heads, 64)
     ohi, olo = planes_empty(Mpad, C)
-    _lib.call("gp_attention_split_scaled", _lib.ptr(ahi), _lib.ptr(alo), _lib.ptr(ohi), _lib.ptr(olo), _lib.i(B), _lib.i(vit.heads), _lib.i(C), _lib.i(Mpad), _lib.f(8.0), st())
+    _lib.call("gp_attention_split_scaled", ahi, alo, ohi, olo, B, vit.heads, C, Mpad, 8.0, st())
     torch.cuda.synchronize()
 
     def attn(x):

@@ -17,7 +17,6 @@ def timeit(fn, iters=5, warm=2):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters
 
-import ctypes
 lib = _lib.lib()
 nbytes = lib.gp_gemm_streamk_workspace_bytes()
 ws = torch.zeros(nbytes // 4, device=dev)
@@ -27,16 +26,13 @@ for mode in []:
         A = torch.randn(K, I, device=dev); Bm = torch.randn(K, J, device=dev); D = torch.randn(I, J, device=dev)
         bias = torch.randn(max(I, J), device=dev); sc = torch.randn(I, device=dev)
         if mode == "plain":
-            fn = lambda: _lib.call("gp_gemm_kmajor", _lib.ptr(A), _lib.i(I), _lib.ptr(Bm), _lib.i(J), _lib.ptr(D), _lib.i(J),
-                                   _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(D), _lib.i(J), _lib.stream_ptr())
+            fn = lambda: _lib.call("gp_gemm_kmajor", A, I, Bm, J, D, J, I, J, K, epi, bias, sc, D, J, _lib.stream_ptr())
         else:
-            fn = lambda: _lib.call("gp_gemm_kmajor_sk", _lib.ptr(A), _lib.i(I), _lib.ptr(Bm), _lib.i(J), _lib.ptr(D), _lib.i(J),
-                                   _lib.i(I), _lib.i(J), _lib.i(K), _lib.i(epi), _lib.ptr(bias), _lib.ptr(sc), _lib.ptr(D), _lib.i(J),
-                                   _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
+            fn = lambda: _lib.call("gp_gemm_kmajor_sk", A, I, Bm, J, D, J, I, J, K, epi, bias, sc, D, J, ws, nbytes, _lib.stream_ptr())
         ms = timeit(fn)
         tot += ms
         print(f"{mode} gemm I={I} J={J} K={K} epi={epi}: {ms:.3f} ms {2.0*I*J*K/ms/1e9:.1f} TF")
-    print(f"{mode} layer total {tot:.3f} ms -> {415.5/tot:.1f} TF  err={lib.gp_gemm_streamk_error(_lib.ptr(ws), _lib.stream_ptr())}")
+    print(f"{mode} layer total {tot:.3f} ms -> {415.5/tot:.1f} TF  err={_lib.value('gp_gemm_streamk_error', ws, _lib.stream_ptr())}")
 
 name = sys.argv[1] if len(sys.argv) > 1 else "dinov2_vitl14"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
