@@ -1,5 +1,5 @@
 """ctypes binding of libgigapose_hip.so (C-ABI: include/gigapose_hip.h), and SideLibrary: the loader of the front-end libraries
-(the fourteen of them: libgigapose_ingest / _rlestr / _onboard / _render / _texture / _eval / _dist / _refine / _verify / _maskfit / _shade / _gtinfo / _label / _coco.so; sixteen
+(the fifteen of them: libgigapose_ingest / _rlestr / _onboard / _render / _texture / _eval / _dist / _refine / _verify / _maskfit / _shade / _gtinfo / _label / _coco / _appear.so; seventeen
 libraries in all with the product library and its probe build), whose modules hold one instance each.
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module

@@ -1,4 +1,4 @@
-// Host-side plumbing of a front-end ("side") library -- libgigapose_ingest / _rlestr / _onboard / _render / _texture / _eval / _dist / _refine / _verify / _maskfit / _shade / _gtinfo / _label / _coco.so -- written once:
+// Host-side plumbing of a front-end ("side") library -- libgigapose_ingest / _rlestr / _onboard / _render / _texture / _eval / _dist / _refine / _verify / _maskfit / _shade / _gtinfo / _label / _coco / _appear.so -- written once:
 // the thread-local message buffer behind <prefix>_last_error, the three return codes and the argument / launch checks of an
 // entry point.  Header only: every library compiles its own copy into its own objects and links nothing of the others.
 //   #define GP_FRONT_PREFIX gpi
@@ -11,7 +11,7 @@
 #include <stdio.h>
 
 #ifndef GP_FRONT_PREFIX
-#error "define GP_FRONT_PREFIX (gpi, gps, gpo, gpr, gpt, gpe, gpd, gpf, gpv, gpm, gpl, gpg, gpa, gpc) before including gp_front.h"
+#error "define GP_FRONT_PREFIX (gpi, gps, gpo, gpr, gpt, gpe, gpd, gpf, gpv, gpm, gpl, gpg, gpa, gpc, gpp) before including gp_front.h"
 #endif
 
 #define GPF_OK 0

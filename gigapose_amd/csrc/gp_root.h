@@ -1,5 +1,5 @@
 // The correctly rounded float64 square root of the side libraries, written ONCE: distance/gpd_dist.hip (ADD / ADD-S distances)
-// shade/gpl_shade.hip (vertex normals, Lambert's cosine) and label/gpa_label.hip (LayerNorm, the descriptor's norm) include it.  include/gigapose_dist.h states the construction and why
+// shade/gpl_shade.hip (vertex normals, Lambert's cosine), label/gpa_label.hip and appear/gpp_appear.hip (LayerNorm, the descriptor's norm) include it.  include/gigapose_dist.h states the construction and why
 // it is exact: the compiler's root, its two neighbours, and two explicit fma() calls -- which stay fused under
 // -ffp-contract=off and are the one fused operation of each library.  numpy.sqrt returns the same bits.
 #pragma once

@@ -15,8 +15,9 @@ the labels do not depend on launch geometry; gigapose_testing/label_ref.py resta
   nms(box, label, num, den, per_label) boxes in suppression order -> keep                                gpa_nms_matrix + gpa_nms_keep
   DescriptorBank                       the descriptors of the onboarded objects' templates, (O, T, C)
   ProposalLabeller                     frames + proposals -> per image the list of CNOS dicts FrameIngest takes
-Out of scope: the segmenter, CNOS's appearance and visibility scores, objects with different template counts.  (A mask-IoU NMS
-is detections.mask_nms; ProposalLabeller(nms_on="mask") routes through it.)  There is no CPU fallback: the kernels need the GPU, a missing library is an error.
+The appearance score of CNOS's successors (patch-level similarity with the best template: appearance.py, libgigapose_appear.so) is
+averaged into the score when ProposalLabeller is given a PatchBank.  Out of scope: the segmenter, CNOS's visibility / geometric score,
+objects with different template counts.  (A mask-IoU NMS is detections.mask_nms; ProposalLabeller(nms_on="mask") routes through it.)  There is no CPU fallback: the kernels need the GPU, a missing library is an error.
 """
 import numpy as np
 import torch
@@ -286,12 +287,24 @@ class ProposalLabeller:
     per_label: only boxes of one label suppress each other.  max_dets: at most this many detections per image, best first.
     nms_on: "box" (the default) compares the boxes; "mask" compares the masks themselves (detections.mask_nms: the same threshold,
     the same greedy pass, the IoU of the run-length masks; at most 2048 proposals above min_score per image).
+    appearance: None (the default: the label rests on the class-token score alone, and libgigapose_appear.so is not loaded) or an
+    appearance.PatchBank made with the same vit, holding the same labels in the same order as `bank` (ValueError otherwise).  With
+    one, a proposal's crop is compared patch by patch with the best template of its label (bank row label * T + best_template): the
+    dicts gain `semantic_score` (the class-token score) and `appearance_score` (the mean over the crop's valid patches of the best
+    cosine among the template's valid patches), and `score` = (semantic + appearance) / 2 in float64 -- min_score, the NMS order
+    and max_dets go by it, ties to the lower proposal index.  A proposal whose crop has no valid patch is dropped and counted in
+    report["no_patch"].
 
     label(frames_u8, proposals) -> per image the list of CNOS dicts {bbox xywh, category_id, score, segmentation, best_template}
     (+ proposal: the index in the image's input list), best first; ingest.FrameIngest.__call__ takes them unchanged.  `report` counts what the last call dropped and why."""
 
-    def __init__(self, vit, bank, top_k=5, min_score=0.5, nms_iou=(1, 4), per_label=False, max_dets=None, device="cuda", nms_on="box"):
+    def __init__(self, vit, bank, top_k=5, min_score=0.5, nms_iou=(1, 4), per_label=False, max_dets=None, device="cuda", nms_on="box",
+                 appearance=None):
         self.vit, self.bank = vit, bank
+        if appearance is not None and list(appearance.labels) != list(bank.labels):
+            raise ValueError(f"ProposalLabeller: the PatchBank holds the objects {list(appearance.labels)}, the DescriptorBank {list(bank.labels)} "
+                             "(the same labels in the same order)")
+        self.appearance = appearance
         self.top_k, self.min_score = int(top_k), float(min_score)
         if not 1 <= self.top_k <= MAX_K:
             raise ValueError(f"ProposalLabeller: top_k = {top_k} (1 to {MAX_K})")
@@ -328,7 +341,8 @@ class ProposalLabeller:
     @torch.no_grad()
     def describe(self, frames_u8, proposals):
         """The device half up to the scores -> dict of host arrays (box int64 (P,4) xyxy, mstatus, dstatus, label, score,
-        best_template, image) + "segs" + the device tensors "crops" and "q"."""
+        best_template, image) + "segs" + the device tensors "crops" and "q".  With a PatchBank also: the device tensors "tar_mask", "a" (limbs), "pstatus",
+        "pvalid", "pcount", "pair_t" (the bank row of each proposal) and the host arrays "app_sum", "app_n", "app_status" (gpp_appearance's)."""
         if isinstance(frames_u8, np.ndarray):
             frames_u8 = torch.from_numpy(frames_u8)
         if not (isinstance(frames_u8, torch.Tensor) and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[1] == 3):
@@ -347,13 +361,34 @@ class ProposalLabeller:
         box[given] = given_xyxy[given]                                  # a proposal's own box stands
         crop_box = box.copy()
         crop_box[mstatus != 0] = (0, 0, 1, 1)                           # an empty mask is dropped below: any box inside the frame does
-        crops = self.preprocess(frames, counts_d, offsets_d, crop_box, im_id)["tar_img"]
-        q, dstatus = self.vit.cls_descriptors(crops)
+        if self.appearance is None:
+            crops = self.preprocess(frames, counts_d, offsets_d, crop_box, im_id)["tar_img"]
+            q, dstatus = self.vit.cls_descriptors(crops)
+        else:
+            pre = self.preprocess(frames, counts_d, offsets_d, crop_box, im_id)
+            crops = pre["tar_img"]
+            patch = self.vit.cls_and_patch_descriptors(crops, pre["tar_mask"], occupancy=self.appearance.occupancy)
+            q, dstatus = patch["q"], patch["status"]
         sc = scores(q, self.bank.q, self.top_k) if P else dict(label=torch.zeros(0, dtype=torch.int32), score=torch.zeros(0, dtype=torch.int64),
                                                                best_template=torch.zeros(0, dtype=torch.int32), kk=min(self.top_k, self.bank.q.shape[1]))
         host = {k: sc[k].cpu().numpy() for k in ("label", "score", "best_template")}
-        return dict(host, kk=sc["kk"], box=box, mstatus=mstatus, dstatus=dstatus.cpu().numpy(), image=im_id, segs=segs, crops=crops, q=q,
-                    score_dev=sc["score"], n_img=n_img, local=local, lists=lists, HW=H * W)
+        out = dict(host, kk=sc["kk"], box=box, mstatus=mstatus, dstatus=dstatus.cpu().numpy(), image=im_id, segs=segs, crops=crops, q=q,
+                   score_dev=sc["score"], n_img=n_img, local=local, lists=lists, HW=H * W)
+        if self.appearance is not None:
+            from . import appearance as app
+
+            T = self.bank.q.shape[1]
+            if P and (self.appearance.templates != T or self.appearance.a.shape[3] != q.shape[1]):
+                raise ValueError(f"ProposalLabeller: the PatchBank has {self.appearance.templates} templates of {self.appearance.a.shape[3]} channels, "
+                                 f"the DescriptorBank {T} of {q.shape[1]}")
+            pair_t = (sc["label"].to(dev) * T + sc["best_template"].to(dev)).to(torch.int32)
+            if P:
+                res = app.appearance(patch["a"], patch["valid"], self.appearance.a, self.appearance.valid, torch.arange(P, dtype=torch.int32, device=dev), pair_t)
+            else:
+                res = dict(sum=torch.zeros(0, dtype=torch.int64), n=torch.zeros(0, dtype=torch.int32), status=torch.zeros(0, dtype=torch.int32))
+            out.update(tar_mask=pre["tar_mask"], a=patch["a"], pstatus=patch["pstatus"], pvalid=patch["valid"], pcount=patch["count"], pair_t=pair_t,
+                       app_sum=res["sum"].cpu().numpy(), app_n=res["n"].cpu().numpy(), app_status=res["status"].cpu().numpy())
+        return out
 
     @torch.no_grad()
     def label(self, frames_u8, proposals):
@@ -362,8 +397,18 @@ class ProposalLabeller:
         fscore = s["score"].astype(np.float64) / np.float64(s["kk"] * (1 << (2 * Q_BITS)))
         report = dict(proposals=P, empty_mask=0, flagged_descriptor=0, low_score=0, suppressed=0, over_max_dets=0, kept=0)
         empty, flagged = s["mstatus"] != 0, (s["mstatus"] == 0) & (s["dstatus"] != 0)
+        semantic, order_key = fscore, None
+        if self.appearance is not None:
+            from . import appearance as app
+
+            no_patch = ~empty & ~flagged & ((s["app_status"] & app.NO_QUERY_PATCH) != 0)
+            appear = app.float_appearance(s["app_sum"], s["app_n"])
+            fscore = (semantic + appear) / np.float64(2.0)                # the halving is exact
+            report["no_patch"] = int(no_patch.sum())
+            flagged = flagged | no_patch                                 # dropped alike; counted apart
+            order_key = torch.from_numpy(fscore).to(dev) if P else None
         low = ~empty & ~flagged & (fscore < self.min_score)
-        report.update(empty_mask=int(empty.sum()), flagged_descriptor=int(flagged.sum()), low_score=int(low.sum()))
+        report.update(empty_mask=int(empty.sum()), flagged_descriptor=int(flagged.sum()) - report.get("no_patch", 0), low_score=int(low.sum()))
         alive = ~(empty | flagged | low)
         box32 = torch.from_numpy(s["box"].clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32)).to(dev) if P else None
         label32 = torch.from_numpy(s["label"]).to(dev) if P else None
@@ -379,7 +424,8 @@ class ProposalLabeller:
             dets = []
             if len(idx):
                 idx_d = torch.from_numpy(idx).to(dev)
-                order = torch.sort(s["score_dev"][idx_d], descending=True, stable=True).indices      # ties: the lower proposal index first
+                key = s["score_dev"] if order_key is None else order_key
+                order = torch.sort(key[idx_d], descending=True, stable=True).indices      # ties: the lower proposal index first
                 idx_d = idx_d[order]
                 if self.nms_on == "mask":
                     keep = detections.mask_nms(fg, idx_d, *self.nms_iou, label=label32 if self.per_label else None)
@@ -394,6 +440,8 @@ class ProposalLabeller:
                     x0, y0, x1, y1 = (int(v) for v in s["box"][p])
                     dets.append(dict(bbox=[x0, y0, x1 - x0, y1 - y0], category_id=self.bank.labels[int(s["label"][p])], score=float(fscore[p]),
                                      segmentation=s["segs"][p], best_template=int(s["best_template"][p]), proposal=s["local"][p]))
+                    if self.appearance is not None:
+                        dets[-1].update(semantic_score=float(semantic[p]), appearance_score=float(appear[p]))
             report["kept"] += len(dets)
             out.append(dets)
         self.report = report

@@ -385,6 +385,33 @@ class Dinov2ViT(nn.Module):
         return q, status
 
     @torch.no_grad()
+    def cls_and_patch_descriptors(self, images, masks, chunk=64, occupancy=(1, 2)):
+        """images (B,3,224,224) f32, masks (B,224,224) f32 -> dict(q int32 (B, C), status int32 (B): what cls_descriptors returns; a int8
+        (3, B, 256, C), pstatus int32 (B, 256): the 256 patch tokens after the same LayerNorm, L2-normalised, quantised and split into
+        limbs; valid u8 (B, 256), count int32 (B): the patches with more than occupancy = num / den of their pixels on the mask) --
+        libgigapose_appear.so's crop description (include/gigapose_appear.h; gigapose_amd/appearance.py).  ONE forward per chunk
+        serves both libraries: gpa_descriptors and gpp_patch_descriptors read the same workspace."""
+        from . import appearance, proposals
+
+        if not 1 <= int(chunk) <= 64:
+            raise ValueError(f"cls_and_patch_descriptors: chunk = {chunk} (1 to 64)")
+        B, C, dev = images.shape[0], self.dim, images.device
+        if not (isinstance(masks, torch.Tensor) and tuple(masks.shape) == (B, 224, 224)):
+            raise ValueError(f"cls_and_patch_descriptors: expected masks ({B}, 224, 224), got {tuple(getattr(masks, 'shape', ()))}")
+        gamma = self.norm.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        beta = self.norm.bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = dict(q=torch.empty(B, C, dtype=torch.int32, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev),
+                   a=torch.empty(3, B, 256, C, dtype=torch.int8, device=dev), pstatus=torch.empty(B, 256, dtype=torch.int32, device=dev))
+        for a in range(0, B, int(chunk)):
+            n = min(B, a + int(chunk)) - a
+            self.patch_features(images[a:a + n], normalize=False)
+            mpad = (n * T + 255) // 256 * 256
+            out["q"][a:a + n], out["status"][a:a + n] = proposals.descriptors(self._ws, T, mpad, gamma, beta, self.norm.eps, n, C)
+            out["a"][:, a:a + n], out["pstatus"][a:a + n] = appearance.patch_descriptors(self._ws, T, 1, mpad, gamma, beta, self.norm.eps, n, C, offset=1)
+        out["valid"], out["count"] = appearance.patch_valid(masks.to(device=dev, dtype=torch.float32).contiguous(), *occupancy)
+        return out
+
+    @torch.no_grad()
     def forward_features(self, images):
         """hub-API compatibility: {"x_prenorm": (B, 257, C)} (token-major view of the workspace)."""
         B = images.shape[0]
