@@ -15,8 +15,8 @@
 //     (a 512 x 128 tile with the waves as 8 x 1 -- the plane GEMM's 48 matrix instructions per wave and k-step for
 //     Cout = 128, all 160 KiB of LDS -- was built and measured: bit-identical, no faster: 2.76 us per k-step against 2 x
 //     1.33, the loop is bound by the global -> LDS staging rate per CU, not by LDS reads; DESIGN.md, negative results)
-//   * work distribution of gp_tile256.h's GpSlotPlan: data-parallel rounds of whole tiles per XCD chunk, a stream-K remainder
-//     with deterministic accumulator hand-overs when the tile count does not fill the slots evenly (layer4 at B = 64:
+//   * launch plans of gp_plan256.h (gp_conv256_plan / gp_stem256_plan on the host, GpSlotPlan in the kernels; plain C++ that the
+//     CPU tests run too): data-parallel rounds of whole tiles per XCD chunk, a stream-K remainder with deterministic accumulator hand-overs when the tile count does not fill the slots evenly (layer4 at B = 64:
 //     128 tiles on 256 slots -> every tile is cut in two k halves);
 //   * epilogue through LDS (per wave, 32 pixel rows at a time): eval-BatchNorm alpha / beta, residual (planes), ReLU,
 //     output planes (npix, Cout) with 8 contiguous bytes per lane and 256-byte row segments per 32 lanes -- or f32 NCHW for
@@ -169,8 +169,8 @@ __global__ __launch_bounds__(CNT, 2) void conv_planes_kernel(const ConvPArgs a)
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
     constexpr int JT = 64 * NI;  // output channels per tile
 
-    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h)
-    const GpSlotPlan plan(a.tiles_i * a.tiles_j, a.K / CBK, true, 0);
+    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_plan256.h)
+    const GpSlotPlan plan(blockIdx.x, gridDim.x, a.tiles_i * a.tiles_j, a.K / CBK, true, 0);
     const int p = plan.p, n_seg = plan.n_seg;
 
     const unsigned x_bytes = (unsigned)a.B * a.H * a.W * a.Cin * 2u, w_bytes = (unsigned)a.Cout * a.K * 2u;
@@ -360,11 +360,11 @@ __global__ __launch_bounds__(CNT, 2) void conv_halo_kernel(const ConvPArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
 
-    // ---- this slot's segments: (tile, channel-block) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h); PAR: at most
+    // ---- this slot's segments: (tile, channel-block) ranges inside its XCD's tile chunk (GpSlotPlan, gp_plan256.h); PAR: at most
     // par_cap slots per tile (the host's cap: channel blocks per slot) and no more than the tile has channel blocks
     const int T = a.tiles_i * a.tiles_j, ncb = a.Cin / CBK;
-    const int par_S = PAR ? min(min(max(1, (int)(gridDim.x >> 3) / max(GpSlotPlan::chunk_tiles(T), 1)), ncb), max(1, a.par_cap)) : 0;
-    const GpSlotPlan plan(T, ncb, !PAR, par_S);
+    const int par_S = PAR ? gp_halo_par_slots(a.par_cap, (int)(gridDim.x >> 3), GpSlotPlan::chunk_tiles(T, blockIdx.x & 7), ncb) : 0;
+    const GpSlotPlan plan(blockIdx.x, gridDim.x, T, ncb, !PAR, par_S);
     const int p = plan.p, x = plan.x, n = plan.n, n_seg = plan.n_seg;
 
     const unsigned x_bytes = (unsigned)a.B * a.H * a.W * a.Cin * 2u, w_bytes = (unsigned)a.Cout * a.K * 2u;
@@ -604,6 +604,35 @@ __global__ __launch_bounds__(256) void resize_stem_planes_kernel(const float* __
 
 unsigned g_epoch_conv = 0;
 unsigned long long* g_conv_trace = nullptr;
+GpPlanHooks g_hooks;  // the convolutions read conv_halo, conv_par, conv_par_min_cb (set by gp_conv2d_planes_set_halo, probe builds)
+
+// The tail of the three launchers: the plan (gp_conv256_plan / gp_stem256_plan: gp_plan256.h) into the arguments, this launch's epoch,
+// the plan's kernel on 8 slots_x slots.  The halo kernel (3 x 3 / stride 1 / pad 1 on 16 x 16 pixel blocks with the halo resident in
+// LDS) takes the same arguments and gives the same results (to f32 round-off) as the gather kernel.
+template <int NI>
+void (*conv_kernel_of(const GpConvPlan& plan))(const ConvPArgs)
+{
+    if (plan.kernel != GP_CONV_HALO) return conv_planes_kernel<NI>;
+    return plan.par ? conv_halo_kernel<NI, true> : conv_halo_kernel<NI, false>;
+}
+int conv_launch(ConvPArgs& a, const GpConvPlan& plan, float* scratch, double work, const char* name, hipStream_t st)
+{
+    a.tiles_i = plan.tiles_i;
+    a.tiles_j = plan.tiles_j;
+    a.par_cap = plan.par_cap;
+    // no per-launch reset of the hand-off flags: a flag is valid only when it holds THIS launch's epoch (below); the
+    // scratch must start zeroed once (the caller allocates it with zeros)
+    a.flags = reinterpret_cast<int*>(scratch);
+    a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes);
+    g_epoch_conv = (g_epoch_conv + 1) & 0x3fffffff;
+    a.epoch = (int)(0x20000000u | g_epoch_conv);
+    a.status = gp_status_buffer();
+    GpProfScope prof(GP_PROF_CONV, work, st);
+    const auto kernel = plan.ni == 2 ? conv_kernel_of<2>(plan) : plan.ni == 3 ? conv_kernel_of<3>(plan) : conv_kernel_of<4>(plan);
+    hipLaunchKernelGGL(kernel, dim3(8 * plan.slots_x), dim3(CNT), 0, st, a);
+    GP_CHECK_LAUNCH(name);
+    return GP_OK;
+}
 
 }  // namespace
 
@@ -624,56 +653,15 @@ int gp_planes_from_cm(const float* X, int C, int npix, void* hi, void* lo, void*
     return GP_OK;
 }
 
-static int g_conv_halo = 1;  // bit 0: 3 x 3 / stride 1 layers take the halo kernel; bit 1 (with it): its parallel split below 256 tiles (A/B hook)
-static int g_conv_par = 1;
-static int g_conv_par_min_cb = 1;  // channel blocks (9 k-steps each) per slot of a split tile at least
 #ifdef GP_PROBES
-int gp_conv2d_planes_set_halo(int on)
+int gp_conv2d_planes_set_halo(int on)  // bit 0: 3 x 3 / stride 1 layers take the halo kernel; bit 1 (with it): its parallel split below 256 tiles (A/B hook)
 {
-    g_conv_halo = (on & 1) ? 1 : 0;
-    g_conv_par = ((on & 15) == 1 || (on & 2)) ? 1 : 0;   // 1 = both (default), 0 = neither, 5 = halo without the parallel split
-    g_conv_par_min_cb = (on >> 4) > 0 ? (on >> 4) : 1;   // probe: on = 1 + 16 n -> at least n channel blocks per slot of a split tile
+    g_hooks.conv_halo = (on & 1) ? 1 : 0;
+    g_hooks.conv_par = ((on & 15) == 1 || (on & 2)) ? 1 : 0;   // 1 = both (default), 0 = neither, 5 = halo without the parallel split
+    g_hooks.conv_par_min_cb = (on >> 4) > 0 ? (on >> 4) : 1;   // probe: on = 1 + 16 n -> at least n channel blocks per slot of a split tile
     return GP_OK;
 }
 #endif
-
-// 3 x 3 / stride 1 / pad 1 on 16 x 16 pixel blocks with the halo resident in LDS (conv_halo_kernel); same arguments and results
-// (to f32 round-off) as gp_conv2d_planes.  Needs H, W multiples of 16.
-static bool conv_halo_usable(int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad)
-{
-    return g_conv_halo && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H % 16 == 0 && W % 16 == 0 && Cin % 32 == 0 && Cout % 64 == 0;
-}
-
-static int conv_halo_launch(ConvPArgs& a, float* scratch, hipStream_t st)
-{
-    const int ni = a.Cout >= 256 ? 4 : a.Cout / 64;
-    a.tiles_i = a.B * (a.OH / 16) * (a.OW / 16);
-    a.tiles_j = (a.Cout + 64 * ni - 1) / (64 * ni);
-    const int ncb = a.Cin / CBK;
-    const long long n_tiles = (long long)a.tiles_i * a.tiles_j, units = n_tiles * ncb * 9;
-    int slots_x = 32;
-    const bool par = g_conv_par && n_tiles < 8 * slots_x && n_tiles >= 8 && ncb >= 2;  // fewer tiles than slots: parallel split over channel blocks
-    a.par_cap = max(1, ncb / g_conv_par_min_cb);
-    while (!par && slots_x > 1 && n_tiles < 8 * slots_x && units / (8 * slots_x) < 32) slots_x >>= 1;
-    a.flags = reinterpret_cast<int*>(scratch);
-    a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes);
-    g_epoch_conv = (g_epoch_conv + 1) & 0x3fffffff;
-    a.epoch = (int)(0x20000000u | g_epoch_conv);
-    a.status = gp_status_buffer();
-    const long long npix = (long long)a.B * a.OH * a.OW;
-    GpProfScope prof(GP_PROF_CONV, 2.0 * a.Cout * (double)npix * a.K, st);
-    if (par) {
-        if (ni == 2) hipLaunchKernelGGL((conv_halo_kernel<2, true>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-        else if (ni == 3) hipLaunchKernelGGL((conv_halo_kernel<3, true>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-        else hipLaunchKernelGGL((conv_halo_kernel<4, true>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-    } else {
-        if (ni == 2) hipLaunchKernelGGL((conv_halo_kernel<2, false>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-        else if (ni == 3) hipLaunchKernelGGL((conv_halo_kernel<3, false>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-        else hipLaunchKernelGGL((conv_halo_kernel<4, false>), dim3(8 * slots_x), dim3(CNT), 0, st, a);
-    }
-    GP_CHECK_LAUNCH("gp_conv2d_planes/halo");
-    return GP_OK;
-}
 
 int gp_conv2d_planes(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* alpha, const float* beta,
                      const void* res_hi, const void* res_lo, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
@@ -690,8 +678,9 @@ int gp_conv2d_planes(const void* x_hi, const void* x_lo, const void* w_hi, const
     a.OW = (W + 2 * pad - KW) / stride + 1;
     a.K = KH * KW * Cin;
     const long long npix = (long long)B * a.OH * a.OW;
-    GP_REQUIRE(Cin % 32 == 0 && Cout % 64 == 0 && KH * KW <= 9, "gp_conv2d_planes: Cin=%d must be a multiple of 32, Cout=%d of 64, at most 9 taps", Cin, Cout);
-    GP_REQUIRE(npix % CT == 0 && (long long)B * H * W * Cin * 2 < (1ll << 31) && (long long)Cout * a.K * 2 < (1ll << 31) && npix * Cout < (1ll << 31),
+    const GpConvPlan plan = gp_conv256_plan(g_hooks, B, H, W, Cin, Cout, KH, KW, stride, pad);
+    GP_REQUIRE(plan.refused != GP_CONV_BAD_CHANNELS, "gp_conv2d_planes: Cin=%d must be a multiple of 32, Cout=%d of 64, at most 9 taps", Cin, Cout);
+    GP_REQUIRE(plan.refused != GP_CONV_BAD_PIXELS && (long long)B * H * W * Cin * 2 < (1ll << 31) && (long long)Cout * a.K * 2 < (1ll << 31) && npix * Cout < (1ll << 31),
                "gp_conv2d_planes: B*OH*OW=%lld must be a multiple of 256 and every plane below 2 GiB", npix);
     GP_REQUIRE(x_hi && x_lo && w_hi && w_lo && ((out_hi && out_lo) || out_f32_nchw), "gp_conv2d_planes: null pointer");
     GP_REQUIRE((alpha == nullptr) == (beta == nullptr) && (res_hi == nullptr) == (res_lo == nullptr), "gp_conv2d_planes: alpha/beta and res_hi/res_lo go together");
@@ -699,31 +688,9 @@ int gp_conv2d_planes(const void* x_hi, const void* x_lo, const void* w_hi, const
     GP_REQUIRE(((uintptr_t)x_hi % 16 == 0) && ((uintptr_t)x_lo % 16 == 0) && ((uintptr_t)w_hi % 16 == 0) && ((uintptr_t)w_lo % 16 == 0) &&
                    ((uintptr_t)alpha % 16 == 0) && ((uintptr_t)beta % 16 == 0), "gp_conv2d_planes: misaligned operand");
     a.stem = 0;
-    a.par_cap = 1;
     a.trace = g_conv_trace;
-    if (conv_halo_usable(H, W, Cin, Cout, KH, KW, stride, pad)) return conv_halo_launch(a, scratch, (hipStream_t)stream);
-    const int ni = Cout >= 256 ? 4 : Cout / 64;  // 128 -> 2, 192 -> 3, >= 256 -> 4
-    a.tiles_i = (int)(npix / CT);
-    a.tiles_j = (Cout + 64 * ni - 1) / (64 * ni);
-    hipStream_t st = (hipStream_t)stream;
-    // slots: all 256 CUs unless there are fewer tiles than slots AND so little work that cutting tiles would leave a slot with
-    // under 32 k-steps per hand-over (the 1 x 1 head: 64 tiles x 16 steps -> 32 slots of two whole tiles)
-    const long long n_tiles = (long long)a.tiles_i * a.tiles_j, units = n_tiles * (a.K / CBK);
-    int slots_x = 32;
-    while (slots_x > 1 && n_tiles < 8 * slots_x && units / (8 * slots_x) < 32) slots_x >>= 1;
-    // no per-launch reset of the hand-off flags: a flag is valid only when it holds THIS launch's epoch (below); the
-    // scratch must start zeroed once (the caller allocates it with zeros)
-    a.flags = reinterpret_cast<int*>(scratch);
-    a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes);
-    g_epoch_conv = (g_epoch_conv + 1) & 0x3fffffff;
-    a.epoch = (int)(0x20000000u | g_epoch_conv);
-    a.status = gp_status_buffer();
-    GpProfScope prof(GP_PROF_CONV, 2.0 * Cout * (double)npix * a.K, st);
-    if (ni == 2) hipLaunchKernelGGL(conv_planes_kernel<2>, dim3(8 * slots_x), dim3(CNT), 0, st, a);
-    else if (ni == 3) hipLaunchKernelGGL(conv_planes_kernel<3>, dim3(8 * slots_x), dim3(CNT), 0, st, a);
-    else hipLaunchKernelGGL(conv_planes_kernel<4>, dim3(8 * slots_x), dim3(CNT), 0, st, a);
-    GP_CHECK_LAUNCH("gp_conv2d_planes");
-    return GP_OK;
+    return conv_launch(a, plan, scratch, 2.0 * Cout * (double)npix * a.K, plan.kernel == GP_CONV_HALO ? "gp_conv2d_planes/halo" : "gp_conv2d_planes",
+                       (hipStream_t)stream);
 }
 
 /* The stem of the IST ResNet (reference resnet.py:333-337, 366-370: bilinear resize to S x S, Conv2d(3 -> Cout, 7 x 7, stride 2,
@@ -748,33 +715,19 @@ int gp_conv2d_stem_planes(const void* x_hi, const void* x_lo, const void* w_hi, 
 {
     GP_REQUIRE(B >= 0 && S > 0 && S % 2 == 0 && (Cout == 128 || Cout == 192 || Cout % 256 == 0), "gp_conv2d_stem_planes: bad sizes");
     if (B == 0) return GP_OK;
+    const GpConvPlan plan = gp_stem256_plan(B, S, Cout);
+    GP_REQUIRE(plan.refused != GP_CONV_BAD_SIZES, "gp_conv2d_stem_planes: bad sizes");  // (Cout <= 0)
     ConvPArgs a;
     a.xhi = (const _Float16*)x_hi; a.xlo = (const _Float16*)x_lo; a.whi = (const _Float16*)w_hi; a.wlo = (const _Float16*)w_lo;
     a.alpha = alpha; a.beta = beta; a.rhi = nullptr; a.rlo = nullptr; a.ohi = (_Float16*)out_hi; a.olo = (_Float16*)out_lo; a.of32 = nullptr;
     a.B = B; a.H = S + 6; a.W = S + 8; a.Cin = 4; a.OH = S / 2; a.OW = S / 2; a.Cout = Cout; a.KH = 7; a.KW = 8; a.stride = 2; a.pad = 0;
-    a.relu = relu; a.K = 7 * 32; a.stem = 1; a.par_cap = 1;
+    a.relu = relu; a.K = 7 * 32; a.stem = 1;
     a.trace = g_conv_trace;
     const long long npix = (long long)B * a.OH * a.OW;
-    GP_REQUIRE(npix % CT == 0 && (long long)B * a.H * a.W * 8 < (1ll << 31) && npix * Cout < (1ll << 31), "gp_conv2d_stem_planes: B*OH*OW=%lld must be a multiple of 256", npix);
+    GP_REQUIRE(plan.refused != GP_CONV_BAD_PIXELS && (long long)B * a.H * a.W * 8 < (1ll << 31) && npix * Cout < (1ll << 31), "gp_conv2d_stem_planes: B*OH*OW=%lld must be a multiple of 256", npix);
     GP_REQUIRE(x_hi && x_lo && w_hi && w_lo && out_hi && out_lo && (alpha == nullptr) == (beta == nullptr), "gp_conv2d_stem_planes: null pointer");
     GP_REQUIRE(scratch && scratch_bytes >= gp_conv2d_planes_workspace_bytes() && ((uintptr_t)scratch % 16 == 0), "gp_conv2d_stem_planes: scratch too small");
-    const int ni = Cout >= 256 ? 4 : Cout / 64;
-    a.tiles_i = (int)(npix / CT);
-    a.tiles_j = (Cout + 64 * ni - 1) / (64 * ni);
-    hipStream_t st = (hipStream_t)stream;
-    // no per-launch reset of the hand-off flags: a flag is valid only when it holds THIS launch's epoch (below); the
-    // scratch must start zeroed once (the caller allocates it with zeros)
-    a.flags = reinterpret_cast<int*>(scratch);
-    a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes);
-    g_epoch_conv = (g_epoch_conv + 1) & 0x3fffffff;
-    a.epoch = (int)(0x20000000u | g_epoch_conv);
-    a.status = gp_status_buffer();
-    GpProfScope prof(GP_PROF_CONV, 2.0 * Cout * (double)npix * 147.0, st);  // algorithmic: 3 x 7 x 7 taps
-    if (ni == 2) hipLaunchKernelGGL(conv_planes_kernel<2>, dim3(kSlots), dim3(CNT), 0, st, a);
-    else if (ni == 3) hipLaunchKernelGGL(conv_planes_kernel<3>, dim3(kSlots), dim3(CNT), 0, st, a);
-    else hipLaunchKernelGGL(conv_planes_kernel<4>, dim3(kSlots), dim3(CNT), 0, st, a);
-    GP_CHECK_LAUNCH("gp_conv2d_stem_planes");
-    return GP_OK;
+    return conv_launch(a, plan, scratch, 2.0 * Cout * (double)npix * 147.0 /* algorithmic: 3 x 7 x 7 taps */, "gp_conv2d_stem_planes", (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 //     behind each of the first 12 MFMAs -> barrier.
 // Activations arrive as f32 k-major [K][n] (converted while staging, balanced over all 512 threads); weights as f16
 // planes [n][K] made by gp_split256_weights().
+// The launch plans -- usable shapes, the plane GEMM's tile shape / serial or parallel split / cap on slots per tile / build, and the
+// kernels' GpSlotPlan -- are gp_plan256.h (plain C++, included through gp_tile256.h; the CPU tests run the same text).
 #include "gp_tile256.h"
 
 typedef _Float16 g16x8 __attribute__((ext_vector_type(8)));
@@ -71,7 +73,8 @@ __global__ __launch_bounds__(TNT, 2) void gemm_split256_kernel(const Args256 a)
     const int w_hi = ACT_IS_B ? P_AHI : P_BHI, w_lo = ACT_IS_B ? P_ALO : P_BLO;
 
     // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan; no data-parallel rounds here)
-    const GpSlotPlan plan(a.tiles_i * a.tiles_j, a.K / TBK, false, 0);
+    const int T = a.tiles_i * a.tiles_j, nstep = a.K / TBK;
+    const GpSlotPlan plan(blockIdx.x, gridDim.x, T, nstep, false, 0);
     const int p = plan.p;
 
     // staging roles (all 512 threads): 2 n x 8 k activation micro-block + four 16-byte weight chunks
@@ -748,14 +751,14 @@ __global__ __launch_bounds__(TNT, 2) void gemm_planes256_kernel(const ArgsP a)
     const int wr = wave >> 1, wc = wave & 1, grp = wave >> 2;
     constexpr int P_AHI = 0, P_ALO = TPLANE, P_BHI = 2 * TPLANE, P_BLO = 3 * TPLANE;
 
-    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_tile256.h).  PAR: S = floor(slots /
-    // tiles) slots per tile, at most a.par (the host's cap: k-steps per slot, see the launch).
+    // ---- this slot's segments: (tile, k-step) ranges inside its XCD's tile chunk (GpSlotPlan, gp_plan256.h).  PAR: S = floor(slots /
+    // tiles) slots per tile, at most a.par (the host's cap: k-steps per slot, gp_planes256_plan).
     // (the GELU build keeps whole tiles, S = 1: with the partial-sum loop next to its epilogue hipcc spills 273 registers, and a
     // launch of T < 256 whole tiles on T slots is within 10 % of the split one at the sizes where it occurs -- fc1 below 16 crops)
-    constexpr bool kParSplit = PAR && PSPLIT && EPI != GP_EPI_GELU_PLANES;
+    constexpr bool kParSplit = gp_planes_build_splits(PAR, PSPLIT, EPI);
     const int T = a.tiles_i * a.tiles_j;
-    const int par_S = kParSplit ? max(1, min(a.par, (int)(gridDim.x >> 3) / max(GpSlotPlan::chunk_tiles(T), 1))) : 1;
-    const GpSlotPlan plan(T, a.K / TBK, !PAR && (a.dp & 1), PAR ? par_S : 0);
+    const int par_S = kParSplit ? gp_planes_par_slots(a.par, (int)(gridDim.x >> 3), GpSlotPlan::chunk_tiles(T, blockIdx.x & 7)) : 1;
+    const GpSlotPlan plan(blockIdx.x, gridDim.x, T, a.K / TBK, !PAR && (a.dp & 1), PAR ? par_S : 0);
     const int p = plan.p, x = plan.x, n = plan.n, n_seg = plan.n_seg;
 
     // staging: thread = (row tid >> 2 [+128], 16-byte k-chunk tid & 3) of each of the four planes
@@ -916,10 +919,7 @@ void launch256(Args256& a, bool act_is_b, int grid, hipStream_t st)
 
 }  // namespace
 
-bool gp_gemm_split256_usable(int I, int J, int K)
-{
-    return I % TB == 0 && J % TB == 0 && K % TBK == 0 && (long long)(I / TB) * (J / TB) >= kSlots;
-}
+bool gp_gemm_split256_usable(int I, int J, int K) { return gp_split256_usable(I, J, K); }
 
 size_t gp_gemm_split256_scratch_bytes() { return kHeaderBytes + sizeof(float) * kFragFloats * kSlots; }
 
@@ -974,39 +974,11 @@ int gp_gemm_split256_launch(const float* act, int ld_act, const void* whi, const
     return GP_OK;
 }
 
-static int g_planes_dp = 1;  // 1: data-parallel rounds before the stream-K remainder (0: everything stream-K; A/B hook)
-
-// internal entry (gp_vit.hip): D[i][j] = epi( out_scale * sum_k A[i][k] B[j][k] ), A / B = pre-split planes (see above)
-// J_valid <= J: rows of B that carry data (J itself stays a multiple of 256: the buffers are padded).  Tiles cover
-// floor(J_valid / 256) * 256 rows, strip_phase the rest (rows beyond round_up(J_valid, 32) are neither read nor written).
-static void planes_ragged(int J, int J_valid, int& J_main, int& strip_fj)
-{
-    J_main = (J_valid >= J || J_valid <= 0) ? J : (J_valid / TB) * TB;
-    strip_fj = (J_main == J) ? 0 : (J_valid - J_main + 31) / 32;
-}
-// Fewer tiles than slots (B < 64 crops at ViT-L): the kernel's parallel split-K mode needs at least one tile per XCD and one
-// k-step per slot (every slot's range then lies inside one or two tiles).
-static bool planes_par_usable(int I, int J_main, int K)
-{
-    if (I <= 0 || J_main <= 0 || I % TB || J_main % TB || K % TBK) return false;
-    const long long T = (long long)(I / TB) * (J_main / TB);
-    return T < kSlots && T >= 8 && (T / 8) * (K / TBK) >= kSlots / 8;
-}
-static int g_planes_par = 1;  // 0: shapes with fewer tiles than slots are refused (the caller falls back to the 128 x 128 kernel; A/B hook)
-static int g_planes_half = 1; // 0: never the 256 x 128 tiles (A/B hook, gp_gemm_planes256_set_half_tiles)
-// A tile is split over at most K / 32 / kParMinSteps slots: below 16 k-steps per slot the partial accumulators (256 KB each, published by
-// all non-owners at once, then read by the owner) cost more than the shorter k loop saves -- proj (K = 1024) at 16 crops 69 -> 62 us with
-// two instead of four slots per tile, at 8 crops 74 -> 55 us with two or four instead of eight (PAR_MIN_STEPS=.. tools/probe_planes_timeline.py).
-constexpr int kParMinSteps = 16;
-static int g_planes_par_min_steps = kParMinSteps;
-bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K)
-{
-    int J_main, fj;
-    planes_ragged(J, J_valid, J_main, fj);
-    if (J % TB || J_valid > J) return false;
-    if ((long long)(I / 32) * fj + kSlots >= 4096) return false;  // strip fragments must fit the 12-bit counter (strip_grab)
-    return gp_gemm_split256_usable(I, J_main, K) || (g_planes_par && planes_par_usable(I, J_main, K));
-}
+// internal entry (gp_vit.hip): D[i][j] = epi( out_scale * sum_k A[i][k] B[j][k] ), A / B = pre-split planes (see above).  The plan of a
+// launch -- usable or not, the ragged strip (J_valid <= J), tile shape, cap on slots per tile, which build -- is gp_plan256.h's
+// gp_planes256_plan; the planes_* fields of g_hooks are its A/B switches (set by the probe entry points at the end of this file).
+static GpPlanHooks g_hooks;
+bool gp_gemm_planes256_usable(int I, int J, int J_valid, int K) { return gp_planes256_plan(g_hooks, I, J, J_valid, K, GP_EPI_NONE).usable; }
 
 // Everything the plane GEMM refuses, before any HIP call (the C entry runs it ahead of its scratch reset as well).
 // Byte ranges: the tile epilogues store (and read the residual) through raw buffer resources of kRsrcBytes = 0x7ffffff0 bytes with
@@ -1021,11 +993,9 @@ static int planes256_check(const void* ahi, const void* alo, const void* bhi, co
                            const float* res, int ldr, const float* scratch, const GpPlaneOut* po)
 {
     constexpr long long kRsrcBytes = 0x7ffffff0ll;
-    GP_REQUIRE(gp_gemm_planes256_usable(I, J, J_valid, K),
-               "gp_gemm_planes256: I=%d, J=%d must be multiples of 256 with >= 8 tiles below J_valid=%d, K=%d of 32", I, J, J_valid, K);
-    int J_main, strip_fj;
-    planes_ragged(J, J_valid, J_main, strip_fj);
-    GP_REQUIRE((long long)(I / 32) * strip_fj + kSlots < 4096, "gp_gemm_planes256: too many strip fragments for the 12-bit counter");
+    const GpPlanesPlan plan = gp_planes256_plan(g_hooks, I, J, J_valid, K, epilogue);
+    GP_REQUIRE(plan.usable, "gp_gemm_planes256: I=%d, J=%d must be multiples of 256 with >= 8 tiles below J_valid=%d, K=%d of 32", I, J, J_valid, K);
+    GP_REQUIRE((long long)(I / 32) * plan.strip_fj + kSlots < 4096, "gp_gemm_planes256: too many strip fragments for the 12-bit counter");
     GP_REQUIRE(ahi && alo && bhi && blo && scratch && ((uintptr_t)ahi % 16 == 0) && ((uintptr_t)alo % 16 == 0) &&
                    ((uintptr_t)bhi % 16 == 0) && ((uintptr_t)blo % 16 == 0) && ((uintptr_t)scratch % 16 == 0),
                "gp_gemm_planes256: null / misaligned operand");
@@ -1065,18 +1035,61 @@ static int planes256_check(const void* ahi, const void* alo, const void* bhi, co
     return GP_OK;
 }
 
+// The kernel of (build, epilogue): every instantiation of gemm_planes256_kernel<EPI, TIMING, PAR, NJ, PSPLIT> is named here and nowhere
+// else; nullptr: not built.  The product's three epilogues (the ViT plane path: 3 = in-place residual, 6 = GELU -> planes, 7 = bias ->
+// planes) have all four builds but 6, which has no PSPLIT = false one (its PAR builds never split); the f32-output epilogues 0, 1, 2, 4, 5
+// are instantiated in probe builds only (-DGP_PROBES: tests of the tile / strip / split-K machinery on plain GEMMs), serial and parallel
+// split; the time-stamped builds (TIMING; probe builds only) are the serial kernel of 0, 3, 6, 7 and the parallel split of 3, 6, 7.
+typedef void (*PlanesKernel)(const ArgsP);
+template <int EPI>
+static PlanesKernel planes_kernel_of(int build, bool traced)
+{
+    constexpr bool kProduct = EPI == GP_EPI_BIAS_I_SCALE_RES || EPI == GP_EPI_GELU_PLANES || EPI == GP_EPI_BIAS_I_PLANES;
+    if (traced) {
+#ifdef GP_PROBES
+        if constexpr (kProduct || EPI == GP_EPI_NONE)
+            if (build == GP_PLANES_SERIAL) return gemm_planes256_kernel<EPI, true>;
+        if constexpr (kProduct)
+            if (build == GP_PLANES_PAR) return gemm_planes256_kernel<EPI, true, true>;
+#endif
+        return nullptr;
+    }
+    if (build == GP_PLANES_SERIAL) return gemm_planes256_kernel<EPI>;
+    if (build == GP_PLANES_PAR) return gemm_planes256_kernel<EPI, false, true>;
+    if constexpr (kProduct)
+        if (build == GP_PLANES_PAR_HALF) return gemm_planes256_kernel<EPI, false, true, 2>;
+    if constexpr (kProduct && EPI != GP_EPI_GELU_PLANES)
+        if (build == GP_PLANES_PAR_WHOLE) return gemm_planes256_kernel<EPI, false, true, 4, false>;
+    return nullptr;
+}
+static PlanesKernel planes_kernel(int build, int epilogue, bool traced)
+{
+    switch (epilogue) {
+#ifdef GP_PROBES
+        case GP_EPI_NONE: return planes_kernel_of<GP_EPI_NONE>(build, traced);
+        case GP_EPI_BIAS_I: return planes_kernel_of<GP_EPI_BIAS_I>(build, traced);
+        case GP_EPI_BIAS_I_GELU: return planes_kernel_of<GP_EPI_BIAS_I_GELU>(build, traced);
+        case GP_EPI_BIAS_J: return planes_kernel_of<GP_EPI_BIAS_J>(build, traced);
+        case GP_EPI_BIAS_I_RELU: return planes_kernel_of<GP_EPI_BIAS_I_RELU>(build, traced);
+#endif
+        case GP_EPI_BIAS_I_SCALE_RES: return planes_kernel_of<GP_EPI_BIAS_I_SCALE_RES>(build, traced);
+        case GP_EPI_GELU_PLANES: return planes_kernel_of<GP_EPI_GELU_PLANES>(build, traced);
+        case GP_EPI_BIAS_I_PLANES: return planes_kernel_of<GP_EPI_BIAS_I_PLANES>(build, traced);
+        default: return nullptr;
+    }
+}
+
 int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, const void* blo, float* D, int ldd, void* ohi,
                              void* olo, int ldo, int I, int J, int J_valid, int K, int epilogue, const float* bias, const float* scale,
                              const float* res, int ldr, float out_scale, float* scratch, hipStream_t st, unsigned long long* trace,
                              const GpPlaneOut* po)
 {
     if (const int rc = planes256_check(ahi, alo, bhi, blo, D, ldd, ohi, olo, ldo, I, J, J_valid, K, epilogue, bias, scale, res, ldr, scratch, po)) return rc;
-    int J_main, strip_fj;
-    planes_ragged(J, J_valid, J_main, strip_fj);
+    const GpPlanesPlan plan = gp_planes256_plan(g_hooks, I, J, J_valid, K, epilogue, trace != nullptr);
     ArgsP a{(const _Float16*)ahi, (const _Float16*)alo, (const _Float16*)bhi, (const _Float16*)blo, D, ldd, (_Float16*)ohi, (_Float16*)olo, ldo,
-            K, bias, scale, res, ldr, I / TB, J_main / TB, 4, reinterpret_cast<int*>(scratch),
-            reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, out_scale, g_planes_dp, trace, gp_status_buffer(),
-            J_main, strip_fj, (long long)(I / TB) * (J_main / TB) < kSlots ? max(1, (K / TBK) / g_planes_par_min_steps) : 0};
+            K, bias, scale, res, ldr, plan.tiles_i, plan.tiles_j, 4, reinterpret_cast<int*>(scratch),
+            reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, out_scale, g_hooks.planes_dp, trace, gp_status_buffer(),
+            plan.J_main, plan.strip_fj, plan.par};
     a.plane_scale = kActScale;
     a.amax = nullptr;
     if (po) {   // per-tensor output scale of the plane epilogues 6 / 7 (planes256_check: only there may it differ from 8)
@@ -1086,88 +1099,20 @@ int gp_gemm_planes256_launch(const void* ahi, const void* alo, const void* bhi, 
     g_epoch256 = (g_epoch256 + 1) & 0x3fffffff;
     a.epoch = (int)(0x40000000u | g_epoch256);
     GpProfScope prof(GP_PROF_GEMM_SPLIT, 2.0 * I * (J_valid > 0 && J_valid < J ? J_valid : J) * K, st);
-    // The product's three epilogues (the ViT plane path: 3 = in-place residual, 6 = GELU -> planes, 7 = bias -> planes); the f32-output
-    // epilogues 0, 1, 2, 4, 5 are instantiated in probe builds only (-DGP_PROBES: tests of the tile / strip / split-K machinery on
-    // plain GEMMs)
-#ifdef GP_PROBES
-#define GP_PLANES_EXTRA(...)                                                                                              \
-    case GP_EPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;           \
-    case GP_EPI_BIAS_I: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
-    case GP_EPI_BIAS_I_GELU: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_GELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break; \
-    case GP_EPI_BIAS_J: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_J, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;       \
-    case GP_EPI_BIAS_I_RELU: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_RELU, __VA_ARGS__>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-    if (trace && a.par) {  // probe build of the parallel split-K kernel with per-slot time stamps
-        switch (epilogue) {
-            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, true, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            default: GP_REQUIRE(false, "gp_gemm_planes256_trace: epilogue %d has no traced parallel build", epilogue);
-        }
-        GP_CHECK_LAUNCH("gp_gemm_planes256_trace/par");
-        return GP_OK;
-    }
-    if (trace) {  // probe build with per-slot time stamps
-        switch (epilogue) {
-            case GP_EPI_NONE: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            default: GP_REQUIRE(false, "gp_gemm_planes256_trace: epilogue %d has no traced build", epilogue);
-        }
-        GP_CHECK_LAUNCH("gp_gemm_planes256_trace");
-        return GP_OK;
-    }
-#else
-#define GP_PLANES_EXTRA(...)
+    const bool par = plan.build != GP_PLANES_SERIAL;
+#ifndef GP_PROBES
     GP_REQUIRE(!trace, "gp_gemm_planes256: time-stamped launches need the probe build (-DGP_PROBES)");
 #endif
-    // 256 x 128 tiles where the 256 x 256 ones fill at most half the slots (ViT-L below ~16 crops): the parallel split-K build on twice
-    // the tiles -- proj / fc2 split every tile over half as many slots with half-size partial accumulators, q|k|v and fc1 stop
-    // splitting / fill the chip with whole tiles.  (Between 128 and 256 whole tiles, twice as many half-width tiles cut stream-K
-    // style over all slots by the serial hand-over build was measured too: ViT-L forward at 12 / 16 / 40 / 48 crops 8.55 -> 8.95,
-    // 10.39 -> 10.44, 22.95 -> 22.5, 25.19 -> 25.55 ms -- the hand-overs cost what the balance gains; not kept.)
-    const long long T256 = (long long)a.tiles_i * a.tiles_j;
-    const bool epi_half = epilogue == GP_EPI_BIAS_I_SCALE_RES || epilogue == GP_EPI_GELU_PLANES || epilogue == GP_EPI_BIAS_I_PLANES;
-    if (a.par && g_planes_half && epi_half && 2 * T256 <= kSlots) {
-        a.tiles_j = J_main / (TB / 2);
-        switch (epilogue) {
-            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            default: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true, 2>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        }
-        GP_CHECK_LAUNCH("gp_gemm_planes256/par128");
-        return GP_OK;
+    const PlanesKernel kernel = planes_kernel(plan.build, epilogue, trace != nullptr);
+    if (trace) {  // probe builds with per-slot time stamps
+        GP_REQUIRE(kernel || par, "gp_gemm_planes256_trace: epilogue %d has no traced build", epilogue);
+        GP_REQUIRE(kernel, "gp_gemm_planes256_trace: epilogue %d has no traced parallel build", epilogue);
     }
-    if (a.par && 2 * T256 > kSlots && (epilogue == GP_EPI_BIAS_I_SCALE_RES || epilogue == GP_EPI_BIAS_I_PLANES)) {
-        // 129-255 whole tiles, one per slot (S = floor(256 / tiles) = 1): the PAR build WITHOUT the split-K reduction (see PSPLIT)
-        a.par = 1;
-        if (epilogue == GP_EPI_BIAS_I_SCALE_RES)
-            hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
-        else
-            hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true, 4, false>), dim3(kSlots), dim3(TNT), 0, st, a);
-        GP_CHECK_LAUNCH("gp_gemm_planes256/par-whole");
-        return GP_OK;
-    }
-    if (a.par) {  // fewer tiles than slots: the parallel split-K build (its own instantiation: the serial hand-over kernel keeps its registers)
-        switch (epilogue) {
-            GP_PLANES_EXTRA(false, true)
-            case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES, false, true>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-            default: GP_REQUIRE(false, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
-        }
-        GP_CHECK_LAUNCH("gp_gemm_planes256/par");
-        return GP_OK;
-    }
-    switch (epilogue) {
-        GP_PLANES_EXTRA(false)
-        case GP_EPI_BIAS_I_SCALE_RES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_SCALE_RES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        case GP_EPI_GELU_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_GELU_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        case GP_EPI_BIAS_I_PLANES: hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_BIAS_I_PLANES>), dim3(kSlots), dim3(TNT), 0, st, a); break;
-        default: GP_REQUIRE(false, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
-    }
-#undef GP_PLANES_EXTRA
-    GP_CHECK_LAUNCH("gp_gemm_planes256");
+    GP_REQUIRE(kernel, "gp_gemm_planes256: epilogue %d is not built (product: 3, 6, 7; the others need -DGP_PROBES)", epilogue);
+    hipLaunchKernelGGL(kernel, dim3(kSlots), dim3(TNT), 0, st, a);
+    static const char* const kNames[2][4] = {{"gp_gemm_planes256", "gp_gemm_planes256/par", "gp_gemm_planes256/par128", "gp_gemm_planes256/par-whole"},
+                                             {"gp_gemm_planes256_trace", "gp_gemm_planes256_trace/par", "", ""}};
+    GP_CHECK_LAUNCH(kNames[trace ? 1 : 0][plan.build]);
     return GP_OK;
 }
 
@@ -1231,10 +1176,10 @@ int gp_gemm_planes256_timing(const void* a_hi, const void* a_lo, const void* b_h
     if (hipMemsetAsync(scratch, 0, kHeaderBytes, (hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     ArgsP a{(const _Float16*)a_hi, (const _Float16*)a_lo, (const _Float16*)b_hi, (const _Float16*)b_lo, D, ldd, nullptr, nullptr, 0,
             K, nullptr, nullptr, nullptr, 0, I / TB, J / TB, 4, reinterpret_cast<int*>(scratch),
-            reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, kOutScale, g_planes_dp};
+            reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + kHeaderBytes), 0, kOutScale, g_hooks.planes_dp};
     if (++g_epoch256 == 0) ++g_epoch256;
     a.epoch = (int)g_epoch256;
-    hipLaunchKernelGGL((gemm_planes256_kernel<GP_EPI_NONE, true>), dim3(kSlots), dim3(TNT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(planes_kernel(GP_PLANES_SERIAL, GP_EPI_NONE, true), dim3(kSlots), dim3(TNT), 0, (hipStream_t)stream, a);
     GP_CHECK_LAUNCH("gp_gemm_planes256_timing");
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GP_ELAUNCH;
     return hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_t256), 8 * sizeof(unsigned long long)) == hipSuccess ? GP_OK : GP_ELAUNCH;
@@ -1255,20 +1200,20 @@ int gp_gemm_planes256_trace(const void* a_hi, const void* a_lo, const void* b_hi
 
 int gp_gemm_planes256_set_dp(int mode)  // bit 0: data-parallel rounds (default on); bit 1: test hook, head fragments are never published
 {
-    g_planes_dp = mode & 3;
+    g_hooks.planes_dp = mode & 3;
     return GP_OK;
 }
 
 int gp_gemm_planes256_set_half_tiles(int on)  // 0: launches below half a tile per slot keep the 256 x 256 tiles (A/B hook)
 {
-    g_planes_half = on ? 1 : 0;
+    g_hooks.planes_half = on ? 1 : 0;
     return GP_OK;
 }
 
 int gp_gemm_planes256_set_par(int on)  // 0: refuse shapes with fewer tiles than slots (A/B hook: the ViT then takes the 128 x 128 kernels)
 {
-    g_planes_par = on ? 1 : 0;
-    g_planes_par_min_steps = on > 1 ? on : kParMinSteps;   // on >= 2 (A/B hook): at least `on` k-steps per slot of a split tile
+    g_hooks.planes_par = on ? 1 : 0;
+    g_hooks.planes_par_min_steps = on > 1 ? on : kParMinSteps;   // on >= 2 (A/B hook): at least `on` k-steps per slot of a split tile
     return GP_OK;
 }
 

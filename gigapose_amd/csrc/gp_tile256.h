@@ -2,13 +2,17 @@
 // conv_planes_kernel / conv_halo_kernel (gp_conv256.hip) -- 512 threads = 8 waves as 4 x 2, wave tile 64 x 32 NJ, ONE f32 accumulator
 // acc[2][NJ] of v_mfma_f32_32x32x16_f16 fragments -- share
 //   * the scratch layout (header of flags + error word, then one accumulator fragment per slot) and the LDS row swizzle,
-//   * the slot plan: which (tile, unit) ranges a workgroup runs and in which order (GpSlotPlan),
+//   * the launch plans (gp_plan256.h, plain C++ that the launchers and the CPU tests run too): the hosts' decisions per launch, and the
+//     slot plan -- which (tile, unit) ranges a workgroup runs and in which order (GpSlotPlan) -- with the slots-per-tile rules,
 //   * the deterministic accumulator hand-over between the slots of a split tile (gp_handoff_wait, gp_frag_publish / _load / _add),
 //   * the three-product matrix step (gp_mfma3_step) and the loop of two wave groups half a step apart (gp_two_group_loop),
 //   * the packed plane arithmetic of the tile epilogues (gp_hi_pair, gp_lo_pair, gp_sum_planes, gp_absmax3).
-// Device code only; everything is inlined into the kernels (they sit at the register limit: a call would spill).
+// Device code only but for gp_plan256.h; everything is inlined into the kernels (they sit at the register limit: a call would spill).
 #pragma once
 #include "gp_common.h"
+#include "gp_plan256.h"  // kSlots, GpSlotPlan, the slots-per-tile rules, the hosts' launch plans
+static_assert(kPlanEpiScaleRes == GP_EPI_BIAS_I_SCALE_RES && kPlanEpiGeluPlanes == GP_EPI_GELU_PLANES && kPlanEpiBiasPlanes == GP_EPI_BIAS_I_PLANES,
+              "gp_plan256.h names the epilogues of the tile-shape policy by their C-ABI numbers");
 
 typedef _Float16 gp_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int gp_u32x4 __attribute__((ext_vector_type(4)));
@@ -16,7 +20,6 @@ typedef unsigned int gp_u32x4 __attribute__((ext_vector_type(4)));
 // ---- scratch: [flags: one int per slot .. error word .. padded to kHeaderBytes][kSlots accumulator fragments of kFragFloats].  A forward
 // shares ONE scratch between these kernels and gp_gemm.hip's stream-K, so the header sizes must agree and this family's error word lies
 // beyond the stream-K flags and their error word (flags[kGpSkMaxSlots]).
-constexpr int kSlots = 256;                        // workgroups of a launch: one per CU
 constexpr int kTileThreads = 512;                  // threads of a workgroup: 8 waves
 constexpr int kErrWord = 1025;                     // header word set when a hand-over timed out
 constexpr size_t kHeaderBytes = 8192;
@@ -31,71 +34,6 @@ static_assert(kErrWord > kGpSkMaxSlots && (size_t)(kErrWord + 1) * sizeof(int) <
 // 64-byte LDS rows, the 16-byte chunk kc of a row XOR-placed by row bits 2-3 (offset in halfs): the 32 rows x 2 chunks of a fragment read
 // and the 4 chunks x 16 rows of a staging write are both conflict-free.
 __device__ __forceinline__ int gp_swz(int row, int kc) { return row * kRowHalfs + ((kc ^ ((row >> 2) & 3)) << 3); }
-
-// ---- Slot plan.  Workgroup p of the grid is slot n = p >> 3 of XCD x = p & 7 (the hardware places block id on XCD id % 8); each XCD
-// owns one contiguous chunk of the tile list (n_t tiles from t_lo) and its slots_x slots cut that chunk's (tile, unit) space -- a unit is
-// a k-step, or a block of 32 input channels in conv_halo_kernel -- into segments: whole tiles, at most one HEAD (the first units of a
-// tile: its accumulator fragment is published for the slot that continues the tile) and at most one REST (continues a tile).
-//   Data-parallel rounds first: while the chunk holds two or more tiles per slot, round r gives slot n the whole tile
-// r * slots_x + n -- the 32 slots of an XCD then sit on the same k-step of 32 neighbouring tiles (4 i-panels x 8
-// j-panels) and share their operand slabs in that XCD's L2.  Only the last round + remainder is cut stream-K style
-// (its slots run at staggered k offsets and get no L2 reuse: 1.9 GB fetched per fc1 launch when everything was).
-//   PAR (par_S > 0; fewer tiles than slots): S = par_S slots per tile, each an equal share of the tile's units from a zero accumulator,
-// all at once; slot n holds part n % S of tile n / S, slots beyond S * tiles have no tile.  All but the last publish their partial
-// accumulator (heads), the slot holding the last range (a rest) adds them in slot order, nearest first -- a fixed order, the result
-// depends on the shape only -- and runs the epilogue.  S = 1: whole tiles, no exchange.  (The serial hand-over, par_S = 0, keeps a split
-// tile's summation order but makes its slots wait for each other: with fewer tiles than slots every tile is split and a launch would
-// take as long as one whole tile.)
-struct GpSlotPlan {
-    struct Segment {
-        int tile;      // index into the launch's tile list
-        int u0, u1;    // units [u0, u1) of that tile
-        bool is_head;  // publishes its accumulator instead of running the epilogue
-        bool is_rest;  // continues a tile: takes over (par_S = 0) or adds (par_S > 0) the fragments of the slots before it
-    };
-    int p, x, n, slots_x;
-    int upt, t_lo, rounds_dp, n_dp, ta, sa, tb, sb, n_head, n_rest, first_whole, n_seg;
-
-    __device__ __forceinline__ GpSlotPlan(int tiles, int units_per_tile, bool dp_rounds_allowed, int par_S)
-    {
-        p = blockIdx.x, x = p & 7, n = p >> 3, slots_x = gridDim.x >> 3;
-        upt = units_per_tile;
-        t_lo = (int)((long long)tiles * x / 8);
-        const int n_t = (int)((long long)tiles * (x + 1) / 8) - t_lo;
-        rounds_dp = (dp_rounds_allowed && n_t / slots_x > 1) ? n_t / slots_x - 1 : 0;
-        n_dp = rounds_dp * slots_x;
-        const long long U = (long long)(n_t - n_dp) * upt;
-        long long u0 = U * n / slots_x, u1 = U * (n + 1) / slots_x;
-        if (par_S > 0) {
-            const int tile = n / par_S, part = n - tile * par_S;
-            u0 = u1 = 0;
-            if (tile < n_t) {
-                u0 = (long long)tile * upt + upt * part / par_S;
-                u1 = (long long)tile * upt + upt * (part + 1) / par_S;
-            }
-        }
-        ta = (int)(u0 / upt), sa = (int)(u0 % upt);
-        tb = (int)(u1 / upt), sb = (int)(u1 % upt);
-        n_head = sb > 0 ? 1 : 0, n_rest = sa > 0 ? 1 : 0;
-        first_whole = ta + n_rest;
-        n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest;
-    }
-    // tiles of this slot's XCD chunk (the cap of PAR's slots per tile is slots_x / tiles_here)
-    static __device__ __forceinline__ int chunk_tiles(int tiles)
-    {
-        const int x = blockIdx.x & 7;
-        return (int)((long long)tiles * (x + 1) / 8) - (int)((long long)tiles * x / 8);
-    }
-    // order: data-parallel rounds, the head, whole tiles, the rest
-    __device__ __forceinline__ Segment segment(int seg) const
-    {
-        const bool is_dp = seg < rounds_dp;
-        const bool is_head = !is_dp && seg - rounds_dp < n_head;
-        const bool is_rest = !is_dp && n_rest && seg == n_seg - 1;
-        const int t = is_dp ? seg * slots_x + n : n_dp + (is_head ? tb : (is_rest ? ta : first_whole + seg - rounds_dp - n_head));
-        return {t_lo + t, is_rest ? sa : 0, is_head ? sb : upt, is_head, is_rest};
-    }
-};
 
 // ---- Hand-over.  A flag is valid when it holds THIS launch's epoch (no reset between launches).  One lane waits for the flags of slots
 // first_slot, first_slot - stride, .. last_slot (nearest first; first_slot == last_slot: the one flag of the serial hand-over), sleeping

@@ -1,12 +1,13 @@
-"""Host model of the launch plans of the IST convolutions in split numerics (gigapose_amd/csrc/gp_conv256.hip, gp_tile256.h).
+"""The launch plans of the IST convolutions in split numerics (gigapose_amd/csrc/gp_conv256.hip), as the tests see them.
 
 The kernels run no fixed schedule: per launch the host picks a plan from the tile count (batch size x a constant of the layer) and the
-kernel's GpSlotPlan cuts every XCD's chunk of tiles into segments.  This module restates those decisions line by line, with the names of
-the sources, so that a test can enumerate every plan a batch size selects and hold the kernels to it:
+kernel's GpSlotPlan cuts every XCD's chunk of tiles into segments.  Both are stated once, in gigapose_amd/csrc/gp_plan256.h, and this
+module CALLS that code (gigapose_testing/plan256.py: the header compiled for the host), so that a test can enumerate every plan a batch size
+selects and hold the kernels to it:
 
-* conv_launch / stem_launch: gp_conv2d_planes, conv_halo_launch, gp_conv2d_stem_planes -- halo usable, ni, tiles_i, tiles_j, units per tile,
-  par, the slots_x loop, par_cap;
-* slot_segments / launch_slots: GpSlotPlan with par_S and chunk_tiles -> per slot the segments (tile, u0, u1, kind), kind in KINDS:
+* conv_launch / stem_launch: gp_conv256_plan / gp_stem256_plan, what gp_conv2d_planes and gp_conv2d_stem_planes launch by -- kernel, ni,
+  tiles_i, tiles_j, units per tile, par, slots_x, par_cap;
+* slot_segments / launch_slots: GpSlotPlan with gp_halo_par_slots and chunk_tiles -> per slot the segments (tile, u0, u1, kind), kind in KINDS:
       dp      a whole tile of a data-parallel round
       head    the first units of a tile; the accumulator fragment is published
       whole   a whole tile
@@ -15,99 +16,42 @@ the sources, so that a test can enumerate every plan a batch size selects and ho
               and publishes its own (serial); a part that is neither first nor last (parallel split: published, nothing received)
 * ist_layer_launches: the launches of one ResNet.forward; plan_class: the signature that tells two plans apart.
 
-BATCHES and STAGE_SHAPES at the end are the cases of the GPU tests (tests/test_gpu_ist_batch_plans.py, tests/test_gpu_split.py);
+What is about the tests and not about the plan stays Python: the flags a slot waits for, the trace words, the plan classes.  BATCHES and
+STAGE_SHAPES at the end are the cases of the GPU tests (tests/test_gpu_ist_batch_plans.py, tests/test_gpu_split.py);
 tests/test_conv_plans.py holds them to the enumeration."""
+from gigapose_testing import plan256
 
-CBK, CT = 32, 256
 KINDS = ("dp", "head", "whole", "rest", "middle")
-g_conv_par_min_cb = 1
 
 
 # ------------------------------------------------------------------------------------------------------------------ host side
-def conv_halo_usable(H, W, Cin, Cout, KH, KW, stride, pad):
-    return KH == 3 and KW == 3 and stride == 1 and pad == 1 and H % 16 == 0 and W % 16 == 0 and Cin % 32 == 0 and Cout % 64 == 0
+def _launch(plan):
+    if plan["refused"]:
+        return None
+    return dict(kernel=plan["kernel"], ni=plan["ni"], tiles_i=plan["tiles_i"], tiles_j=plan["tiles_j"], tiles=plan["tiles_i"] * plan["tiles_j"],
+                upt=plan["upt"], steps_per_unit=plan["steps_per_unit"], par=plan["par"], slots_x=plan["slots_x"], par_cap=plan["par_cap"])
 
 
 def conv_launch(B, H, W, Cin, Cout, KH, KW, stride, pad):
     """gp_conv2d_planes -> the launch: dict(kernel, ni, tiles_i, tiles_j, tiles, upt, steps_per_unit, par, slots_x, par_cap), or None where
     the entry point refuses the shape (GP_REQUIRE)."""
-    OH = (H + 2 * pad - KH) // stride + 1
-    OW = (W + 2 * pad - KW) // stride + 1
-    K = KH * KW * Cin
-    npix = B * OH * OW
-    if not (Cin % 32 == 0 and Cout % 64 == 0 and KH * KW <= 9 and npix % CT == 0 and B > 0):
-        return None
-    ni = 4 if Cout >= 256 else Cout // 64
-    if conv_halo_usable(H, W, Cin, Cout, KH, KW, stride, pad):          # conv_halo_launch
-        tiles_i = B * (OH // 16) * (OW // 16)
-        tiles_j = (Cout + 64 * ni - 1) // (64 * ni)
-        ncb = Cin // CBK
-        n_tiles, units = tiles_i * tiles_j, tiles_i * tiles_j * ncb * 9
-        slots_x = 32
-        par = n_tiles < 8 * slots_x and n_tiles >= 8 and ncb >= 2
-        par_cap = max(1, ncb // g_conv_par_min_cb)
-        while (not par) and slots_x > 1 and n_tiles < 8 * slots_x and units // (8 * slots_x) < 32:
-            slots_x >>= 1
-        return dict(kernel="halo", ni=ni, tiles_i=tiles_i, tiles_j=tiles_j, tiles=n_tiles, upt=ncb, steps_per_unit=9, par=par, slots_x=slots_x,
-                    par_cap=par_cap)
-    tiles_i = npix // CT
-    tiles_j = (Cout + 64 * ni - 1) // (64 * ni)
-    n_tiles, units = tiles_i * tiles_j, tiles_i * tiles_j * (K // CBK)
-    slots_x = 32
-    while slots_x > 1 and n_tiles < 8 * slots_x and units // (8 * slots_x) < 32:
-        slots_x >>= 1
-    return dict(kernel="gather", ni=ni, tiles_i=tiles_i, tiles_j=tiles_j, tiles=n_tiles, upt=K // CBK, steps_per_unit=1, par=False, slots_x=slots_x,
-                par_cap=1)
+    return _launch(plan256.conv256(B, H, W, Cin, Cout, KH, KW, stride, pad))
 
 
 def stem_launch(B, S, Cout):
     """gp_conv2d_stem_planes: conv_planes_kernel on all 256 slots, one kernel row (K = 7 x 32) per k-step."""
-    npix = B * (S // 2) * (S // 2)
-    if not (B > 0 and S % 2 == 0 and (Cout in (128, 192) or Cout % 256 == 0) and npix % CT == 0):
-        return None
-    ni = 4 if Cout >= 256 else Cout // 64
-    tiles_i = npix // CT
-    tiles_j = (Cout + 64 * ni - 1) // (64 * ni)
-    return dict(kernel="stem", ni=ni, tiles_i=tiles_i, tiles_j=tiles_j, tiles=tiles_i * tiles_j, upt=7, steps_per_unit=1, par=False, slots_x=32,
-                par_cap=1)
+    return _launch(plan256.stem256(B, S, Cout))
 
 
 # ------------------------------------------------------------------------------------------------------------------ device side
-def chunk_tiles(tiles, x):
-    return tiles * (x + 1) // 8 - tiles * x // 8
+chunk_tiles = plan256.chunk_tiles
 
 
 def slot_segments(p, grid, tiles, units_per_tile, dp_rounds_allowed, par_S):
     """GpSlotPlan of workgroup p of a grid of `grid`: -> [(tile, u0, u1, kind)] in the order the slot runs them."""
-    x, n, slots_x = p & 7, p >> 3, grid >> 3
-    upt = units_per_tile
-    t_lo = tiles * x // 8
-    n_t = tiles * (x + 1) // 8 - t_lo
-    rounds_dp = n_t // slots_x - 1 if (dp_rounds_allowed and n_t // slots_x > 1) else 0
-    n_dp = rounds_dp * slots_x
-    U = (n_t - n_dp) * upt
-    u0, u1 = U * n // slots_x, U * (n + 1) // slots_x
-    if par_S > 0:
-        tile = n // par_S
-        part = n - tile * par_S
-        u0 = u1 = 0
-        if tile < n_t:
-            u0 = tile * upt + upt * part // par_S
-            u1 = tile * upt + upt * (part + 1) // par_S
-    ta, sa = u0 // upt, u0 % upt
-    tb, sb = u1 // upt, u1 % upt
-    n_head, n_rest = (1 if sb > 0 else 0), (1 if sa > 0 else 0)
-    first_whole = ta + n_rest
-    n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest
-    segs = []
-    for seg in range(n_seg):                                           # GpSlotPlan::segment
-        is_dp = seg < rounds_dp
-        is_head = (not is_dp) and seg - rounds_dp < n_head
-        is_rest = (not is_dp) and n_rest == 1 and seg == n_seg - 1
-        t = seg * slots_x + n if is_dp else n_dp + (tb if is_head else (ta if is_rest else first_whole + seg - rounds_dp - n_head))
-        kind = "dp" if is_dp else "middle" if (is_head and is_rest) else "head" if is_head else "rest" if is_rest else "whole"
-        segs.append((t_lo + t, sa if is_rest else 0, sb if is_head else upt, kind))
-    return segs
+    segs = plan256.slot_segments(p, grid, tiles, units_per_tile, dp_rounds_allowed, par_S)
+    return [(t, u0, u1, "dp" if dp else "middle" if (head and rest) else "head" if head else "rest" if rest else "whole")
+            for t, u0, u1, head, rest, dp in segs]
 
 
 def launch_slots(launch):
@@ -118,7 +62,7 @@ def launch_slots(launch):
         x = p & 7
         par_S = 0
         if launch["par"]:                                              # conv_halo_kernel<.., PAR = true>; ncb = upt
-            par_S = min(min(max(1, (grid >> 3) // max(chunk_tiles(T, x), 1)), upt), max(1, launch["par_cap"]))
+            par_S = plan256.halo_par_slots(launch["par_cap"], grid >> 3, chunk_tiles(T, x), upt)
             S_of[x] = par_S
         slots[p] = slot_segments(p, grid, T, upt, not launch["par"], par_S)
     return dict(launch, grid=grid, slots=slots, par_S=S_of)

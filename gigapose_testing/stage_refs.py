@@ -931,7 +931,7 @@ PLANES_FLOOR = (2.0 ** -22, 2.0 ** -28)      # (relative, absolute) term of a pl
 WIDE_FLOOR = (2.0 ** -22, 2.0 ** -35)        # hi + lo / 2048: 22 bits; the lo plane's f16 subnormal spacing 2^-24 / 2048
 
 # route -> (Cin, Cout, k, stride, pad, H = W, B): the smallest launches of gp_conv2d_planes that reach each kernel instantiation
-# (Cin % 32 = 0, Cout % 64 = 0, B OH OW % 256 = 0; gp_conv256.hip: conv_halo_usable / conv_halo_launch / gp_conv2d_planes)
+# (Cin % 32 = 0, Cout % 64 = 0, B OH OW % 256 = 0; gp_plan256.h: gp_conv256_plan, launched by gp_conv256.hip's gp_conv2d_planes)
 CONV_GUARD_ROUTES = {
     "gather_ni2": (32, 128, 3, 2, 1, 32, 1),
     "gather_ni3_1x1": (32, 192, 1, 2, 0, 32, 1),

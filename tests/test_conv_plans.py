@@ -1,6 +1,6 @@
-"""CPU: the host model of the IST convolutions' launch plans (gigapose_testing/conv_plans.py: gp_conv2d_planes, conv_halo_launch,
-gp_conv2d_stem_planes and gp_tile256.h's GpSlotPlan restated) checked exhaustively -- every layer of IST_CFG at every batch size from
-1 to 64 and at 65, 96, 127, 128:
+"""CPU: the IST convolutions' launch plans (gigapose_testing/conv_plans.py calls gp_plan256.h's gp_conv256_plan, gp_stem256_plan and
+GpSlotPlan -- the code gp_conv2d_planes, gp_conv2d_stem_planes and their kernels run, compiled for the host) checked exhaustively --
+every layer of IST_CFG at every batch size from 1 to 64 and at 65, 96, 127, 128:
 
 * every (tile, unit) is computed exactly once;
 * serial plans: a rest or middle segment continues exactly where slot p - 8 stopped, a chain starts at unit 0 and ends at the tile's last
@@ -10,14 +10,13 @@ gp_conv2d_stem_planes and gp_tile256.h's GpSlotPlan restated) checked exhaustive
 * the plan classes over B = 1 .. 64 are enumerated and printed, and the case lists of the GPU tests are held to them: BATCHES runs every
   class, STAGE_SHAPES has every property of every class of gp_conv2d_planes and the plans it promises.
 
-The model is tied to the kernels by the trace test of tests/test_gpu_ist_batch_plans.py (segments and k-steps per slot)."""
+That the kernels run what the plan says is the trace test's business (tests/test_gpu_ist_batch_plans.py: segments and k-steps per slot)."""
 import functools
 
 import pytest
 
 from gigapose_testing import conv_plans as cp
 from test_oracle_pose_ist import IST_CFG
-from test_schedule_models import launch_plan, par_plan
 
 SIZES = list(range(1, 65)) + [65, 96, 127, 128]
 
@@ -88,14 +87,6 @@ def test_every_plan_computes_every_unit_once_and_pairs_its_hand_overs():
         check_plan(plan, where)
         kinds = {k for s in plan["slots"].values() for *_, k in s}
         n_middle += "middle" in kinds
-        # the models of tests/test_schedule_models.py where they apply (launch_plan never considered a middle segment: it asserts there is none)
-        if launch["par"]:
-            got, S_of = par_plan(launch["tiles"], launch["upt"], 1, plan["grid"])
-            assert S_of == plan["par_S"], where
-            mine = {p: (s[0][0], s[0][1], s[0][2]) for p, s in plan["slots"].items() if s}
-            assert {p: v[:3] for p, v in got.items()} == mine, where
-        elif "middle" not in kinds:
-            assert launch_plan(launch["tiles"], launch["upt"], True, plan["grid"]) == plan["slots"], where
     print(f"{len(distinct_launches())} distinct launches over B = {SIZES[0]} .. {SIZES[-1]}, {n_middle} with a middle segment")
     assert n_middle > 0
 

@@ -109,7 +109,7 @@ def test_split256_layout(case, shape):
 # ---- the plane GEMM
 
 def planes_build(I, J, jv, epi):
-    """Which build gp_gemm_planes256_launch takes (gp_split256.hip: planes_ragged, planes_par_usable and the half-tile rule), 256 slots:
+    """Which build gp_gemm_planes256_launch takes (gp_plan256.h: gp_planes256_plan -- the ragged strip and the half-tile rule), 256 slots:
     tiled = the serial kernel on >= 256 tiles of 256 x 256; half-width = parallel split-K on 256 x 128 tiles (at most 128 whole tiles);
     whole = the parallel build without the reduction, one tile per slot (129-255 tiles, epilogues 3 and 7); split-K = the parallel
     split-K build on 256 x 256 tiles (what is left: epilogue 6 and the probe-only epilogues at 129-255 tiles)."""

@@ -2,7 +2,7 @@
 
 conv_planes_kernel, conv_halo_kernel and the stem build (gp_conv256.hip) run no fixed schedule: the host picks a plan from the tile count
 -- batch size x a constant of the layer -- and GpSlotPlan cuts each XCD's chunk of tiles into data-parallel rounds, whole tiles, published
-heads, received rests and middle segments.  gigapose_testing/conv_plans.py restates those decisions; tests/test_conv_plans.py enumerates
+heads, received rests and middle segments.  gigapose_testing/conv_plans.py calls those decisions (gp_plan256.h); tests/test_conv_plans.py enumerates
 the 78 plan classes of B = 1 .. 64 (20 of them reached at B = 1, 3, 5, where the backbone was compared with float64 until now) and holds
 conv_plans.BATCHES to running every one.  Here, for each B of that list, on the product binary:
 

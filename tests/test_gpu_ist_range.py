@@ -105,7 +105,7 @@ def check_in_range_outputs(tag, got, ref, floor):
 
 
 ROUTE_DOC = {
-    "gather_ni2": "32 -> 128, 3 x 3 stride 2 on 32 x 32, B = 1: stride 2 -> conv_halo_usable false; ni = 128 / 64 = 2 -> conv_planes_kernel<2>, one whole tile",
+    "gather_ni2": "32 -> 128, 3 x 3 stride 2 on 32 x 32, B = 1: stride 2 -> not the halo kernel (gp_conv256_plan); ni = 128 / 64 = 2 -> conv_planes_kernel<2>, one whole tile",
     "gather_ni3_1x1": "32 -> 192, 1 x 1 stride 2: ni = 3 -> conv_planes_kernel<3> (alpha | beta through the LDS stash), K = 32: ONE k-step",
     "gather_ni4_two_channel_tiles": "32 -> 512, 3 x 3 stride 2: ni = 4, tiles_j = 2 -> conv_planes_kernel<4>, two whole tiles on two XCD chunks",
     "gather_3x3_s1_not_16": "32 -> 128, 3 x 3 stride 1 on 8 x 8, B = 4: H % 16 != 0 -> the halo kernel refuses, conv_planes_kernel<2>",

@@ -5,37 +5,27 @@
 * the half-step-offset k loop of the two wave groups (one barrier per k-step): LDS slabs are complete before they are
   read and never overwritten while still being read.
 
-The arithmetic below restates the kernel's index computations line by line (same names); the GPU tests check the
-kernel itself against f64 and bit-for-bit against the lock-step kernel."""
+The work plans are not restated here: launch_plan, par_plan and vit_large_layer_plans call the code the launcher and the kernel run
+(gigapose_amd/csrc/gp_plan256.h, compiled for the host: gigapose_testing/plan256.py).  The loop model and the strip counter's protocol
+below are host models at the granularity of their barriers / atomic operations; the GPU tests check the kernel itself against f64
+and bit-for-bit against the lock-step kernel."""
 import numpy as np
 import pytest
 
+from gigapose_testing import plan256
+
 
 def launch_plan(T, nstep, dp=True, slots=256):
-    """-> {slot: [(tile, s0, s1, kind)]}, kind in {"dp", "head", "whole", "rest"}; tile is the global chunk-ordered index."""
+    """GpSlotPlan of the serial hand-over builds -> {slot: [(tile, s0, s1, kind)]}, kind in {"dp", "head", "whole", "rest"}; tile is the
+    global chunk-ordered index."""
     plan = {}
     for p in range(slots):
-        x, n, slots_x = p & 7, p >> 3, slots >> 3
-        t_lo = T * x // 8
-        n_t = T * (x + 1) // 8 - t_lo
-        rounds_dp = n_t // slots_x - 1 if (dp and n_t // slots_x > 1) else 0
-        n_dp = rounds_dp * slots_x
-        U = (n_t - n_dp) * nstep
-        u0, u1 = U * n // slots_x, U * (n + 1) // slots_x
-        ta, sa = divmod(u0, nstep)
-        tb, sb = divmod(u1, nstep)
-        n_head, n_rest = (1 if sb > 0 else 0), (1 if sa > 0 else 0)
-        first_whole = ta + n_rest
-        n_seg = rounds_dp + n_head + (tb - first_whole) + n_rest
+        x = p & 7
+        lo, hi = T * x // 8, T * (x + 1) // 8
         segs = []
-        for seg in range(n_seg):
-            is_dp = seg < rounds_dp
-            is_head = (not is_dp) and seg - rounds_dp < n_head
-            is_rest = (not is_dp) and n_rest == 1 and seg == n_seg - 1
-            t = seg * slots_x + n if is_dp else n_dp + (tb if is_head else (ta if is_rest else first_whole + seg - rounds_dp - n_head))
-            assert 0 <= t < n_t and not (is_head and is_rest)
-            s0, s1 = (sa if is_rest else 0), (sb if is_head else nstep)
-            segs.append((t_lo + t, s0, s1, "dp" if is_dp else "head" if is_head else "rest" if is_rest else "whole"))
+        for tile, s0, s1, is_head, is_rest, is_dp in plan256.slot_segments(p, slots, T, nstep, dp, 0):
+            assert lo <= tile < hi and not (is_head and is_rest)
+            segs.append((tile, s0, s1, "dp" if is_dp else "head" if is_head else "rest" if is_rest else "whole"))
         plan[p] = segs
     return plan
 
@@ -167,23 +157,22 @@ def test_strip_fragments_are_handed_out_exactly_once(seed, nslots, nfrag):
 
 
 # ---- the parallel split-K plan (fewer tiles than slots: gemm_planes256_kernel<.., PAR = true>) with the host's cap of at least
-# kParMinSteps k-steps per slot of a split tile (gp_gemm_planes256_launch: a.par = max(1, nstep / kParMinSteps)).
-def par_plan(T, nstep, min_steps=16, slots=256):
-    """-> ({slot: (tile, s0, s1, part, S)} for slots that hold a tile, S per XCD chunk); tile is the global chunk-ordered index."""
-    cap = max(1, nstep // min_steps)
+# kParMinSteps k-steps per slot of a split tile (gp_planes256_plan: par = gp_planes_par_cap = max(1, nstep / kParMinSteps)).
+def par_plan(T, nstep, min_steps=16, slots=256, cap=None):
+    """gp_planes_par_slots + GpSlotPlan -> ({slot: (tile, s0, s1, part, S)} for slots that hold a tile, S per XCD chunk); tile is the global
+    chunk-ordered index.  cap: the launch's cap on slots per tile (default: the one K = 32 nstep gives at min_steps k-steps per slot)."""
+    if cap is None:
+        cap = plan256.planes_par_cap(32 * nstep, dict(planes_par_min_steps=min_steps))
     plan, S_of = {}, {}
     for p in range(slots):
         x, n, slots_x = p & 7, p >> 3, slots >> 3
-        t_lo = T * x // 8
-        n_t = T * (x + 1) // 8 - t_lo
-        par_S = max(1, min(cap, slots_x // max(n_t, 1)))
+        par_S = plan256.planes_par_slots(cap, slots_x, plan256.chunk_tiles(T, x))
         S_of[x] = par_S
-        tile, part = n // par_S, n % par_S
-        if tile < n_t:
-            u0 = tile * nstep + nstep * part // par_S
-            u1 = tile * nstep + nstep * (part + 1) // par_S
-            assert u0 // nstep == tile and (u1 - 1) // nstep == tile
-            plan[p] = (t_lo + tile, u0 - tile * nstep, u1 - tile * nstep, part, par_S)
+        segs = plan256.slot_segments(p, slots, T, nstep, False, par_S)
+        assert len(segs) <= 1                                               # one part of one tile, or nothing
+        for tile, s0, s1, *_ in segs:
+            assert T * x // 8 <= tile < T * (x + 1) // 8 and 0 <= s0 and s1 <= nstep
+            plan[p] = (tile, s0, s1, n % par_S, par_S)                      # slot n holds part n % S of tile n / S of its chunk
     return plan, S_of
 
 
@@ -216,19 +205,20 @@ def test_parallel_split_plan_covers_every_unit_once_with_the_owner_last(T, nstep
 # 256 x 256 tiles fill at most half the 256 slots; the parallel split then runs on twice the tiles with half-size partial accumulators.
 def vit_large_layer_plans(crops, half_tiles=True):
     """-> {gemm: (tile columns, tiles, S, slots busy, partial MB moved)} for q|k|v, proj, fc1, fc2 of a ViT-L layer at `crops` crops."""
-    j_main = (257 * crops) // 256 * 256
+    tokens = 257 * crops
+    hooks = None if half_tiles else dict(planes_half=0)                 # gp_gemm_planes256_set_half_tiles(0)
     out = {}
-    for name, I, K, can_split in (("qkv", 3072, 1024, True), ("proj", 1024, 1024, True), ("fc1", 4096, 1024, False), ("fc2", 1024, 4096, True)):
-        t256 = (I // 256) * (j_main // 256)
-        if t256 >= 256:
-            out[name] = (256, t256, 1, 256, 0.0)
+    # epilogues (gp_vit.hip): q|k|v 7 = bias -> planes, proj / fc2 3 = LayerScale + residual, fc1 6 = GELU -> planes
+    for name, I, K, epilogue in (("qkv", 3072, 1024, 7), ("proj", 1024, 1024, 3), ("fc1", 4096, 1024, 6), ("fc2", 1024, 4096, 3)):
+        launch = plan256.planes256(I, (tokens + 255) // 256 * 256, tokens, K, epilogue, hooks=hooks)
+        assert launch["usable"], (crops, name)
+        T, width = launch["tiles_i"] * launch["tiles_j"], 128 if launch["build"] == "par128" else 256
+        if launch["build"] == "serial":
+            out[name] = (256, T, 1, 256, 0.0)
             continue
-        half = half_tiles and 2 * t256 <= 256
-        T, width = (2 * t256, 128) if half else (t256, 256)
         # the GELU build keeps whole tiles (S = 1); so does (round 5) every 256-wide launch of 129-255 tiles: the launcher takes the
         # PSPLIT = false instantiation for them (an XCD holding exactly 16 of 132 tiles would otherwise have split them two ways)
-        whole = (not can_split) or (width == 256 and T > 128)
-        plan, S_of = par_plan(T, K // 32, 10 ** 9 if whole else 16)
+        plan, S_of = par_plan(T, K // 32, cap=launch["par"] if launch["splits"] else 1)
         S = max(S_of.values())
         partial_mb = sum(1 for (_, _, _, part, s) in plan.values() if part < s - 1) * 256 * width * 4 / 1e6
         out[name] = (width, T, S, len(plan), partial_mb)
